@@ -19,6 +19,9 @@ ball query, fused grouped MLP, FPS 512->128, ball query, fused MLP, group-all ML
 FK + robot-cloud refresh in place -> swept-sphere SDF collision check of the new configuration.
 fp32 end to end (fp32 MFMA for every contraction).
 
+`--dump-outputs DIR` writes what the last timed step computed (joint angles, collision flags, a fixed sample of the
+refreshed point clouds) to DIR/<name>.npy: same arguments, same inputs, so two builds can be compared output for output.
+
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the SA2 fused grouped MLP),
 timed live with HIP events on the launch stream inside the timed region; `cpu_baseline` is the
 oracle (a port, not the product) timed on this host's cores on a bounded sample.
@@ -42,6 +45,14 @@ import torch
 SA1_FLOPS = 65536 * 8448 * 2  # 512*128 rows x (4*64 + 64*64 + 64*64) MACs     
 SA2_FLOPS = 16384 * 57728 * 2  # 128*128 rows x (67*128 + 128*128 + 128*256) MACs
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
+
+
+def host_cpus() -> int:
+    """CPUs this process may run on: its affinity mask, capped by OMP_NUM_THREADS when that is set (a job share of a
+    larger host; os.cpu_count() counts the whole machine)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else int(os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(omp))) if omp.isdigit() and int(omp) > 0 else max(1, n)
 
 
 def cpu_step(orc, ft, sd, xyz, qn, prim, tables, torch_threads=0):
@@ -87,10 +98,11 @@ def _cpu_worker(args):
 
 
 def cpu_baseline(prob, model, n_env: int):
-    """Oracle (CPU port) timed on `n_env` env-steps of the same workload on ALL host cores.  One process
-    does not use 256 cores on this op mix (measured on the box: the torch fp32 restatement peaks at 16-32 threads, 22
-    env-steps/s, and drops to 3 with 256), so the sample is cut over host_cores / 16 worker processes of 16 threads each
-    (C parts OpenMP-parallel over environments, grouping / MLPs / heads as the oracle's torch restatement in fp32);
+    """Oracle (CPU port) timed on `n_env` env-steps of the same workload on every host core this process may use
+    (host_cpus()).  One process does not use 256 cores on this op mix (measured on the box: the torch
+    fp32 restatement peaks at 16-32 threads, 22 env-steps/s, and drops to 3 with 256), so the sample is cut over
+    host_cores / 16 worker processes of 16 threads each (C parts OpenMP-parallel over environments, grouping / MLPs /
+    heads as the oracle's torch restatement in fp32);
     `cores` = processes x threads.  The workers start together behind a barrier; the time is first start -> last end.
     `scalar_1t`: the same step on 8 environments in this process with the C parts on ONE thread and the float64 numpy
     MLPs (what rounds 1-3 reported)."""
@@ -101,7 +113,7 @@ def cpu_baseline(prob, model, n_env: int):
     from oracle import oracle as orc
 
     orc.build()
-    host = int(os.cpu_count() or 1)
+    host = host_cpus()
     sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
     tables = (ft.collision_sphere_table(False)[:3], ft.link_point_table())
     prim_keys = [k for k in prob if k.startswith(("cuboid_", "cylinder_"))]
@@ -244,6 +256,43 @@ HEAD_MACS = (1024 * 4096 + 4096 * 2048 + 2048 * 2048 + 7 * 32 + 32 * 64 + 64 * 1
              + 2112 * 512 + 512 * 256 + 256 * 128 + 128 * 7)
 
 
+DUMP_ENVS, DUMP_CLOUDS, DUMP_SEED = 65536, 128, 20240601  # --dump-outputs: ~17 MB at most
+
+
+def dump_sample(global_envs: int):
+    """The global environment ids whose outputs --dump-outputs writes: all of them up to DUMP_ENVS (a fixed, seeded
+    sample beyond), and a fixed, seeded DUMP_CLOUDS of those for the point clouds.  Depends on `global_envs` only."""
+    rng = np.random.default_rng(DUMP_SEED)
+    ids = np.arange(global_envs) if global_envs <= DUMP_ENVS else np.sort(rng.choice(global_envs, DUMP_ENVS, replace=False))
+    clouds = np.sort(rng.choice(ids, min(DUMP_CLOUDS, ids.size), replace=False))
+    return ids, clouds
+
+
+def step_outputs(eng, envs: range, global_envs: int) -> dict:
+    """This rank's share of what a caller of RolloutEngine.step() holds after the step, as float32 host arrays
+    (environment ids float64): joint angles `q` (radians) and `q_norm` ([-1, 1]) [n, 7], collision flags `collision`
+    [n] and the refreshed point clouds `xyz` [m, 6272, 4] (robot | scene | target points, 4th column the label), for
+    the rows of dump_sample()."""
+    ids, clouds = dump_sample(global_envs)
+    rows = lambda g: torch.from_numpy(g[(g >= envs.start) & (g < envs.stop)] - envs.start).to(eng.device)
+    r, c = rows(ids), rows(clouds)
+    return {"env_ids": (r.cpu().numpy() + envs.start).astype(np.float64), "q": eng.q[r].cpu().numpy(),
+            "q_norm": eng.q_norm[r].cpu().numpy(), "collision": eng.flags[r].float().cpu().numpy(),
+            "cloud_env_ids": (c.cpu().numpy() + envs.start).astype(np.float64), "xyz": eng.xyz[c].cpu().numpy()}
+
+
+def write_outputs(out_dir: str, parts: list) -> dict:
+    """Rank 0: the ranks' step_outputs() joined in global environment order -> out_dir/<name>.npy; returns the shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name in parts[0]:
+        a = np.concatenate([p[name] for p in parts], axis=0)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def spawn_ranks_if_needed(args) -> bool:
     """`python bench.py --gpus N` (N > 1) outside a torchrun job: start the N ranks ourselves and exit with their
     status.  Returns True when the ranks of THIS job share GPUs (development mode, MPX_SHARE_GPU=1)."""
@@ -287,7 +336,11 @@ def main():
     ap.add_argument("--global-envs", type=int, default=8192, help="total environments of a --scaling strong run")
     ap.add_argument("--train-steps", type=int, default=10, help="timed steps of the row-N1 training-step extra (0 = skip); the figure is the MEDIAN step, after 3 untimed ones")
     ap.add_argument("--scene-pool", type=int, default=1024, help="distinct host-generated primitive sets tiled over the batch (clouds are drawn per env on the device)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see step_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     shared_devices = spawn_ranks_if_needed(args)
 
     from mpinets_amd import _lib, shard
@@ -342,6 +395,12 @@ def main():
     shard.barrier()
     elapsed = time.perf_counter() - t0
     prof = _lib.profile_stop()
+    dumped = None
+    if args.dump_outputs:  # (after the timed region, before the extras below move the rollout on)
+        parts = shard.gather_objects(step_outputs(eng, envs, global_envs))
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs, "arrays": write_outputs(args.dump_outputs, parts)}
+        del parts
     elapsed_local = elapsed
     elapsed = shard.max_over_ranks(elapsed, dev)
     # self-check record of an N-rank run: which communicator, which device every rank ran on, every rank's own time
@@ -595,7 +654,7 @@ def main():
             from oracle import oracle as orc
 
             orc.build()
-            cpu_threads = orc.set_threads(int(os.cpu_count() or 1))
+            cpu_threads = orc.set_threads(host_cpus())
             c_, r_, l_, _ = ft.collision_sphere_table(False)
             host_prims = lambda n: {k: prob[k][:n].cpu().numpy() for k in prob if k.startswith(("cuboid_", "cylinder_"))}
 
@@ -758,6 +817,8 @@ def main():
         "dist_backend": dist_backend, "rccl_ranks": n_gpus if dist_backend == "nccl" else 0,
         "ranks": rank_records,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if extra:
         out["extra_configs"] = extra
     if all_slots is not None:
