@@ -332,6 +332,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   static_assert(Y_STAGES == 3, "the slab loop is written for a three-stage ring (st1 / st2 arithmetic, the 6-way unroll, kb % 3)");
   static_assert(LPS == Y_BM / 64 + Y_BN / 64 && Y_BM == 256 && Y_BN == 128,
                 "WAIT_ONE counts the loads one dma() issues per wave: 16 rows each, a wave brings 64 rows of A and 32 of B");
+  // (the counts assume no scratch traffic -- a spill adds vector-memory operations: tests/test_code_objects.py asserts
+  // zero private segment and zero spills for OUT = 0..3)
   constexpr int WAIT_ONE = 0x0070 | LPS;       // vmcnt(6), lgkmcnt(0): everything but the youngest slab has landed
   constexpr int WAIT_ALL = 0x0070;             // vmcnt(0), lgkmcnt(0)
   // Software pipeline of a slab (24 MFMAs per wave): the B fragments and A tiles 0-1 of slab k+1 are read into a second

@@ -193,6 +193,8 @@ __global__ void __launch_bounds__(64 * sa3f::WV) __attribute__((amdgpu_waves_per
   // for the stores too (as a plain vmcnt(LPC) does) held every wave for ~10 k cycles behind each group's 64 scattered stores.
   // Chunks past the end of the pack are requested like the others (the descriptor's range check answers zeros into a stage
   // nobody reads any more): every barrier then sees the same number of younger loads, also inside the rolled loop of layer 2.
+  // The count holds only while the kernel has no scratch traffic (a spill adds vector-memory operations to the same counter):
+  // tests/test_code_objects.py asserts zero private segment and zero spills for every instantiation.
   auto open_chunk = [&](auto C, auto YS, int dyn_bytes) __attribute__((always_inline)) {
     constexpr int c = decltype(C)::value, younger_stores = decltype(YS)::value;
     constexpr int n = LPC + younger_stores;
