@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .pointnet2 import (PRECISIONS, PointnetSAModule, SplitWeights, groupnorm_leaky, groupnorm_leaky_train,
+from .pointnet2 import (PRECISIONS, DerivedWeights, PointnetSAModule, SplitWeights, groupnorm_leaky, groupnorm_leaky_train,
                         launch_sa, linear, linear_train, linear_x3, mlp_chain_train, sa_mlp_factored, use_factored)
 from .utils import unnormalize_franka_joints
 
@@ -48,6 +48,11 @@ def side_stream(device) -> "torch.cuda.Stream":
     return st
 
 
+def _chunks(n: int, step: int):
+    """(start, count) of the consecutive runs of at most ``step`` of ``n`` environments."""
+    return ((b0, min(step, n - b0)) for b0 in range(0, n, step))
+
+
 class MPiNetsPointNet(nn.Module):
     """PointNet++ encoder of the reference (model.py:355-426)."""
 
@@ -69,15 +74,11 @@ class MPiNetsPointNet(nn.Module):
             nn.LeakyReLU(inplace=True),
             nn.Linear(2048, 2048),
         )
-        self._sa3_w0 = None  # first group-all layer with K padded 259 -> 272 (whole 16-float slabs: direct-to-LDS GEMM)
-        self._sa3_pk = None  # (key, mpx_sa3_pack_weights of the group-all module)
-        self._sa3_fp = None  # (key, mpx_sa3_front_bf16x3_pack, last layer's permuted weight pairs): bf16x3 mode
         # bf16x3 only: the group-all module's first two layers as one kernel (default) or layer by layer (the round-5 form,
         # bit-identical to the chain through fp32 rows; kept for the tests that pin the fused kernel to it)
         self.sa3_front_fused = True
         self.dense_precision = "fp32"  # "bf16x3": the large dense layers on the bf16 matrix cores (set_precision)
         self.train_precision = "fp32"  # "bf16x3": the grouped / group-all MLPs' training GEMMs in split bf16 (set_training_precision)
-        self._split = SplitWeights()
         # bf16x3 only: keep the group-all MLP's activations in the split "pairs" form between layers (default) or as
         # fp32 rows that every layer splits again on its way in -- bit-identical results (tests), pairs are faster
         self.dense_through_pairs = True
@@ -86,60 +87,58 @@ class MPiNetsPointNet(nn.Module):
         # +5.5 % time -- every launch has a tail); larger ones (the whole 65 536-environment configuration) in slabs of <= 8192.
         # Slabs stay above 1024 environments for chunk >= 2048, i.e. inside the dense layers' large-batch launch shape.
         self.workspace_chunk = 8192
+        self._derived = SplitWeights()  # (its pairs entries are named by their layer)
 
-    def _lin(self, x, weight, bias, act=0, out=None, source=None):
+    def _lin(self, x, layer, act=ACT_NONE, out=None, weight=None):
+        """``layer`` on the rows ``x`` in the dense precision; ``weight``: its [out, in] matrix when that is not
+        ``layer.weight`` itself (1x1 convolutions, padded copies)."""
+        w = layer.weight if weight is None else weight
         if self.dense_precision == "bf16x3":
-            return linear_x3(x, weight, bias, act, self._split, out=out, source=source)
-        return linear(x, weight, bias, act, out=out)
+            return linear_x3(x, w, layer.bias, act, self._derived, out=out, source=layer.weight, name=layer)
+        return linear(x, w, layer.bias, act, out=out)
 
-    def _sa3_through_pairs(self, h: torch.Tensor, c3, B: int, pooled_pairs: bool = False) -> torch.Tensor:
+    def _pairs(self, layer, weight=None) -> torch.Tensor:
+        """``layer``'s weight matrix (``weight``: when that is not ``layer.weight`` itself) in the ``bf16x3`` pairs form."""
+        return self._derived.get(layer.weight if weight is None else weight, layer.weight, layer)
+
+    def _sa3_through_pairs(self, h: torch.Tensor, c3, B: int, pooled_pairs: bool) -> torch.Tensor:
         """The group-all MLP in ``bf16x3`` with its intermediate activations kept in the kernels' pairs form (hi / lo
         bf16 per 16 k-values: the operand of the next layer, staged by DMA and split once, by the epilogue that makes
         them) instead of fp32 rows.  Bit-identical to the fp32-row chain (same split, same accumulation order).  Rows
-        go in chunks that keep an operand under the 4 GB a buffer descriptor spans."""
+        go in chunks that keep an operand under the 4 GB a buffer descriptor spans.  -> the pooled rows, fp32 [B, C3]
+        or with ``pooled_pairs`` in the pairs form [B, 2 * C3]."""
         lib, dev = _lib, h.device
-        front = self._sa3_front_pack(h.size(1)) if self.sa3_front_fused else None
+        n1, n2, n3 = (c.out_channels for c in c3)
+        front = self._sa3_pack(h.size(1), front=True) if self.sa3_front_fused else None
         if front is not None:
             # layers 1-2 as ONE kernel (rows divided among the waves, activations in registers, the weights through an LDS
             # ring once per environment: csrc/sa3_front_bf16.hip); its rows carry their k-steps in the kernel's channel
             # order, the last layer's weight pairs have their columns permuted to match.  Equal to the layer-by-layer form
             # to rounding (1e-7 relative), not bit for bit.
             pack, w3p = front
-            n2, n3 = c3[1].out_channels, c3[2].out_channels
-            pooled = (torch.empty((B, 2 * n3), dtype=torch.bfloat16, device=dev) if pooled_pairs else
-                      torch.empty((B, n3), dtype=torch.float32, device=dev))
             step = max(1, min(65535, ((1 << 32) - 4096) // (128 * 4 * n2)))  # environments per call (4 GB descriptors)
-            p2 = torch.empty((min(step, B) * 128, 2 * n2), dtype=torch.bfloat16, device=dev)
-            for b0 in range(0, B, step):
-                nb = min(step, B - b0)
-                lib.call("mpx_sa3_front_bf16x3", lib.ptr(h[b0 * 128:]), h.stride(0), nb, 128, lib.ptr(pack), lib.ptr(p2), 2 * n2)
-                lib.call("mpx_linear_rowmax_bf16x3_pairs", lib.ptr(p2), 2 * n2, lib.ptr(w3p), lib.ptr(c3[2].bias), nb * 128, n3, n2,
-                         128, None if pooled_pairs else lib.ptr(pooled[b0:]), 0 if pooled_pairs else pooled.stride(0),
-                         lib.ptr(pooled[b0:]) if pooled_pairs else None, pooled.stride(0) if pooled_pairs else 0)
-            return pooled
-        w = [self._sa3_first_weight(), c3[1].weight.view(c3[1].out_channels, -1), c3[2].weight.view(c3[2].out_channels, -1)]
-        wp = [self._split.get(w[0], c3[0].weight), self._split.get(w[1]), self._split.get(w[2])]
-        n1, n2, n3 = (x.size(0) for x in w)
+        else:
+            w0 = self._sa3_first_weight()
+            wp0 = self._pairs(c3[0], w0)
+            wp1, w3p = self._pairs(c3[1], c3[1].weight.flatten(1)), self._pairs(c3[2], c3[2].weight.flatten(1))
+            step = max(1, min(65535, ((1 << 32) - 4096) // (128 * 4 * max(n1, n2))))
+            p1 = torch.empty((min(step, B) * 128, 2 * n1), dtype=torch.bfloat16, device=dev)
         pooled = (torch.empty((B, 2 * n3), dtype=torch.bfloat16, device=dev) if pooled_pairs else
                   torch.empty((B, n3), dtype=torch.float32, device=dev))
-        step = max(1, min(65535, ((1 << 32) - 4096) // (128 * 4 * max(n1, n2))))  # environments per call
-        nb0 = min(step, B)
-        p1 = torch.empty((nb0 * 128, 2 * n1), dtype=torch.bfloat16, device=dev)
-        p2 = torch.empty((nb0 * 128, 2 * n2), dtype=torch.bfloat16, device=dev)
-        for b0 in range(0, B, step):
-            nb = min(step, B - b0)
-            M = nb * 128
+        p2 = torch.empty((min(step, B) * 128, 2 * n2), dtype=torch.bfloat16, device=dev)
+        for b0, nb in _chunks(B, step):
             x = h[b0 * 128:]
-            lib.call("mpx_linear_bf16x3_to_pairs", lib.ptr(x), h.stride(0), lib.ptr(wp[0]), lib.ptr(c3[0].bias), M, n1,
-                     w[0].size(1), ACT_RELU, lib.ptr(p1), 2 * n1)
-            lib.call("mpx_linear_bf16x3_pairs", lib.ptr(p1), 2 * n1, lib.ptr(wp[1]), lib.ptr(c3[1].bias), M, n2, n1, ACT_RELU,
-                     None, 0, lib.ptr(p2), 2 * n2)
-            if pooled_pairs:
-                lib.call("mpx_linear_rowmax_bf16x3_pairs", lib.ptr(p2), 2 * n2, lib.ptr(wp[2]), lib.ptr(c3[2].bias), M, n3,
-                         n2, 128, None, 0, lib.ptr(pooled[b0:]), pooled.stride(0))
+            if front is not None:
+                lib.call("mpx_sa3_front_bf16x3", lib.ptr(x), h.stride(0), nb, 128, lib.ptr(pack), lib.ptr(p2), 2 * n2)
             else:
-                lib.call("mpx_linear_rowmax_bf16x3_pairs", lib.ptr(p2), 2 * n2, lib.ptr(wp[2]), lib.ptr(c3[2].bias), M, n3,
-                         n2, 128, lib.ptr(pooled[b0:]), pooled.stride(0), None, 0)
+                lib.call("mpx_linear_bf16x3_to_pairs", lib.ptr(x), h.stride(0), lib.ptr(wp0), lib.ptr(c3[0].bias), nb * 128, n1,
+                         w0.size(1), ACT_RELU, lib.ptr(p1), 2 * n1)
+                lib.call("mpx_linear_bf16x3_pairs", lib.ptr(p1), 2 * n1, lib.ptr(wp1), lib.ptr(c3[1].bias), nb * 128, n2, n1,
+                         ACT_RELU, None, 0, lib.ptr(p2), 2 * n2)
+            dst = (lib.ptr(pooled[b0:]), pooled.stride(0))
+            rows, pairs = ((None, 0), dst) if pooled_pairs else (dst, (None, 0))
+            lib.call("mpx_linear_rowmax_bf16x3_pairs", lib.ptr(p2), 2 * n2, lib.ptr(w3p), lib.ptr(c3[2].bias), nb * 128, n3, n2,
+                     128, *rows, *pairs)
         return pooled
 
     @staticmethod
@@ -168,7 +167,7 @@ class MPiNetsPointNet(nn.Module):
             N, K = lin.weight.shape
             last = gi is None
             y = out if (last and out is not None) else torch.empty((B, N), dtype=torch.float32, device=dev)
-            lib.call("mpx_linear_bf16x3_pairs", lib.ptr(h), h.stride(0), lib.ptr(self._split.get(lin.weight)), lib.ptr(lin.bias),
+            lib.call("mpx_linear_bf16x3_pairs", lib.ptr(h), h.stride(0), lib.ptr(self._pairs(lin)), lib.ptr(lin.bias),
                      B, N, K, ACT_NONE, lib.ptr(y), y.stride(0), None, 0)
             if last:
                 return y
@@ -179,11 +178,17 @@ class MPiNetsPointNet(nn.Module):
 
     def _fc(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         fc = self.fc_layer
-        h = self._lin(x, fc[0].weight, fc[0].bias)
+        h = self._lin(x, fc[0])
         h = groupnorm_leaky(h, fc[1].weight, fc[1].bias, fc[1].num_groups, fc[1].eps, out=h)
-        h = self._lin(h, fc[3].weight, fc[3].bias)
+        h = self._lin(h, fc[3])
         h = groupnorm_leaky(h, fc[4].weight, fc[4].bias, fc[4].num_groups, fc[4].eps, out=h)
-        return self._lin(h, fc[6].weight, fc[6].bias, out=out)
+        return self._lin(h, fc[6], out=out)
+
+    def _keep(self, stages: Dict[str, torch.Tensor], pooled: torch.Tensor, aux: Optional[dict]) -> None:
+        """The distinct-neighbour counts of the latest forward (bench accounting); with ``aux``, its intermediates."""
+        self.last_counts = (stages["ball_cnt1"], stages["ball_cnt2"])
+        if aux is not None:
+            aux.update(stages, f3=pooled)
 
     def forward_train(self, point_cloud: torch.Tensor, aux: Optional[dict] = None) -> torch.Tensor:
         """Differentiable forward (training_step, model.py:185-240): sampling / neighbour search / grouping /
@@ -225,62 +230,50 @@ class MPiNetsPointNet(nn.Module):
         seg = torch.arange(B + 1, dtype=torch.int64, device=dev) * sa2.npoint
         pooled = mlp_chain_train(h.view(B * sa2.npoint, -1), [(c.weight.view(c.out_channels, -1), c.bias) for c in sa3.convs()],
                                  [ACT_RELU] * 3, offsets=seg, precision=tp, offsets_checked=True)
-        self.last_counts = (cnt1, cnt2)
-        if aux is not None:
-            aux.update(fps_idx1=idx1, xyz1=xyz1, ball_idx1=nbr1, ball_cnt1=cnt1, f1=f1, fps_idx2=idx2, ball_idx2=nbr2,
-                       ball_cnt2=cnt2, f3=pooled)
+        self._keep(dict(fps_idx1=idx1, xyz1=xyz1, ball_idx1=nbr1, ball_cnt1=cnt1, f1=f1, fps_idx2=idx2, ball_idx2=nbr2,
+                        ball_cnt2=cnt2), pooled, aux)
         fc = self.fc_layer  # Linear -> GroupNorm -> LeakyReLU (x2) -> Linear
         h = groupnorm_leaky_train(linear_train(pooled, fc[0].weight, fc[0].bias), fc[1])
         h = groupnorm_leaky_train(linear_train(h, fc[3].weight, fc[3].bias), fc[4])
         return linear_train(h, fc[6].weight, fc[6].bias)
 
     def _sa3_first_weight(self) -> torch.Tensor:
+        """The group-all module's first layer with K padded 259 -> 272 (whole 16-float slabs: direct-to-LDS GEMM)."""
         conv = self.SA_modules[2].convs()[0]
-        key = (conv.weight._version, conv.weight.data_ptr())
-        if self._sa3_w0 is None or self._sa3_w0[0] != key:
+
+        def make():
             w = conv.weight.detach().reshape(conv.out_channels, -1)
-            self._sa3_w0 = (key, torch.nn.functional.pad(w, (0, (-w.size(1)) % 16)).contiguous())
-        return self._sa3_w0[1]
+            return torch.nn.functional.pad(w, (0, (-w.size(1)) % 16)).contiguous()
 
-    def _sa3_front_pack(self, K3: int):
-        """(weight pack of ``mpx_sa3_front_bf16x3``, the last layer's weight pairs in its channel order), or None when the
-        group-all MLP does not have the widths the kernel is built for."""
+        return self._derived.entry("sa3_w0", (conv.weight,), make)
+
+    def _sa3_pack(self, K3: int, front: bool = False):
+        """The group-all module's weights packed for ``mpx_sa3_chain`` (its three layers) or, with ``front``, for
+        ``mpx_sa3_front_bf16x3`` (its first two layers; returned with the last layer's weight pairs in that kernel's
+        channel order).  None: the kernel is not built for these widths."""
         c3 = self.SA_modules[2].convs()
-        dims = (K3, c3[0].out_channels, c3[1].out_channels)
-        n = _lib.load().mpx_sa3_front_bf16x3_pack_size(*dims)
-        if n < 0 or c3[2].out_channels % 16:
+        n1, n2, n3 = (c.out_channels for c in c3)
+        lib, p = _lib.load(), _lib.ptr
+        n = lib.mpx_sa3_front_bf16x3_pack_size(K3, n1, n2) if front else lib.mpx_sa3_pack_size(K3, n1, n2, n3)
+        if n < 0 or (front and n3 % 16):
             return None
-        ps = [p for c in c3 for p in (c.weight, c.bias)]
-        key = tuple((p._version, p.data_ptr()) for p in ps) + dims
-        if self._sa3_fp is None or self._sa3_fp[0] != key:
-            dev = c3[0].weight.device
+
+        def make():
             w = [_lib.f32c(c.weight.detach().view(c.out_channels, -1)) for c in c3]
             b = [_lib.f32c(c.bias.detach()) for c in c3]
-            pack = torch.empty(n, dtype=torch.uint8, device=dev)
-            _lib.call("mpx_sa3_front_bf16x3_pack", _lib.ptr(w[0]), w[0].size(1), _lib.ptr(b[0]), _lib.ptr(w[1]), _lib.ptr(b[1]), *dims,
-                      _lib.ptr(pack))
-            w3p = torch.empty((w[2].size(0), 2 * w[2].size(1)), dtype=torch.bfloat16, device=dev)
-            _lib.call("mpx_sa3_front_bf16x3_w3_pairs", _lib.ptr(w[2]), w[2].size(0), w[2].size(1), _lib.ptr(w3p))
-            self._sa3_fp = (key, pack, w3p)
-        return self._sa3_fp[1], self._sa3_fp[2]
+            if not front:
+                pack = torch.empty(n, dtype=torch.float32, device=w[0].device)
+                _lib.call("mpx_sa3_pack_weights", p(w[0]), w[0].size(1), p(b[0]), p(w[1]), p(b[1]), p(w[2]), p(b[2]), K3, n1,
+                          n2, n3, p(pack))
+                return pack
+            pack = torch.empty(n, dtype=torch.uint8, device=w[0].device)
+            _lib.call("mpx_sa3_front_bf16x3_pack", p(w[0]), w[0].size(1), p(b[0]), p(w[1]), p(b[1]), K3, n1, n2, p(pack))
+            w3p = torch.empty((n3, 2 * w[2].size(1)), dtype=torch.bfloat16, device=w[0].device)
+            _lib.call("mpx_sa3_front_bf16x3_w3_pairs", p(w[2]), n3, w[2].size(1), p(w3p))
+            return pack, w3p
 
-    def _sa3_pack(self, K3: int) -> Optional[torch.Tensor]:
-        """The group-all module's three layers in the stream order of ``mpx_sa3_chain`` (None: unsupported widths)."""
-        c3 = self.SA_modules[2].convs()
-        dims = (K3, c3[0].out_channels, c3[1].out_channels, c3[2].out_channels)
-        n = _lib.load().mpx_sa3_pack_size(*dims)
-        if n < 0:
-            return None
-        ps = [p for c in c3 for p in (c.weight, c.bias)]
-        key = tuple((p._version, p.data_ptr()) for p in ps) + dims
-        if self._sa3_pk is None or self._sa3_pk[0] != key:
-            pack = torch.empty(n, dtype=torch.float32, device=c3[0].weight.device)
-            w = [_lib.f32c(c.weight.detach().view(c.out_channels, -1)) for c in c3]
-            b = [_lib.f32c(c.bias.detach()) for c in c3]
-            _lib.call("mpx_sa3_pack_weights", _lib.ptr(w[0]), w[0].size(1), _lib.ptr(b[0]), _lib.ptr(w[1]), _lib.ptr(b[1]),
-                      _lib.ptr(w[2]), _lib.ptr(b[2]), *dims, _lib.ptr(pack))
-            self._sa3_pk = (key, pack)
-        return self._sa3_pk[1]
+        return self._derived.entry(("sa3_front" if front else "sa3_chain", K3), [t for c in c3 for t in (c.weight, c.bias)],
+                                 make)
 
     def forward(self, point_cloud: torch.Tensor, out: Optional[torch.Tensor] = None,
                 aux: Optional[dict] = None, side_work: Optional[Callable[[], object]] = None) -> torch.Tensor:
@@ -302,8 +295,7 @@ class MPiNetsPointNet(nn.Module):
                 raise _lib.MpxError("out= is an inference-path argument")
             return enc
         pc = _lib.f32c(point_cloud)
-        B, N, _ = pc.shape
-        dev = pc.device
+        B = pc.size(0)
         chunk = self.workspace_chunk
         if chunk and aux is None and B > chunk:
             # Large batches go through the encoder in slabs of <= `workspace_chunk` environments: the intermediates
@@ -314,7 +306,7 @@ class MPiNetsPointNet(nn.Module):
             if side_work is not None:
                 side_work()
             if out is None:
-                out = torch.empty((B, self.fc_layer[6].out_features), dtype=torch.float32, device=dev)
+                out = torch.empty((B, self.fc_layer[6].out_features), dtype=torch.float32, device=pc.device)
             counts = []
             n_slabs = -(-B // chunk)
             for i in range(n_slabs):  # near-equal slabs: no small tail with other launch shapes
@@ -323,9 +315,21 @@ class MPiNetsPointNet(nn.Module):
                 counts.append(self.last_counts)
             self.last_counts = tuple(torch.cat([c[k] for c in counts]) for k in (0, 1))
             return out
-        sa1, sa2, sa3 = self.SA_modules
+        stages = self._sa1_sa2(pc, aux, side_work)
+        sa3_in = stages["sa3_in"]
+        pooled = self._group_all(sa3_in.view(B * sa3_in.size(1), sa3_in.size(2)), B, want_pairs=aux is None)
+        self._keep(stages, pooled, aux)
+        if pooled.dtype == torch.bfloat16:
+            return self._fc_through_pairs(pooled, out=out)
+        return self._fc(pooled, out=out)
+
+    def _sa1_sa2(self, pc: torch.Tensor, aux: Optional[dict], side_work) -> Dict[str, torch.Tensor]:
+        """Sampling, neighbour search and the two grouped modules -> their results under their ``aux`` names, and
+        ``sa3_in``: the group-all module's input rows [B, 128, K3] = [xyz2 | f2 | 0]."""
+        B, N, _ = pc.shape
+        dev = pc.device
+        sa1, sa2, _ = self.SA_modules
         lib = _lib
-        # ---- SA1 -------------------------------------------------------------------------------
         idx1 = torch.empty((B, sa1.npoint), dtype=torch.int32, device=dev)
         xyz1 = torch.empty((B, sa1.npoint, 3), dtype=torch.float32, device=dev)
         lib.call("mpx_fps", lib.ptr(pc), B, N, 4, sa1.npoint, lib.ptr(idx1), lib.ptr(xyz1), 3)
@@ -355,102 +359,83 @@ class MPiNetsPointNet(nn.Module):
         # or with padding elision off, the rows are padded like pointnet2_ops pads them.
         bq1 = "mpx_ball_query_hits" if (aux is None and sa1.elide_padding) else "mpx_ball_query"
         bq2 = "mpx_ball_query_hits" if (aux is None and sa2.elide_padding) else "mpx_ball_query"
+        want_rows = use_factored(sa2, C1o, c2)
 
         def sample_sa2():  # needs only xyz1
             lib.call("mpx_fps", lib.ptr(xyz1), B, sa1.npoint, 3, sa2.npoint, lib.ptr(idx2), lib.ptr(sa3_in), K3)
             lib.call(bq2, lib.ptr(sa3_in), K3, lib.ptr(xyz1), 3, B, sa1.npoint, sa2.npoint,
                      float(sa2.radius), sa2.nsample, lib.ptr(nbr2), lib.ptr(cnt2))
 
-        def module_sa1():
+        def module_sa1() -> bool:
             lib.call(bq1, lib.ptr(xyz1), 3, lib.ptr(pc), 4, B, N, sa1.npoint, float(sa1.radius),
                      sa1.nsample, lib.ptr(nbr1), lib.ptr(cnt1))
             # (SA1 also completes its rows to [f1 | xyz1 | 0] when SA2's first layer is evaluated per point)
-            state["centre_done"] = launch_sa(sa1.precision, lib.ptr(pc), 4, lib.ptr(xyz1), 3, lib.ptr(pc) + 12, 4, 1, nbr1,
-                                             cnt1 if sa1.elide_padding else None, B, N, sa1.npoint, sa1.nsample, w1,
-                                             tuple(c.out_channels for c in c1), lib.ptr(f1), f1.stride(1),
-                                             append_centre=want_rows)
+            return launch_sa(sa1.precision, lib.ptr(pc), 4, lib.ptr(xyz1), 3, lib.ptr(pc) + 12, 4, 1, nbr1,
+                             cnt1 if sa1.elide_padding else None, B, N, sa1.npoint, sa1.nsample, w1,
+                             tuple(c.out_channels for c in c1), lib.ptr(f1), f1.stride(1), append_centre=want_rows)
 
-        want_rows = use_factored(sa2, C1o, c2)
-        state = {"centre_done": False}
-        keep = None
         if B <= OVERLAP_MAX_BATCH:  # two independent chains, two streams (buffers were allocated above, on `main`)
             main, side = torch.cuda.current_stream(), side_stream(dev)
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 sample_sa2()
-                if side_work is not None:
-                    keep = side_work()  # (its temporaries stay referenced until `main` has waited for `side`)
-            module_sa1()
+                # (side_work's temporaries stay referenced until `main` has waited for `side`)
+                keep = side_work() if side_work is not None else None
+            centre_done = module_sa1()
             main.wait_stream(side)
+            del keep
         else:
             if side_work is not None:
                 side_work()
-            module_sa1()
+            centre_done = module_sa1()
             sample_sa2()
-        del keep
         if want_rows:
-            if not state["centre_done"]:
+            if not centre_done:
                 lib.call("mpx_append_columns", lib.ptr(xyz1), 3, 3, 1, B * sa1.npoint, lib.ptr(f1buf), C1o + 4, C1o)
             sa_mlp_factored(f1buf.view(B * sa1.npoint, C1o + 4), sa3_in.view(B * sa2.npoint, K3)[:, :4], nbr2,
                             cnt2 if sa2.elide_padding else torch.full_like(cnt2, sa2.nsample), sa2._packed, c2, C1o,
-                            sa1.npoint, lib.ptr(sa3_in) + 12, K3, precision=sa2.precision, split=self._split)
+                            sa1.npoint, lib.ptr(sa3_in) + 12, K3, precision=sa2.precision)
         else:
             w2 = sa2._packed.get(c2, C1o, sa2.precision)
             launch_sa(sa2.precision, lib.ptr(xyz1), 3, lib.ptr(sa3_in), K3, lib.ptr(f1), f1.stride(1), C1o, nbr2,
                       cnt2 if sa2.elide_padding else None, B, sa1.npoint, sa2.npoint, sa2.nsample, w2,
                       tuple(c.out_channels for c in c2), lib.ptr(sa3_in) + 12, K3)
-        # ---- SA3 (group-all): three GEMMs over B*128 rows + max over each environment's rows ------------
-        c3 = sa3.convs()
-        h = sa3_in.view(B * sa2.npoint, K3)
-        if (self.dense_precision == "bf16x3" and sa2.npoint == 128 and self.dense_through_pairs
-                and all(c.out_channels % 16 == 0 for c in c3)):
-            self.last_counts = (cnt1, cnt2)
-            if aux is None and c3[2].out_channels % 16 == 0:  # (aux wants the pooled features as fp32)
-                return self._fc_through_pairs(self._sa3_through_pairs(h, c3, B, pooled_pairs=True), out=out)
-            pooled = self._sa3_through_pairs(h, c3, B)
-            if aux is not None:
-                aux.update(fps_idx1=idx1, xyz1=xyz1, ball_idx1=nbr1, ball_cnt1=cnt1, f1=f1, fps_idx2=idx2, ball_idx2=nbr2,
-                           ball_cnt2=cnt2, sa3_in=sa3_in, f3=pooled)
-            return self._fc(pooled, out=out)
-        pack3 = (self._sa3_pack(K3) if self.dense_precision == "fp32" and sa2.npoint == 128 and B >= SA3_CHAIN_MIN_BATCH
-                 else None)
-        if pack3 is not None:  # the whole module as one kernel: nothing between the rows and the pooled row in HBM
-            pooled = torch.empty((B, c3[2].out_channels), dtype=torch.float32, device=dev)
-            lib.call("mpx_sa3_chain", lib.ptr(h), K3, B, 128, lib.ptr(pack3), K3, c3[0].out_channels, c3[1].out_channels,
-                     c3[2].out_channels, lib.ptr(pooled), pooled.stride(0))
-            self.last_counts = (cnt1, cnt2)
-            if aux is not None:
-                aux.update(fps_idx1=idx1, xyz1=xyz1, ball_idx1=nbr1, ball_cnt1=cnt1, f1=f1, fps_idx2=idx2, ball_idx2=nbr2,
-                           ball_cnt2=cnt2, sa3_in=sa3_in, f3=pooled)
-            return self._fc(pooled, out=out)
-        h = self._lin(h, self._sa3_first_weight(), c3[0].bias, ACT_RELU, source=c3[0].weight)
-        h = self._lin(h, c3[1].weight.view(c3[1].out_channels, -1), c3[1].bias, ACT_RELU)
-        # last layer + max over each environment's 128 points in one kernel (nothing [B*128,1024] is stored)
-        w3 = c3[2].weight.view(c3[2].out_channels, -1)
-        pooled = torch.empty((B, w3.size(0)), dtype=torch.float32, device=dev)
-        # (a handful of problems leave the fused kernel 8 workgroups per problem: there the split-K layer followed
-        # by the row-max kernel is quicker -- 45 -> 22 us for one problem)
-        if sa2.npoint == 128 and (B > 8 or self.dense_precision == "bf16x3"):
-            for b0 in range(0, B, 65535):
-                nb = min(65535, B - b0)
-                if self.dense_precision == "bf16x3":
-                    lib.call("mpx_linear_rowmax_bf16x3", lib.ptr(h[b0 * 128:]), h.stride(0), lib.ptr(self._split.get(w3)),
-                             lib.ptr(c3[2].bias), nb * 128, w3.size(0), w3.size(1), 128, lib.ptr(pooled[b0:]),
-                             pooled.stride(0))
-                else:
-                    lib.call("mpx_linear_rowmax", lib.ptr(h[b0 * 128:]), h.stride(0), lib.ptr(w3), lib.ptr(c3[2].bias),
-                             nb * 128, w3.size(0), w3.size(1), 128, lib.ptr(pooled[b0:]), pooled.stride(0))
+        return dict(fps_idx1=idx1, xyz1=xyz1, ball_idx1=nbr1, ball_cnt1=cnt1, f1=f1, fps_idx2=idx2, ball_idx2=nbr2,
+                    ball_cnt2=cnt2, sa3_in=sa3_in)
+
+    def _group_all(self, h: torch.Tensor, B: int, want_pairs: bool) -> torch.Tensor:
+        """The group-all module on its input rows ``h`` [B*128, K3]: three GEMMs and the max over each environment's rows
+        -> the pooled rows, fp32 [B, C3], or in the pairs form [B, 2 * C3] where ``want_pairs`` and the bf16x3 chain
+        through pairs runs."""
+        lib = _lib
+        _, sa2, sa3 = self.SA_modules
+        c3, P = sa3.convs(), sa2.npoint  # (P: rows per environment)
+        x3 = self.dense_precision == "bf16x3"
+        if x3 and P == 128 and self.dense_through_pairs and all(c.out_channels % 16 == 0 for c in c3):
+            return self._sa3_through_pairs(h, c3, B, pooled_pairs=want_pairs)
+        pooled = torch.empty((B, c3[2].out_channels), dtype=torch.float32, device=h.device)
+        if not x3 and P == 128 and B >= SA3_CHAIN_MIN_BATCH and (pack := self._sa3_pack(h.size(1))) is not None:
+            # the whole module as one kernel: nothing between the rows and the pooled row in HBM
+            lib.call("mpx_sa3_chain", lib.ptr(h), h.size(1), B, 128, lib.ptr(pack), h.size(1), c3[0].out_channels,
+                     c3[1].out_channels, c3[2].out_channels, lib.ptr(pooled), pooled.stride(0))
+            return pooled
+        h = self._lin(h, c3[0], ACT_RELU, weight=self._sa3_first_weight())
+        h = self._lin(h, c3[1], ACT_RELU, weight=c3[1].weight.flatten(1))
+        if P == 128 and (B > 8 or x3):
+            # last layer + max over each environment's 128 points in one kernel (nothing [B*128,1024] is stored).  (A
+            # handful of problems leave the fused kernel 8 workgroups per problem: there the split-K layer followed by
+            # the row-max kernel is quicker -- 45 -> 22 us for one problem.)
+            w3 = c3[2].weight.flatten(1)
+            fn, w3 = ("mpx_linear_rowmax_bf16x3", self._pairs(c3[2], w3)) if x3 else ("mpx_linear_rowmax", w3)
+            for b0, nb in _chunks(B, 65535):
+                lib.call(fn, lib.ptr(h[b0 * 128:]), h.stride(0), lib.ptr(w3), lib.ptr(c3[2].bias), nb * 128,
+                         c3[2].out_channels, c3[2].in_channels, 128, lib.ptr(pooled[b0:]), pooled.stride(0))
         else:
-            h = self._lin(h, w3, c3[2].bias, ACT_RELU)
-            for b0 in range(0, B, 65535):
-                nb = min(65535, B - b0)
-                lib.call("mpx_rowmax", lib.ptr(h[b0 * sa2.npoint:]), h.stride(0), nb, sa2.npoint, h.size(1),
-                         lib.ptr(pooled[b0:]), pooled.stride(0))
-        self.last_counts = (cnt1, cnt2)  # distinct-neighbour counts of the latest forward (bench accounting)
-        if aux is not None:
-            aux.update(fps_idx1=idx1, xyz1=xyz1, ball_idx1=nbr1, ball_cnt1=cnt1, f1=f1, fps_idx2=idx2, ball_idx2=nbr2,
-                       ball_cnt2=cnt2, sa3_in=sa3_in, f3=pooled)
-        return self._fc(pooled, out=out)
+            h = self._lin(h, c3[2], ACT_RELU, weight=c3[2].weight.flatten(1))
+            for b0, nb in _chunks(B, 65535):
+                lib.call("mpx_rowmax", lib.ptr(h[b0 * P:]), h.stride(0), nb, P, h.size(1), lib.ptr(pooled[b0:]),
+                         pooled.stride(0))
+        return pooled
 
 
 class MotionPolicyNetwork(nn.Module):
@@ -467,7 +452,7 @@ class MotionPolicyNetwork(nn.Module):
             nn.Linear(2048 + 64, 512), nn.LeakyReLU(), nn.Linear(512, 256), nn.LeakyReLU(), nn.Linear(256, 128),
             nn.LeakyReLU(), nn.Linear(128, 7),
         )
-        self._q_w0 = None
+        self._derived = DerivedWeights()
 
     @property
     def device(self):
@@ -509,20 +494,13 @@ class MotionPolicyNetwork(nn.Module):
 
     def invalidate_caches(self) -> "MotionPolicyNetwork":
         """Drop every derived weight buffer (MFMA-stream packs, bf16 hi/lo planes, padded first layers).  They refresh
-        by themselves when a parameter is modified through torch (``_version`` changes: optimizer steps,
+        by themselves when a parameter is replaced or modified through torch (``_version`` changes: optimizer steps,
         ``load_state_dict``, ``copy_``); writes through ``param.data`` (EMA swaps, manual init) do not bump the
         version -- call this after them."""
-        enc = self.point_cloud_encoder
-        for sa in enc.SA_modules:
-            sa._packed.packs.clear()
-            sa._packed._fact = None
-            if hasattr(sa, "_split"):
-                sa._split.cache.clear()
-        enc._split.cache.clear()
-        enc._sa3_w0 = None
-        enc._sa3_pk = None
-        enc._sa3_fp = None
-        self._q_w0 = None
+        for m in self.modules():
+            for v in vars(m).values():
+                if isinstance(v, DerivedWeights):
+                    v.clear()
         return self
 
     def configure_optimizers(self):
@@ -558,10 +536,7 @@ class MotionPolicyNetwork(nn.Module):
 
     def _q_first_weight(self) -> torch.Tensor:
         lin = self.feature_encoder[0]
-        key = (lin.weight._version, lin.weight.data_ptr())
-        if self._q_w0 is None or self._q_w0[0] != key:
-            self._q_w0 = (key, torch.nn.functional.pad(lin.weight.detach(), (0, 1)).contiguous())
-        return self._q_w0[1]
+        return self._derived.entry("q_w0", (lin.weight,), lambda: torch.nn.functional.pad(lin.weight.detach(), (0, 1)).contiguous())
 
     # ---- the single-call C entry point (mpx_policy_forward): what a caller without Python would use ----------
     class _NativeWeights(ctypes.Structure):  # field order = struct mpx_policy_weights (include/mpinets_hip.h)
@@ -650,7 +625,7 @@ class MotionPolicyNetwork(nn.Module):
     def decode(self, cat: torch.Tensor) -> torch.Tensor:
         """``decoder`` (model.py:56-64) on ``[pc_encoding (2048) | feature_encoding (64)]`` rows -> [B,7]."""
         de = self.decoder
-        h = self.point_cloud_encoder._lin(cat, de[0].weight, de[0].bias, ACT_LEAKY)
+        h = self.point_cloud_encoder._lin(cat, de[0], ACT_LEAKY)
         h = linear(h, de[2].weight, de[2].bias, ACT_LEAKY)
         h = linear(h, de[4].weight, de[4].bias, ACT_LEAKY)
         return linear(h, de[6].weight, de[6].bias, ACT_NONE)

@@ -12,7 +12,7 @@ All compute runs in ``libmpinets_hip.so``; CPU tensors are rejected like in the 
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Any, Callable, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -107,33 +107,48 @@ def split_pairs(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     return out
 
 
-class SplitWeights:
-    """Dense weight matrices in the pairs form for the ``bf16x3`` mode, refreshed when a parameter changes."""
+class DerivedWeights:
+    """Tensors derived from parameters (kernel weight packs, ``bf16x3`` pairs, padded copies), one entry per derived
+    tensor under a name saying what it is.  An entry is rebuilt when the (data_ptr, _version, shape) of any tensor it
+    was made from has changed.  It keeps those tensors referenced, so their memory cannot pass to another tensor that
+    would match the key.  Writes through ``param.data`` do not bump the version: ``clear()`` after them."""
 
     def __init__(self):
-        self.cache = {}
+        self._entries = {}
 
-    def get(self, weight: torch.Tensor, source: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``source``: the parameter a derived matrix (padded / transposed copy) was made from -- its version
-        decides when the pairs are stale."""
+    def entry(self, name, sources, make: Callable[[], Any]):
+        """The entry ``name``, made by ``make()`` from ``sources`` unless it was made from them as they are now."""
+        key = [(t.data_ptr(), t._version, t.shape) for t in sources]
+        hit = self._entries.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._entries[name] = (key, sources, make())
+        return hit[2]
+
+    def __contains__(self, name) -> bool:
+        return name in self._entries
+
+    def clear(self) -> None:
+        self._entries.clear()
+
+
+class SplitWeights(DerivedWeights):
+    """Dense weight matrices in the pairs form for the ``bf16x3`` mode."""
+
+    def get(self, weight: torch.Tensor, source: Optional[torch.Tensor] = None, name=None) -> torch.Tensor:
+        """``weight`` [N, K] in the pairs form.  ``source``: the parameter a derived matrix (padded / reshaped copy) was
+        made from (default: ``weight``); ``name``: what the matrix is, e.g. its layer (default: ``source``)."""
         src = weight if source is None else source
-        key = (src.data_ptr(), tuple(weight.shape))
-        ver = (src._version, tuple(weight.shape))
-        hit = self.cache.get(key)
-        if hit is None or hit[0] != ver:
-            w = _lib.f32c(weight.detach())
-            hit = (ver, split_pairs(w), w)  # w kept alive: its data_ptr is the key
-            self.cache[key] = hit
-        return hit[1]
+        return self.entry(src if name is None else name, (src,), lambda: split_pairs(_lib.f32c(weight.detach())))
 
 
 def linear_x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: int, split: SplitWeights,
-              out: Optional[torch.Tensor] = None, source: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``linear`` on the bf16 matrix cores (three split products per fp32 product, fp32 accumulate)."""
+              out: Optional[torch.Tensor] = None, source: Optional[torch.Tensor] = None, name=None) -> torch.Tensor:
+    """``linear`` on the bf16 matrix cores (three split products per fp32 product, fp32 accumulate); ``source``,
+    ``name``: see ``SplitWeights.get``."""
     assert x.ndim == 2 and weight.ndim == 2 and x.size(1) == weight.size(1) and x.stride(1) == 1
     M, K = x.shape
     N = weight.size(0)
-    wp = split.get(weight, source)
+    wp = split.get(weight, source, name)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     assert out.shape == (M, N) and out.stride(1) == 1
@@ -162,34 +177,30 @@ SPARSE_POOL_BACKWARD = True
 FUSED_POOL_FORWARD = True
 
 
-class SAWeights:
-    """Packed (MFMA-stream order) weights of one shared MLP, refreshed when parameters change.
-    One pack per precision mode: ``fp32`` (exact fp32 MFMA, the parity default) or ``bf16x3``
-    (split-bf16: hi/lo bf16 operand blocks for the bf16 matrix cores)."""
-
-    def __init__(self):
-        self.packs = {}
-        self._fact = None
+class SAWeights(DerivedWeights):
+    """Packed (MFMA-stream order) weights of one shared MLP: one pack per precision mode, ``fp32`` (exact fp32 MFMA,
+    the parity default) or ``bf16x3`` (split-bf16: hi/lo bf16 operand blocks for the bf16 matrix cores), and the first
+    layer split for the factored kernels."""
 
     def factored(self, convs: List[nn.Conv2d], C: int):
         """First layer split for ``mpx_sa_mlp_factored``: (w_point [c1, Kp] over rows [feat | xyz | 0],
         w_centre [c1, 4] over rows [xyz | 0], -b1)."""
         c0 = convs[0]
-        ver = (c0.weight._version, c0.bias._version, c0.weight.data_ptr())
-        if self._fact is None or self._fact[0] != ver:
+
+        def make():
             w = c0.weight.detach().reshape(c0.out_channels, -1).float()
             assert w.size(1) == 3 + C
             z = lambda n: torch.zeros((w.size(0), n), dtype=torch.float32, device=w.device)
             wp = torch.cat((w[:, 3:], w[:, :3], z((-(3 + C)) % 4)), dim=1).contiguous()
             wc = torch.cat((w[:, :3], z(1)), dim=1).contiguous()
-            self._fact = (ver, (wp, wc, (-c0.bias.detach().float()).contiguous()))
-        return self._fact[1]
+            return wp, wc, (-c0.bias.detach().float()).contiguous()
+
+        return self.entry("factored", (c0.weight, c0.bias), make)
 
     def get(self, convs: List[nn.Conv2d], C: int, precision: str = "fp32") -> torch.Tensor:
         assert precision in PRECISIONS, precision
-        ver = tuple((c.weight._version, c.bias._version, c.weight.data_ptr()) for c in convs)
-        hit = self.packs.get(precision)
-        if hit is None or hit[0] != ver:
+
+        def make():
             c1, c2, c3 = (c.out_channels for c in convs)
             lib = _lib.load()
             dev = convs[0].weight.device
@@ -207,9 +218,9 @@ class SAWeights:
                 raise _lib.MpxError(f"unsupported shared-MLP shape C={C} mlp=({c1},{c2},{c3})")
             _lib.call(fn, _lib.ptr(w[0]), _lib.ptr(b[0]), _lib.ptr(w[1]), _lib.ptr(b[1]), _lib.ptr(w[2]),
                       _lib.ptr(b[2]), C, c1, c2, c3, _lib.ptr(pack))
-            self.packs[precision] = (ver, pack)
-            hit = self.packs[precision]
-        return hit[1]
+            return pack
+
+        return self.entry(("pack", precision), [p for c in convs for p in (c.weight, c.bias)], make)
 
 
 def launch_sa(precision: str, xyz_ptr: int, stride: int, new_xyz_ptr: int, new_stride: int, feat_ptr: int,
@@ -259,26 +270,23 @@ def sa_mlp_fused(xyz: torch.Tensor, new_xyz: torch.Tensor, feat: torch.Tensor, f
 
 
 def sa_mlp_factored(point_rows: torch.Tensor, centre_rows: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor,
-                    packed: "SAWeights", convs: List[nn.Conv2d], C: int, N: int, out_ptr: int, out_stride: int,
-                    precision: str = "fp32", split: Optional["SplitWeights"] = None) -> None:
+                    packed: SAWeights, convs: List[nn.Conv2d], C: int, N: int, out_ptr: int, out_stride: int,
+                    precision: str = "fp32") -> None:
     """The (64+3,128,128,256) module with its first layer evaluated per point / per query instead of per
     (query, neighbour) row (``mpx_sa_mlp_factored`` / ``mpx_sa_mlp_bf16x3_factored``).  ``point_rows`` [B*N, Kp] =
     [feat | xyz | 0] rows, ``centre_rows`` [B*npoint, 4] = [xyz | anything finite] rows (row strides free)."""
     B, npoint, nsample = idx.shape
     wp, wc, nb1 = packed.factored(convs, C)
     c1, c2, c3 = (c.out_channels for c in convs)
-    if precision == "bf16x3":
-        # (K = 68: HBM-bound either way -- the fp32 row-per-lane kernel is the faster one, 0.71 vs 0.79 ms, and exact)
-        pre = linear(point_rows, wp, None)
-        ctr = linear(centre_rows, wc, nb1)  # K = 4: not worth the matrix cores
-        # (the factored kernel is persistent and takes its units from a device-side queue: no sorting pass, order = NULL)
-        _lib.call("mpx_sa_mlp_bf16x3_factored", _lib.ptr(pre), _lib.ptr(ctr), _lib.ptr(idx), _lib.ptr(cnt), None,
-                  B, N, npoint, nsample, _lib.ptr(packed.get(convs, C, "bf16x3")), C, c1, c2, c3, out_ptr, out_stride)
-        return
+    # (bf16x3 too: K = 68 is HBM-bound either way -- the fp32 row-per-lane kernel is the faster one, 0.71 vs 0.79 ms, and exact)
     pre = linear(point_rows, wp, None)
-    ctr = linear(centre_rows, wc, nb1)
-    _lib.call("mpx_sa_mlp_factored", _lib.ptr(pre), _lib.ptr(ctr), _lib.ptr(idx), _lib.ptr(cnt), B, N, npoint, nsample,
-              _lib.ptr(packed.get(convs, C, "fp32")), C, c1, c2, c3, out_ptr, out_stride)
+    ctr = linear(centre_rows, wc, nb1)  # K = 4: not worth the matrix cores
+    x3 = precision == "bf16x3"
+    # (the bf16x3 kernel is persistent and takes its units from a device-side queue: no sorting pass, order = NULL)
+    order = (None,) if x3 else ()
+    _lib.call("mpx_sa_mlp_bf16x3_factored" if x3 else "mpx_sa_mlp_factored", _lib.ptr(pre), _lib.ptr(ctr), _lib.ptr(idx),
+              _lib.ptr(cnt), *order, B, N, npoint, nsample, _lib.ptr(packed.get(convs, C, precision)), C, c1, c2, c3, out_ptr,
+              out_stride)
 
 
 FACTORED_SHAPE = (64, 128, 128, 256)
@@ -711,10 +719,8 @@ class PointnetSAModule(nn.Module):
                 rows = torch.cat((feat_pm, xyz, torch.zeros_like(xyz[:, :, :1])), dim=2).view(B * N, C + 4)
                 ctr_rows = torch.nn.functional.pad(new_xyz, (0, 1)).view(B * self.npoint, 4)
                 out = torch.empty((B, self.npoint, convs[-1].out_channels), dtype=torch.float32, device=xyz.device)
-                if not hasattr(self, "_split"):
-                    self._split = SplitWeights()
                 sa_mlp_factored(rows, ctr_rows, nbr, full, self._packed, convs, C, N, _lib.ptr(out), out.stride(1),
-                                precision=self.precision, split=self._split)
+                                precision=self.precision)
                 return new_xyz, out.transpose(1, 2).contiguous()
             wpack = self._packed.get(convs, C, self.precision)
             out = sa_mlp_fused(xyz, new_xyz, feat_pm, C, C, nbr, wpack, tuple(c.out_channels for c in convs),

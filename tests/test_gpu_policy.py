@@ -542,7 +542,7 @@ def test_linear_bf16x3_pairs_chain_is_bit_identical_to_the_row_chain():
                   _lib.ptr(out), 512, _lib.ptr(p2), 1024)
 
 
-def test_policy_forward_bf16x3_pairs_on_and_off_agree():
+def test_policy_forward_bf16x3_fused_front_and_pairs_on_and_off_agree():
     """The policy forward in bf16x3 with the group-all MLP layer by layer through pairs == with fp32 rows, bit for bit; the
     default -- its first two layers as ONE kernel (mpx_sa3_front_bf16x3: another order of the 16 products inside an MFMA
     step, the bias added last instead of in the epilogue's place) -- equals both to rounding."""
@@ -555,7 +555,7 @@ def test_policy_forward_bf16x3_pairs_on_and_off_agree():
     prob = make_problem_batch(6, seed=31, device=dev())
     with torch.no_grad():
         fused = mdl(prob["xyz"], prob["q_norm"]).clone()
-        assert enc._sa3_fp is not None  # (the fused kernel served the default call)
+        assert ("sa3_front", 272) in enc._derived  # (the fused kernel's weight pack served the default call)
         enc.sa3_front_fused = False
         a = mdl(prob["xyz"], prob["q_norm"]).clone()
         enc.dense_through_pairs = False
@@ -746,6 +746,21 @@ def test_lightning_style_checkpoint_and_cache_invalidation(tmp_path):
         stale = m2(prob["xyz"], prob["q_norm"]).clone()
         fresh = m2.invalidate_caches()(prob["xyz"], prob["q_norm"]).clone()  # ... until the caches are dropped
     assert torch.equal(stale, a) and not torch.equal(fresh, a)
+    # a parameter replaced by a new one is noticed without invalidate_caches(), even at the old one's version number
+    conv = m2.point_cloud_encoder.SA_modules[0].convs()[0]
+    old = conv.bias
+    new = torch.nn.Parameter(old.detach() + 0.25)
+    with torch.no_grad():
+        while new._version < old._version:
+            new.add_(0)
+    assert new._version == old._version
+    conv.bias = new
+    m3 = MotionPolicyNetwork().to(dev()).eval()
+    m3.load_state_dict(m2.state_dict())
+    with torch.no_grad():
+        replaced = m2(prob["xyz"], prob["q_norm"]).clone()
+        rebuilt = m3(prob["xyz"], prob["q_norm"]).clone()
+    assert not torch.equal(replaced, fresh) and torch.equal(replaced, rebuilt)
 
 
 def test_operands_on_another_device_are_rejected():
