@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/s of the closed-loop policy step (FK + SDF collision + PointNet++).
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: starts its own N ranks, one per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -23,8 +23,13 @@ fp32 end to end (fp32 MFMA for every contraction).
 refreshed point clouds) to DIR/<name>.npy: same arguments, same inputs, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the SA2 fused grouped MLP),
-timed live with HIP events on the launch stream inside the timed region; `cpu_baseline` is the
-oracle (a port, not the product) timed on this host's cores on a bounded sample.
+timed live with HIP events on the launch stream inside the timed region.
+
+A plain run sets up, warms up, times the steps, dumps (if asked) and prints the line.  `--full` adds every secondary
+measurement after the timed region: the split-bf16 mode (`fast_mode`), the extra configurations (`extra_configs`,
+`all_slots`) and `cpu_baseline`, the oracle (a port, not the product) timed on this host's cores on a bounded sample.
+Their own options (--fast-steps, --extra, --cpu-envs) take the defaults below under --full and 0 without it; an option
+given explicitly holds either way.
 """
 from __future__ import annotations
 
@@ -319,18 +324,23 @@ def spawn_ranks_if_needed(args) -> bool:
     sys.exit(subprocess.call(cmd, env=env))
 
 
-def main():
+def parse_args(argv=None):
+    """The command line -> args, with the secondary measurements' options resolved against --full."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--envs", type=int, default=8192, help="environments per GPU")
-    ap.add_argument("--fast-steps", type=int, default=3, help="steps of the secondary bf16x3 measurement (0 = skip)")
-    ap.add_argument("--extra", type=int, default=1, help="also time BASELINE configs 2 and 4 (collision validation only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (bf16x3 mode, extra configurations, CPU baseline) after "
+                         "the timed steps; without it --fast-steps, --extra and --cpu-envs default to 0")
+    ap.add_argument("--fast-steps", type=int, default=None, help="steps of the secondary bf16x3 measurement (0 = skip; default 3 with --full)")
+    ap.add_argument("--extra", type=int, default=None, help="also time the collision-only configurations, the small batches and the extras below "
+                                                             "(static scenes, all slots, training step; default 1 with --full)")
     ap.add_argument("--static-steps", type=int, default=2, help="steps of the extra without scene re-render on tabletop-only scenes (BASELINE config 3 shape at this batch size); 0 = skip")
     ap.add_argument("--all-slots-steps", type=int, default=2, help="steps of the worst-case extra: padding elision off, all 128 slots per neighbourhood (0 = skip)")
     ap.add_argument("--whole-batch-steps", type=int, default=0, help="opt-in extra: steps of the whole 65 536-environment configs[4] batch on this one GPU (0 = skip; 17 GB: the encoder works in slabs of 8192 environments)")
-    ap.add_argument("--cpu-envs", type=int, default=512, help="env-steps in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-envs", type=int, default=None, help="env-steps in the CPU baseline sample (0 = skip; default 512 with --full)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default): --envs environments per GPU; strong: --global-envs environments split evenly over the GPUs")
     ap.add_argument("--global-envs", type=int, default=8192, help="total environments of a --scaling strong run")
@@ -338,9 +348,17 @@ def main():
     ap.add_argument("--scene-pool", type=int, default=1024, help="distinct host-generated primitive sets tiled over the batch (clouds are drawn per env on the device)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed to DIR/<name>.npy (see step_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for name, full_default in (("fast_steps", 3), ("extra", 1), ("cpu_envs", 512)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
+
+
+def main():
+    args = parse_args()
     shared_devices = spawn_ranks_if_needed(args)
 
     from mpinets_amd import _lib, shard

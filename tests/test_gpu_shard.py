@@ -93,7 +93,7 @@ def test_bench_distributed_path_on_a_real_rccl_communicator():
     env = dict(os.environ, MPX_DIST_FORCE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("MPX_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--envs", "1040", "--steps", "2",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--envs", "1040", "--steps", "2",
            "--warmup", "1", "--extra", "0", "--fast-steps", "1", "--cpu-envs", "0", "--scene-pool", "64"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -120,7 +120,7 @@ def test_bench_two_ranks_report_sharded_extras_and_both_scalings(scaling):
     env = dict(os.environ, MPX_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("MPX_DIST_BACKEND", "MPX_DIST_FORCE", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--scaling", scaling, "--envs", "520", "--global-envs",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--scaling", scaling, "--envs", "520", "--global-envs",
            "1041", "--steps", "1", "--warmup", "1", "--fast-steps", "0", "--static-steps", "0",
            "--all-slots-steps", "0", "--train-steps", "1", "--cpu-envs", "0", "--scene-pool", "32"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
@@ -152,7 +152,7 @@ def test_bench_two_ranks_report_sharded_extras_and_both_scalings(scaling):
 def test_bench_eight_ranks_dress_rehearsal(launcher, scaling):
     """The 1 -> 8 GPU curve is taken by the driver in ONE run on a node no round has touched, so the 8-rank command is
     rehearsed here in full: eight processes (sharing this box's GPU over gloo: MPX_SHARE_GPU / MPX_SHARED_DEVICES, flagged
-    in the JSON), every default-on extra, small shares.  `driver` is the driver's own command line
+    in the JSON), every --full extra, small shares.  `driver` is the driver's own command line
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8
     --steps K --warmup W`), `self` lets bench.py start its ranks.  Checks: 8 rank records with contiguous environment
     ranges, the gathered result's shape, config 3 split 8 ways, the data-parallel training step over 8 ranks, rank 0's
@@ -173,7 +173,7 @@ def test_bench_eight_ranks_dress_rehearsal(launcher, scaling):
     for k in ("MPX_DIST_BACKEND", "MPX_DIST_FORCE", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MPX_SHARED_DEVICES"):
         env.pop(k, None)
     total = 515 if scaling == "strong" else world * per  # strong: 3 shares of 65 + 5 of 64 (padded gather)
-    small = ["--envs", str(per), "--global-envs", str(total), "--scaling", scaling, "--steps", "2", "--warmup", "1",
+    small = ["--full", "--envs", str(per), "--global-envs", str(total), "--scaling", scaling, "--steps", "2", "--warmup", "1",
              "--fast-steps", "1", "--static-steps", "1", "--all-slots-steps", "1", "--train-steps", "1",
              "--cpu-envs", "0", "--scene-pool", "16"]
     if launcher == "driver":

@@ -12,7 +12,7 @@ timeout 1800 python -m pytest tests -m gpu -q -rA --tb=short -p no:cacheprovider
 echo "pytest exit: $?" >> $O/pytest_gpu.log; tail -3 $O/pytest_gpu.log | cut -c1-200
 fi
 cp gpurun_out/soak_hashes.json gpurun_out/horizon_report.json $O/ 2>/dev/null
-timeout 1200 python bench.py --whole-batch-steps 1 > $O/bench.log 2> $O/bench.err; echo "bench exit: $?" >> $O/bench.err; tail -1 $O/bench.err; cut -c1-200 $O/bench.log
+timeout 1200 python bench.py --full --whole-batch-steps 1 > $O/bench.log 2> $O/bench.err; echo "bench exit: $?" >> $O/bench.err; tail -1 $O/bench.err; cut -c1-200 $O/bench.log
 HEAD_ARGS="--steps 3 --warmup 1 --cpu-envs 0 --extra 0 --fast-steps 0 --all-slots-steps 0 --train-steps 0"
 pmc() {  # tag, counters, command...
   tag=$1; ctr=$2; shift 2
