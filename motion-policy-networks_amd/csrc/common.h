@@ -57,6 +57,18 @@ int mpx_unit_queue_slots();
 void mpx_unit_queue_set_slots(int n);
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// ---- host helpers shared across files ----------------------------------------------------------------------------------
+// dense.hip: the segment max-pool's checks and key unpacking (mpx_linear_segmax, dense_bf16.hip's mpx_linear_segmax_bf16x3)
+int mpx_segmax_check(const char *name, int M, const int32_t *seg, int64_t Q, int N, const void *keys, const float *pooled,
+                     int ldp, const int64_t *arg);
+int mpx_segmax_unpack_launch(const unsigned long long *keys, int64_t Q, int N, float *pooled, int ldp, int64_t *arg,
+                             hipStream_t stream);
+// dense_bf16.hip: the split-bf16 weight-gradient kernel (dense_grad.hip's mpx_linear_wgrad_bf16x3)
+void mpx_wgrad_bf16x3_launch(const float *dy, int lddy, const float *x, int ldx, int M, int N, int K, int rows_per_split,
+                             int S, float *partial, int with_bias, hipStream_t stream);
+// dense_grad.hip: the in-order sum of split partials (train_ops.hip: the sparse pool backward)
+void mpx_reduce_partials_launch(const float *partial, int S, int64_t stride, int64_t n, float *out, hipStream_t stream);
+
 // ---- launch slabs ----------------------------------------------------------------------------------------------------
 // gridDim.y is limited to 65535, and kernels that reach an operand through a 32-bit buffer offset need it under 4 GB.
 // A batched entry point whose batch exceeds one launch walks it in slabs (same kernels, same per-row arithmetic: results

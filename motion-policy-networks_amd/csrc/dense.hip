@@ -431,19 +431,66 @@ static bool rowlane_ok(const float *x, int ldx, const float *w, const float *bia
          (((uintptr_t)x | (uintptr_t)w) & 7) == 0 && ((uintptr_t)y & 15) == 0;
 }
 
+// What a linear_kernel launch adds to x . w^T (linear_launch; the defaults: nothing).
+struct LinearEpi {
+  const float *bias = nullptr;
+  int act = MPX_ACT_NONE;
+  int S = 1, kslice = 0;           // split-K (mpx_linear_ws): S slices of kslice k (0: all of K), partials at y + z * zstride
+  size_t zstride = 0;
+  const float *dact_of = nullptr;  // times act'(dact_of) (mpx_linear_dact)
+  int lddact = 0, dact = MPX_ACT_NONE;
+  const int32_t *seg = nullptr;    // POOL: max over each segment into the keys y, else over each BM-row group into y[M / BM]
+  bool gemv = false;               // a slab of <= 8 rows takes the gemv kernel (mpx_linear)
+};
+
+// The one launch site of linear_kernel.  Rows past one launch are walked in slabs (common.h); per slab: the route, the row
+// operands' offsets, and the zeroing of the row-max output in front of its kernel.  Launch errors: the caller's check.
+template <bool POOL>
+static int linear_launch(const char *name, const float *x, int ldx, const float *w, int M, int N, int K, float *y, int ldy,
+                         const LinearEpi &e, mpx_stream_t stream) {
+  const int64_t slab = mpx_row_slab(BM, (int64_t)ldx * 4);  // (split-K: M <= 1024, one slab)
+  for (int64_t m0 = 0; m0 < M; m0 += slab) {
+    const int m = (int)(M - m0 < slab ? M - m0 : slab);
+    const float *xs = x + m0 * ldx;
+    float *ys = e.seg ? y : y + (POOL ? m0 / BM : m0) * ldy;  // (the keys are per segment, not per row)
+    if (e.gemv && gemv_fits(m, K)) {
+      gemv_launch(xs, ldx, w, e.bias, m, N, K, e.act, ys, ldy, stream);
+      continue;
+    }
+    if (POOL && !e.seg) {
+      const hipError_t err = hipMemset2DAsync(ys, (size_t)ldy * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)(m / BM),
+                                              mpx_s(stream));
+      MPX_REQUIRE(err == hipSuccess, "%s: memset failed: %s", name, hipGetErrorString(err));
+    }
+    // (BK = 32 slabs were measured: no gain, twice the LDS)
+    // (A 256 x 128-tile form with a three-stage counted-vmcnt ring at two waves per SIMD -- the structure of
+    // dense_bf16.hip's pairs kernel -- was measured on the 1 M-row layers: 8.98 vs 8.32 ms and 4.56 vs 4.21 ms: with
+    // 64-cycle fp32 MFMAs four waves per SIMD cover more than the leaner slab does.)
+    // (split-K slices are whole 16-k steps, so every slice suits the DMA form too)
+    const auto kernel = dma_ok(m, N, K, ldx, K) ? linear_kernel<16, POOL, true> : linear_kernel<16, POOL, false>;
+    hipLaunchKernelGGL(kernel, dim3(cdiv(N, BN), cdiv(m, BM), e.S), dim3(256), 0, mpx_s(stream), xs, ldx, w, K, e.bias, m, N, K,
+                       e.act, ys, ldy, e.kslice ? e.kslice : K, e.zstride, e.dact_of ? e.dact_of + m0 * e.lddact : nullptr,
+                       e.lddact, e.dact, e.seg ? e.seg + m0 : nullptr, e.seg ? (int)m0 : 0);
+  }
+  return 0;
+}
+
+// the operand checks of the fp32 entries (ldy = N where the output is not rows)
+static int linear_check(const char *name, const float *x, int ldx, const float *w, int M, int N, int K, int ldy) {
+  MPX_REQUIRE(M >= 0 && N >= 1 && K >= 1, "%s: bad size", name);
+  MPX_REQUIRE(K % 4 == 0 && ldx % 4 == 0, "%s: K and ldx must be multiples of 4 (got %d, %d)", name, K, ldx);
+  MPX_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "%s: x and w must be 16-byte aligned", name);
+  MPX_REQUIRE(ldx >= K && ldy >= N, "%s: leading dimension too small", name);
+  return 0;
+}
+
 MPX_EXPORT int mpx_linear(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K,
                           int act, float *y, int ldy, mpx_stream_t stream) {
-  MPX_REQUIRE(M >= 0 && N >= 1 && K >= 1, "mpx_linear: bad size");
-  MPX_REQUIRE(K % 4 == 0 && ldx % 4 == 0, "mpx_linear: K and ldx must be multiples of 4 (got %d, %d)", K, ldx);
-  MPX_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "mpx_linear: x and w must be 16-byte aligned");
-  MPX_REQUIRE(ldx >= K && ldy >= N, "mpx_linear: leading dimension too small");
+  if (linear_check("mpx_linear", x, ldx, w, M, N, K, ldy)) return 1;
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear: unknown activation %d", act);
   if (M == 0) return 0;
-  if (gemv_fits(M, K)) {
-    gemv_launch(x, ldx, w, bias, M, N, K, act, y, ldy, stream);
-    MPX_LAUNCH_CHECK("mpx_linear");
-  }
-  if (rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy)) {  // short K, 128 outputs: a row per lane, W in registers (every M: one rounding order)
+  // short K, 128 outputs: a row per lane, W in registers (every M: one rounding order; a few rows take the gemv kernel)
+  if (!gemv_fits(M, K) && rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy)) {
     int cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
@@ -452,22 +499,9 @@ MPX_EXPORT int mpx_linear(const float *x, int ldx, const float *w, const float *
                        ldx, w, (int64_t)M, y, ldy);
     MPX_LAUNCH_CHECK("mpx_linear");
   }
-  if (const int64_t slab = mpx_row_slab(BM, (int64_t)ldx * 4); M > slab) {  // more rows than one launch covers
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear(x + m0 * ldx, ldx, w, bias, (int)(M - m0 < slab ? M - m0 : slab), N, K, act, y + m0 * ldy, ldy, stream))
-        return rc;
-    return 0;
-  }
-  // (BK = 32 slabs were measured: no gain, twice the LDS)
-  // (A 256 x 128-tile form with a three-stage counted-vmcnt ring at two waves per SIMD -- the structure of
-  // dense_bf16.hip's pairs kernel -- was measured on the 1 M-row layers: 8.98 vs 8.32 ms and 4.56 vs 4.21 ms: with
-  // 64-cycle fp32 MFMAs four waves per SIMD cover more than the leaner slab does.)
-  if (dma_ok(M, N, K, ldx, K))
-    hipLaunchKernelGGL((linear_kernel<16, false, true>), dim3(cdiv(N, BN), cdiv(M, BM)), dim3(256), 0, mpx_s(stream), x,
-                       ldx, w, K, bias, M, N, K, act, y, ldy, K, (size_t)0, static_cast<const float *>(nullptr), 0, 0, static_cast<const int32_t *>(nullptr), 0);
-  else
-    hipLaunchKernelGGL((linear_kernel<16, false, false>), dim3(cdiv(N, BN), cdiv(M, BM)), dim3(256), 0, mpx_s(stream), x,
-                       ldx, w, K, bias, M, N, K, act, y, ldy, K, (size_t)0, static_cast<const float *>(nullptr), 0, 0, static_cast<const int32_t *>(nullptr), 0);
+  LinearEpi e;  // (the route is chosen per slab: a remainder slab of <= 8 rows streams the weights too)
+  e.bias = bias, e.act = act, e.gemv = true;
+  if (int rc = linear_launch<false>("mpx_linear", x, ldx, w, M, N, K, y, ldy, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear");
 }
 
@@ -477,29 +511,13 @@ MPX_EXPORT int mpx_linear(const float *x, int ldx, const float *w, const float *
 // instead of a GEMM store + a read-modify-write).  Every M takes the 128 x 128 tile kernel.
 MPX_EXPORT int mpx_linear_dact(const float *x, int ldx, const float *w, int M, int N, int K, const float *dact_of,
                                int lddact, int dact, float *y, int ldy, mpx_stream_t stream) {
-  MPX_REQUIRE(M >= 0 && N >= 1 && K >= 1, "mpx_linear_dact: bad size");
-  MPX_REQUIRE(K % 4 == 0 && ldx % 4 == 0, "mpx_linear_dact: K and ldx must be multiples of 4 (got %d, %d)", K, ldx);
-  MPX_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "mpx_linear_dact: x and w must be 16-byte aligned");
-  MPX_REQUIRE(ldx >= K && ldy >= N, "mpx_linear_dact: leading dimension too small");
+  if (linear_check("mpx_linear_dact", x, ldx, w, M, N, K, ldy)) return 1;
   MPX_REQUIRE(dact == MPX_ACT_NONE || (dact_of != nullptr && lddact >= N && (dact == MPX_ACT_RELU || dact == MPX_ACT_LEAKY)),
               "mpx_linear_dact: the activation's output rows are missing or too short, or the activation is unknown");
   if (M == 0) return 0;
-  if (dact == MPX_ACT_NONE) dact_of = nullptr;
-  if (const int64_t slab = mpx_row_slab(BM, (int64_t)ldx * 4); M > slab) {  // more rows than one launch covers
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_dact(x + m0 * ldx, ldx, w, (int)(M - m0 < slab ? M - m0 : slab), N, K,
-                                   dact_of ? dact_of + m0 * lddact : nullptr, lddact, dact, y + m0 * ldy, ldy, stream))
-        return rc;
-    return 0;
-  }
-  if (dma_ok(M, N, K, ldx, K))
-    hipLaunchKernelGGL((linear_kernel<16, false, true>), dim3(cdiv(N, BN), cdiv(M, BM)), dim3(256), 0, mpx_s(stream), x,
-                       ldx, w, K, static_cast<const float *>(nullptr), M, N, K, MPX_ACT_NONE, y, ldy, K, (size_t)0, dact_of,
-                       lddact, dact, static_cast<const int32_t *>(nullptr), 0);
-  else
-    hipLaunchKernelGGL((linear_kernel<16, false, false>), dim3(cdiv(N, BN), cdiv(M, BM)), dim3(256), 0, mpx_s(stream), x,
-                       ldx, w, K, static_cast<const float *>(nullptr), M, N, K, MPX_ACT_NONE, y, ldy, K, (size_t)0, dact_of,
-                       lddact, dact, static_cast<const int32_t *>(nullptr), 0);
+  LinearEpi e;
+  e.dact_of = dact == MPX_ACT_NONE ? nullptr : dact_of, e.lddact = lddact, e.dact = dact;
+  if (int rc = linear_launch<false>("mpx_linear_dact", x, ldx, w, M, N, K, y, ldy, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear_dact");
 }
 
@@ -547,51 +565,29 @@ MPX_EXPORT int mpx_linear_ws(const float *x, int ldx, const float *w, const floa
   int kslice = K;
   const int S = (M > 0 && N > 0 && K > 0) ? splitk_plan(M, N, K, &kslice) : 1;
   if (S <= 1 || workspace == nullptr) return mpx_linear(x, ldx, w, bias, M, N, K, act, y, ldy, stream);
-  MPX_REQUIRE(K % 4 == 0 && ldx % 4 == 0, "mpx_linear_ws: K and ldx must be multiples of 4 (got %d, %d)", K, ldx);
-  MPX_REQUIRE((((uintptr_t)x | (uintptr_t)w | (uintptr_t)workspace) & 15) == 0,
-              "mpx_linear_ws: x, w and workspace must be 16-byte aligned");
-  MPX_REQUIRE(ldx >= K && ldy >= N, "mpx_linear_ws: leading dimension too small");
+  if (linear_check("mpx_linear_ws", x, ldx, w, M, N, K, ldy)) return 1;
+  MPX_REQUIRE(((uintptr_t)workspace & 15) == 0, "mpx_linear_ws: the workspace must be 16-byte aligned");
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_ws: unknown activation %d", act);
   MPX_REQUIRE(workspace_bytes >= mpx_linear_workspace(M, N, K),
               "mpx_linear_ws: workspace of %lld bytes, mpx_linear_workspace asks for %lld", (long long)workspace_bytes,
               (long long)mpx_linear_workspace(M, N, K));
   float *part = static_cast<float *>(workspace);
-  const size_t zstride = (size_t)M * N;
-  if (dma_ok(M, N, K, ldx, K))  // (slices are multiples of the slab, so every slice keeps whole slabs too)
-    hipLaunchKernelGGL((linear_kernel<16, false, true>), dim3(cdiv(N, BN), cdiv(M, BM), S), dim3(256), 0, mpx_s(stream), x,
-                       ldx, w, K, static_cast<const float *>(nullptr), M, N, K, MPX_ACT_NONE, part, N, kslice, zstride, static_cast<const float *>(nullptr), 0, 0, static_cast<const int32_t *>(nullptr), 0);
-  else
-    hipLaunchKernelGGL((linear_kernel<16, false, false>), dim3(cdiv(N, BN), cdiv(M, BM), S), dim3(256), 0, mpx_s(stream), x,
-                       ldx, w, K, static_cast<const float *>(nullptr), M, N, K, MPX_ACT_NONE, part, N, kslice, zstride, static_cast<const float *>(nullptr), 0, 0, static_cast<const int32_t *>(nullptr), 0);
+  LinearEpi e;
+  e.S = S, e.kslice = kslice, e.zstride = (size_t)M * N;
+  if (int rc = linear_launch<false>("mpx_linear_ws", x, ldx, w, M, N, K, part, N, e, stream)) return rc;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv((int64_t)M * N, 256)), dim3(256), 0, mpx_s(stream), part, S,
-                     zstride, bias, M, N, act, y, ldy);
+                     e.zstride, bias, M, N, act, y, ldy);
   MPX_LAUNCH_CHECK("mpx_linear_ws");
 }
 
 MPX_EXPORT int mpx_linear_rowmax(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K,
                                  int rows, float *y, int ldy, mpx_stream_t stream) {
-  MPX_REQUIRE(M >= 0 && N >= 1 && K >= 1, "mpx_linear_rowmax: bad size");
+  if (linear_check("mpx_linear_rowmax", x, ldx, w, M, N, K, ldy)) return 1;
   MPX_REQUIRE(rows == BM && M % BM == 0, "mpx_linear_rowmax: pooled groups must be exactly %d rows", BM);
-  MPX_REQUIRE(K % 4 == 0 && ldx % 4 == 0, "mpx_linear_rowmax: K and ldx must be multiples of 4");
-  MPX_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "mpx_linear_rowmax: x and w must be 16-byte aligned");
-  MPX_REQUIRE(ldx >= K && ldy >= N, "mpx_linear_rowmax: leading dimension too small");
   if (M == 0) return 0;
-  if (const int64_t slab = mpx_row_slab(BM, (int64_t)ldx * 4); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_rowmax(x + m0 * ldx, ldx, w, bias, (int)(M - m0 < slab ? M - m0 : slab), N, K, rows,
-                                     y + (m0 / BM) * ldy, ldy, stream))
-        return rc;
-    return 0;
-  }
-  hipError_t e = hipMemset2DAsync(y, (size_t)ldy * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)(M / BM),
-                                  mpx_s(stream));
-  MPX_REQUIRE(e == hipSuccess, "mpx_linear_rowmax: memset failed: %s", hipGetErrorString(e));
-  if (dma_ok(M, N, K, ldx, K))
-    hipLaunchKernelGGL((linear_kernel<16, true, true>), dim3(cdiv(N, BN), M / BM), dim3(256), 0, mpx_s(stream), x, ldx, w,
-                       K, bias, M, N, K, MPX_ACT_RELU, y, ldy, K, (size_t)0, static_cast<const float *>(nullptr), 0, 0, static_cast<const int32_t *>(nullptr), 0);
-  else
-    hipLaunchKernelGGL((linear_kernel<16, true, false>), dim3(cdiv(N, BN), M / BM), dim3(256), 0, mpx_s(stream), x, ldx, w,
-                       K, bias, M, N, K, MPX_ACT_RELU, y, ldy, K, (size_t)0, static_cast<const float *>(nullptr), 0, 0, static_cast<const int32_t *>(nullptr), 0);
+  LinearEpi e;
+  e.bias = bias, e.act = MPX_ACT_RELU;
+  if (int rc = linear_launch<true>("mpx_linear_rowmax", x, ldx, w, M, N, K, y, ldy, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear_rowmax");
 }
 
@@ -623,35 +619,17 @@ int mpx_segmax_check(const char *name, int M, const int32_t *seg, int64_t Q, int
   MPX_REQUIRE(M >= 1, "%s: every segment holds at least one row", name);
   return 0;
 }
-static int segmax_rows(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K, int act,
-                       const int32_t *seg, int row0, unsigned long long *keys, mpx_stream_t stream) {
-  if (const int64_t slab = mpx_row_slab(BM, (int64_t)ldx * 4); M > slab) {  // more rows than one launch covers
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = segmax_rows(x + m0 * ldx, ldx, w, bias, (int)(M - m0 < slab ? M - m0 : slab), N, K, act, seg + m0,
-                               row0 + (int)m0, keys, stream))
-        return rc;
-    return 0;
-  }
-  float *ky = reinterpret_cast<float *>(keys);
-  if (dma_ok(M, N, K, ldx, K))
-    hipLaunchKernelGGL((linear_kernel<16, true, true>), dim3(cdiv(N, BN), cdiv(M, BM)), dim3(256), 0, mpx_s(stream), x, ldx, w,
-                       K, bias, M, N, K, act, ky, N, K, (size_t)0, static_cast<const float *>(nullptr), 0, 0, seg, row0);
-  else
-    hipLaunchKernelGGL((linear_kernel<16, true, false>), dim3(cdiv(N, BN), cdiv(M, BM)), dim3(256), 0, mpx_s(stream), x, ldx, w,
-                       K, bias, M, N, K, act, ky, N, K, (size_t)0, static_cast<const float *>(nullptr), 0, 0, seg, row0);
-  return 0;
-}
 MPX_EXPORT int mpx_linear_segmax(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K, int act,
                                  const int32_t *seg, int64_t Q, void *keys, float *pooled, int ldp, int64_t *arg,
                                  mpx_stream_t stream) {
-  MPX_REQUIRE(M >= 0 && N >= 1 && K >= 1, "mpx_linear_segmax: bad size");
-  MPX_REQUIRE(K % 4 == 0 && ldx % 4 == 0, "mpx_linear_segmax: K and ldx must be multiples of 4 (got %d, %d)", K, ldx);
-  MPX_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0, "mpx_linear_segmax: x and w must be 16-byte aligned");
-  MPX_REQUIRE(ldx >= K && act >= 0 && act <= 2, "mpx_linear_segmax: leading dimension too small / unknown activation");
+  if (linear_check("mpx_linear_segmax", x, ldx, w, M, N, K, N)) return 1;
+  MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_segmax: unknown activation %d", act);
   if (mpx_segmax_check("mpx_linear_segmax", M, seg, Q, N, keys, pooled, ldp, arg)) return 1;
-  hipError_t e = hipMemsetAsync(keys, 0, (size_t)Q * N * 8, mpx_s(stream));
-  MPX_REQUIRE(e == hipSuccess, "mpx_linear_segmax: memset failed: %s", hipGetErrorString(e));
-  if (int rc = segmax_rows(x, ldx, w, bias, M, N, K, act, seg, 0, static_cast<unsigned long long *>(keys), stream)) return rc;
+  const hipError_t err = hipMemsetAsync(keys, 0, (size_t)Q * N * 8, mpx_s(stream));
+  MPX_REQUIRE(err == hipSuccess, "mpx_linear_segmax: memset failed: %s", hipGetErrorString(err));
+  LinearEpi e;
+  e.bias = bias, e.act = act, e.seg = seg;
+  if (int rc = linear_launch<true>("mpx_linear_segmax", x, ldx, w, M, N, K, static_cast<float *>(keys), N, e, stream)) return rc;
   mpx_segmax_unpack_launch(static_cast<const unsigned long long *>(keys), Q, N, pooled, ldp, arg, mpx_s(stream));
   MPX_LAUNCH_CHECK("mpx_linear_segmax");
 }

@@ -472,21 +472,48 @@ static int hb_check_pairs_out(const char *name, const void *yp, int N, int ldp) 
   return 0;
 }
 
+// What a linear_bf16x3_kernel launch adds to x . w^T (hb_launch; the defaults: nothing).
+struct HbEpi {
+  const float *bias = nullptr;
+  int act = MPX_ACT_NONE;
+  __bf16 *yp = nullptr;            // the result in the pairs form instead of the fp32 rows y (mpx_linear_bf16x3_to_pairs)
+  int ldp = 0;
+  const float *dact_of = nullptr;  // times act'(dact_of) (mpx_linear_bf16x3_dact)
+  int lddact = 0, dact = MPX_ACT_NONE;
+  const int32_t *seg = nullptr;    // POOL: max over each segment into the keys y, else over each 128-row group into y[M / 128]
+};
+
+// The one launch site of linear_bf16x3_kernel.  Rows past one launch's grid are walked in slabs (common.h); per slab: the
+// row operands' offsets and the zeroing of the row-max output in front of its kernel.  Launch errors: the caller's check.
+template <bool POOL>
+static int hb_launch(const char *name, const float *x, int ldx, const void *w_pairs, int M, int N, int K, float *y, int ldy,
+                     const HbEpi &e, mpx_stream_t stream) {
+  const int64_t slab = mpx_row_slab(HB_BM, 0);
+  for (int64_t m0 = 0; m0 < M; m0 += slab) {
+    const int m = (int)(M - m0 < slab ? M - m0 : slab);
+    float *ys = e.seg || !y ? y : y + (POOL ? m0 / HB_BM : m0) * ldy;  // (the keys are per segment, not per row)
+    if (POOL && !e.seg) {
+      const hipError_t err = hipMemset2DAsync(ys, (size_t)ldy * sizeof(float), 0, (size_t)N * sizeof(float),
+                                              (size_t)(m / HB_BM), mpx_s(stream));
+      MPX_REQUIRE(err == hipSuccess, "%s: memset failed: %s", name, hipGetErrorString(err));
+    }
+    hipLaunchKernelGGL((linear_bf16x3_kernel<POOL>), dim3(cdiv(N, HB_BN), cdiv(m, HB_BM)), dim3(256), 0, mpx_s(stream),
+                       x + m0 * ldx, ldx, reinterpret_cast<const __bf16 *>(w_pairs), 2 * hb_kp(K), e.bias, m, N, K, hb_kp(K),
+                       e.act, ys, ldy, e.yp ? e.yp + m0 * e.ldp : nullptr, e.ldp,
+                       e.dact_of ? e.dact_of + m0 * e.lddact : nullptr, e.lddact, e.dact, e.seg ? e.seg + m0 : nullptr,
+                       e.seg ? (int)m0 : 0);
+  }
+  return 0;
+}
+
 MPX_EXPORT int mpx_linear_bf16x3(const float *x, int ldx, const void *w_pairs, const float *bias, int M, int N, int K, int act,
                                  float *y, int ldy, mpx_stream_t stream) {
   if (hb_check("mpx_linear_bf16x3", x, ldx, w_pairs, M, N, K, ldy)) return 1;
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_bf16x3: unknown activation %d", act);
   if (M == 0) return 0;
-  if (const int64_t slab = mpx_row_slab(HB_BM, 0); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_bf16x3(x + m0 * ldx, ldx, w_pairs, bias, (int)(M - m0 < slab ? M - m0 : slab), N, K, act,
-                                     y + m0 * ldy, ldy, stream))
-        return rc;
-    return 0;
-  }
-  hipLaunchKernelGGL((linear_bf16x3_kernel<false>), dim3(cdiv(N, HB_BN), cdiv(M, HB_BM)), dim3(256), 0, mpx_s(stream), x,
-                     ldx, reinterpret_cast<const __bf16 *>(w_pairs), 2 * hb_kp(K), bias, M, N, K, hb_kp(K), act, y, ldy,
-                     (__bf16 *)nullptr, 0, (const float *)nullptr, 0, 0, static_cast<const int32_t *>(nullptr), 0);
+  HbEpi e;
+  e.bias = bias, e.act = act;
+  if (int rc = hb_launch<false>("mpx_linear_bf16x3", x, ldx, w_pairs, M, N, K, y, ldy, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear_bf16x3");
 }
 
@@ -496,16 +523,9 @@ MPX_EXPORT int mpx_linear_bf16x3_to_pairs(const float *x, int ldx, const void *w
   if (hb_check_pairs_out("mpx_linear_bf16x3_to_pairs", y_pairs, N, ldp)) return 1;
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_bf16x3_to_pairs: unknown activation %d", act);
   if (M == 0) return 0;
-  if (const int64_t slab = mpx_row_slab(HB_BM, 0); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_bf16x3_to_pairs(x + m0 * ldx, ldx, w_pairs, bias, (int)(M - m0 < slab ? M - m0 : slab), N, K, act,
-                                              static_cast<__bf16 *>(y_pairs) + m0 * ldp, ldp, stream))
-        return rc;
-    return 0;
-  }
-  hipLaunchKernelGGL((linear_bf16x3_kernel<false>), dim3(cdiv(N, HB_BN), cdiv(M, HB_BM)), dim3(256), 0, mpx_s(stream), x,
-                     ldx, reinterpret_cast<const __bf16 *>(w_pairs), 2 * hb_kp(K), bias, M, N, K, hb_kp(K), act,
-                     (float *)nullptr, 0, reinterpret_cast<__bf16 *>(y_pairs), ldp, (const float *)nullptr, 0, 0, static_cast<const int32_t *>(nullptr), 0);
+  HbEpi e;
+  e.bias = bias, e.act = act, e.yp = static_cast<__bf16 *>(y_pairs), e.ldp = ldp;
+  if (int rc = hb_launch<false>("mpx_linear_bf16x3_to_pairs", x, ldx, w_pairs, M, N, K, nullptr, 0, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear_bf16x3_to_pairs");
 }
 
@@ -514,42 +534,25 @@ MPX_EXPORT int mpx_linear_rowmax_bf16x3(const float *x, int ldx, const void *w_p
   if (hb_check("mpx_linear_rowmax_bf16x3", x, ldx, w_pairs, M, N, K, ldy)) return 1;
   MPX_REQUIRE(rows == HB_BM && M % HB_BM == 0, "mpx_linear_rowmax_bf16x3: pooled groups must be exactly %d rows", HB_BM);
   if (M == 0) return 0;
-  if (const int64_t slab = mpx_row_slab(HB_BM, 0); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_rowmax_bf16x3(x + m0 * ldx, ldx, w_pairs, bias, (int)(M - m0 < slab ? M - m0 : slab), N, K, rows,
-                                            y + (m0 / HB_BM) * ldy, ldy, stream))
-        return rc;
-    return 0;
-  }
-  hipError_t e = hipMemset2DAsync(y, (size_t)ldy * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)(M / HB_BM),
-                                  mpx_s(stream));
-  MPX_REQUIRE(e == hipSuccess, "mpx_linear_rowmax_bf16x3: memset failed: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL((linear_bf16x3_kernel<true>), dim3(cdiv(N, HB_BN), M / HB_BM), dim3(256), 0, mpx_s(stream), x, ldx,
-                     reinterpret_cast<const __bf16 *>(w_pairs), 2 * hb_kp(K), bias, M, N, K, hb_kp(K), (int)MPX_ACT_RELU, y,
-                     ldy, (__bf16 *)nullptr, 0, (const float *)nullptr, 0, 0, static_cast<const int32_t *>(nullptr), 0);
+  HbEpi e;
+  e.bias = bias, e.act = MPX_ACT_RELU;
+  if (int rc = hb_launch<true>("mpx_linear_rowmax_bf16x3", x, ldx, w_pairs, M, N, K, y, ldy, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear_rowmax_bf16x3");
 }
 
 // the grouped MLPs' last layer + activation + max over each query's rows (dense.hip: mpx_linear_segmax) in split bf16
-int mpx_segmax_unpack_launch(const unsigned long long *keys, int64_t Q, int N, float *pooled, int ldp, int64_t *arg,
-                             hipStream_t stream);  // dense.hip
-int mpx_segmax_check(const char *name, int M, const int32_t *seg, int64_t Q, int N, const void *keys, const float *pooled,
-                     int ldp, const int64_t *arg);
 MPX_EXPORT int mpx_linear_segmax_bf16x3(const float *x, int ldx, const void *w_pairs, const float *bias, int M, int N, int K,
                                         int act, const int32_t *seg, int64_t Q, void *keys, float *pooled, int ldp,
                                         int64_t *arg, mpx_stream_t stream) {
   if (hb_check("mpx_linear_segmax_bf16x3", x, ldx, w_pairs, M, N, K, N)) return 1;
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_segmax_bf16x3: unknown activation %d", act);
   if (mpx_segmax_check("mpx_linear_segmax_bf16x3", M, seg, Q, N, keys, pooled, ldp, arg)) return 1;
-  hipError_t e = hipMemsetAsync(keys, 0, (size_t)Q * N * 8, mpx_s(stream));
-  MPX_REQUIRE(e == hipSuccess, "mpx_linear_segmax_bf16x3: memset failed: %s", hipGetErrorString(e));
-  const int64_t slab = mpx_row_slab(HB_BM, 0);
-  for (int64_t m0 = 0; m0 < M; m0 += slab) {
-    const int m = (int)(M - m0 < slab ? M - m0 : slab);
-    hipLaunchKernelGGL((linear_bf16x3_kernel<true>), dim3(cdiv(N, HB_BN), cdiv(m, HB_BM)), dim3(256), 0, mpx_s(stream),
-                       x + m0 * ldx, ldx, reinterpret_cast<const __bf16 *>(w_pairs), 2 * hb_kp(K), bias, m, N, K, hb_kp(K), act,
-                       reinterpret_cast<float *>(keys), N, (__bf16 *)nullptr, 0, (const float *)nullptr, 0, 0, seg + m0, (int)m0);
-  }
+  const hipError_t err = hipMemsetAsync(keys, 0, (size_t)Q * N * 8, mpx_s(stream));
+  MPX_REQUIRE(err == hipSuccess, "mpx_linear_segmax_bf16x3: memset failed: %s", hipGetErrorString(err));
+  HbEpi e;
+  e.bias = bias, e.act = act, e.seg = seg;
+  if (int rc = hb_launch<true>("mpx_linear_segmax_bf16x3", x, ldx, w_pairs, M, N, K, static_cast<float *>(keys), N, e, stream))
+    return rc;
   mpx_segmax_unpack_launch(static_cast<const unsigned long long *>(keys), Q, N, pooled, ldp, arg, mpx_s(stream));
   MPX_LAUNCH_CHECK("mpx_linear_segmax_bf16x3");
 }
@@ -561,48 +564,51 @@ static int pb_check(const char *name, const void *a, int lda, const void *w, int
               name, K, lda);
   MPX_REQUIRE(((uintptr_t)a & 15) == 0, "%s: the activation pairs must be 16-byte aligned", name);
   MPX_REQUIRE((int64_t)N * K * 4 < ((int64_t)1 << 32) - 16, "%s: the weight pairs must stay under 4 GB", name);
-  // (rows: the entry points walk them in slabs of mpx_row_slab(Y_BM, lda * 2): activation pairs under 4 GB per launch)
+  // (rows: pb_launch walks them in slabs of mpx_row_slab(Y_BM, lda * 2): activation pairs under 4 GB per launch)
   return hb_check_w(name, w, N, K);
 }
-#define PB_LAUNCH(OUT, grid, s, ...)                                                                       \
-  do {                                                                                                      \
-    MPX_LDS_LIMIT_ONCE(linear_bf16x3_pairs_kernel<OUT>, Y_LDS, "mpx_linear_bf16x3_pairs");                  \
-    hipLaunchKernelGGL((linear_bf16x3_pairs_kernel<OUT>), grid, dim3(256), Y_LDS, s, __VA_ARGS__);          \
-  } while (0)
+
+// The one launch site of linear_bf16x3_pairs_kernel<OUT>: fp32 rows y (OUT 0, 2) or pairs yp (1, 3), the unused one null
+// with a zero leading dimension.  Rows past one launch are walked in slabs, the pooled outputs (OUT 2, 3) a row per 128.
+template <int OUT>
+static int pb_launch(const char *name, const void *a_pairs, int lda, const void *w_pairs, const float *bias, int M, int N,
+                     int K, int act, float *y, int ldy, void *y_pairs, int ldp, mpx_stream_t stream) {
+  MPX_LDS_LIMIT_ONCE(linear_bf16x3_pairs_kernel<OUT>, Y_LDS, name);
+  const int64_t slab = mpx_row_slab(Y_BM, (int64_t)lda * 2), per = OUT >= 2 ? 128 : 1;
+  const __bf16 *ap = static_cast<const __bf16 *>(a_pairs);
+  __bf16 *yp = static_cast<__bf16 *>(y_pairs);
+  for (int64_t m0 = 0; m0 < M; m0 += slab) {
+    const int m = (int)(M - m0 < slab ? M - m0 : slab);
+    hipLaunchKernelGGL((linear_bf16x3_pairs_kernel<OUT>), dim3(cdiv(N, Y_BN), cdiv(m, Y_BM)), dim3(256), Y_LDS, mpx_s(stream),
+                       ap + m0 * lda, lda, static_cast<const __bf16 *>(w_pairs), 2 * K, K, bias, m, N, act,
+                       y ? y + m0 / per * ldy : nullptr, ldy, yp ? yp + m0 / per * ldp : nullptr, ldp);
+  }
+  return 0;
+}
 
 MPX_EXPORT int mpx_linear_bf16x3_pairs(const void *a_pairs, int lda, const void *w_pairs, const float *bias, int M, int N,
                                        int K, int act, float *y, int ldy, void *y_pairs, int ldp, mpx_stream_t stream) {
-  if (pb_check("mpx_linear_bf16x3_pairs", a_pairs, lda, w_pairs, M, N, K)) return 1;
+  const char *name = "mpx_linear_bf16x3_pairs";
+  if (pb_check(name, a_pairs, lda, w_pairs, M, N, K)) return 1;
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_bf16x3_pairs: unknown activation %d", act);
   MPX_REQUIRE((y != nullptr) != (y_pairs != nullptr), "mpx_linear_bf16x3_pairs: pass either y (fp32 rows) or y_pairs");
   if (y) {
     MPX_REQUIRE(ldy >= N, "mpx_linear_bf16x3_pairs: leading dimension too small");
-  } else if (hb_check_pairs_out("mpx_linear_bf16x3_pairs", y_pairs, N, ldp)) {
+  } else if (hb_check_pairs_out(name, y_pairs, N, ldp)) {
     return 1;
   }
   if (M == 0) return 0;
-  if (const int64_t slab = mpx_row_slab(Y_BM, (int64_t)lda * 2); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_bf16x3_pairs(static_cast<const __bf16 *>(a_pairs) + m0 * lda, lda, w_pairs, bias,
-                                           (int)(M - m0 < slab ? M - m0 : slab), N, K, act, y ? y + m0 * ldy : nullptr, ldy,
-                                           y_pairs ? static_cast<__bf16 *>(y_pairs) + m0 * ldp : nullptr, ldp, stream))
-        return rc;
-    return 0;
-  }
-  const dim3 grid(cdiv(N, Y_BN), cdiv(M, Y_BM));
-  const __bf16 *ap = reinterpret_cast<const __bf16 *>(a_pairs), *wp = reinterpret_cast<const __bf16 *>(w_pairs);
-  if (y)
-    PB_LAUNCH(0, grid, mpx_s(stream), ap, lda, wp, 2 * K, K, bias, M, N, act, y, ldy, (__bf16 *)nullptr, 0);
-  else
-    PB_LAUNCH(1, grid, mpx_s(stream), ap, lda, wp, 2 * K, K, bias, M, N, act, (float *)nullptr, 0,
-              reinterpret_cast<__bf16 *>(y_pairs), ldp);
-  MPX_LAUNCH_CHECK("mpx_linear_bf16x3_pairs");
+  if (int rc = y ? pb_launch<0>(name, a_pairs, lda, w_pairs, bias, M, N, K, act, y, ldy, nullptr, 0, stream)
+                 : pb_launch<1>(name, a_pairs, lda, w_pairs, bias, M, N, K, act, nullptr, 0, y_pairs, ldp, stream))
+    return rc;
+  MPX_LAUNCH_CHECK(name);
 }
 
 MPX_EXPORT int mpx_linear_rowmax_bf16x3_pairs(const void *a_pairs, int lda, const void *w_pairs, const float *bias, int M,
                                               int N, int K, int rows, float *y, int ldy, void *y_pairs, int ldp,
                                               mpx_stream_t stream) {
-  if (pb_check("mpx_linear_rowmax_bf16x3_pairs", a_pairs, lda, w_pairs, M, N, K)) return 1;
+  const char *name = "mpx_linear_rowmax_bf16x3_pairs";
+  if (pb_check(name, a_pairs, lda, w_pairs, M, N, K)) return 1;
   MPX_REQUIRE(rows == 128 && M % 128 == 0, "mpx_linear_rowmax_bf16x3_pairs: pooled groups must be exactly 128 rows");
   MPX_REQUIRE((y != nullptr) != (y_pairs != nullptr), "mpx_linear_rowmax_bf16x3_pairs: pass either y (fp32 rows) or y_pairs");
   if (y) {
@@ -611,23 +617,10 @@ MPX_EXPORT int mpx_linear_rowmax_bf16x3_pairs(const void *a_pairs, int lda, cons
     MPX_REQUIRE(ldp >= 2 * hb_kp(N) && ((uintptr_t)y_pairs & 1) == 0, "mpx_linear_rowmax_bf16x3_pairs: bad output pairs");
   }
   if (M == 0) return 0;
-  if (const int64_t slab = mpx_row_slab(Y_BM, (int64_t)lda * 2); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_rowmax_bf16x3_pairs(static_cast<const __bf16 *>(a_pairs) + m0 * lda, lda, w_pairs, bias,
-                                                  (int)(M - m0 < slab ? M - m0 : slab), N, K, rows,
-                                                  y ? y + (m0 / 128) * ldy : nullptr, ldy,
-                                                  y_pairs ? static_cast<__bf16 *>(y_pairs) + (m0 / 128) * ldp : nullptr, ldp, stream))
-        return rc;
-    return 0;
-  }
-  const dim3 grid(cdiv(N, Y_BN), cdiv(M, Y_BM));
-  const __bf16 *ap = reinterpret_cast<const __bf16 *>(a_pairs), *wp = reinterpret_cast<const __bf16 *>(w_pairs);
-  if (y)
-    PB_LAUNCH(2, grid, mpx_s(stream), ap, lda, wp, 2 * K, K, bias, M, N, (int)MPX_ACT_RELU, y, ldy, (__bf16 *)nullptr, 0);
-  else
-    PB_LAUNCH(3, grid, mpx_s(stream), ap, lda, wp, 2 * K, K, bias, M, N, (int)MPX_ACT_RELU, (float *)nullptr, 0,
-              reinterpret_cast<__bf16 *>(y_pairs), ldp);
-  MPX_LAUNCH_CHECK("mpx_linear_rowmax_bf16x3_pairs");
+  if (int rc = y ? pb_launch<2>(name, a_pairs, lda, w_pairs, bias, M, N, K, MPX_ACT_RELU, y, ldy, nullptr, 0, stream)
+                 : pb_launch<3>(name, a_pairs, lda, w_pairs, bias, M, N, K, MPX_ACT_RELU, nullptr, 0, y_pairs, ldp, stream))
+    return rc;
+  MPX_LAUNCH_CHECK(name);
 }
 
 // ---- training (row N1) in the split-bf16 arithmetic ("AMP" of the reference, run_training.py:112 precision=16, with fp32
@@ -639,17 +632,9 @@ MPX_EXPORT int mpx_linear_bf16x3_dact(const float *x, int ldx, const void *w_pai
   MPX_REQUIRE(dact == MPX_ACT_NONE || (dact_of != nullptr && lddact >= N && (dact == MPX_ACT_RELU || dact == MPX_ACT_LEAKY)),
               "mpx_linear_bf16x3_dact: the activation's output rows are missing or too short, or the activation is unknown");
   if (M == 0) return 0;
-  if (dact == MPX_ACT_NONE) dact_of = nullptr;
-  if (const int64_t slab = mpx_row_slab(HB_BM, 0); M > slab) {
-    for (int64_t m0 = 0; m0 < M; m0 += slab)
-      if (int rc = mpx_linear_bf16x3_dact(x + m0 * ldx, ldx, w_pairs, (int)(M - m0 < slab ? M - m0 : slab), N, K,
-                                          dact_of ? dact_of + m0 * lddact : nullptr, lddact, dact, y + m0 * ldy, ldy, stream))
-        return rc;
-    return 0;
-  }
-  hipLaunchKernelGGL((linear_bf16x3_kernel<false>), dim3(cdiv(N, HB_BN), cdiv(M, HB_BM)), dim3(256), 0, mpx_s(stream), x,
-                     ldx, reinterpret_cast<const __bf16 *>(w_pairs), 2 * hb_kp(K), (const float *)nullptr, M, N, K, hb_kp(K),
-                     (int)MPX_ACT_NONE, y, ldy, (__bf16 *)nullptr, 0, dact_of, lddact, dact, static_cast<const int32_t *>(nullptr), 0);
+  HbEpi e;
+  e.dact_of = dact == MPX_ACT_NONE ? nullptr : dact_of, e.lddact = lddact, e.dact = dact;
+  if (int rc = hb_launch<false>("mpx_linear_bf16x3_dact", x, ldx, w_pairs, M, N, K, y, ldy, e, stream)) return rc;
   MPX_LAUNCH_CHECK("mpx_linear_bf16x3_dact");
 }
 

@@ -277,8 +277,6 @@ MPX_EXPORT int64_t mpx_linear_wgrad_scratch(int M, int N, int K) {
   return (int64_t)wgrad_splits(M, N, K) * ((int64_t)N * K + N);  // floats: weight partials + bias partials
 }
 
-void mpx_wgrad_bf16x3_launch(const float *dy, int lddy, const float *x, int ldx, int M, int N, int K, int rows_per_split,
-                             int S, float *partial, int with_bias, hipStream_t stream);  // dense_bf16.hip
 static int wgrad_run(const char *name, bool x3, const float *dy, int lddy, const float *x, int ldx, int M, int N, int K,
                      float *dw, float *db, float *scratch, mpx_stream_t stream);
 MPX_EXPORT int mpx_linear_wgrad(const float *dy, int lddy, const float *x, int ldx, int M, int N, int K, float *dw,

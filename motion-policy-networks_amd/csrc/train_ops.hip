@@ -370,7 +370,6 @@ static int64_t pool_wgrad_splits(int64_t Q, int C, int K) {
   if (S > maxs) S = maxs;
   return S < 1 ? 1 : (S > 65535 ? 65535 : S);
 }
-void mpx_reduce_partials_launch(const float *partial, int S, int64_t stride, int64_t n, float *out, hipStream_t stream);  // dense_grad.hip
 
 MPX_EXPORT int64_t mpx_pool_wgrad_scratch(int64_t Q, int C, int K) {
   return pool_wgrad_splits(Q, C, K) * ((int64_t)C * K + C);  // floats

@@ -542,6 +542,123 @@ def test_linear_bf16x3_pairs_chain_is_bit_identical_to_the_row_chain():
                   _lib.ptr(out), 512, _lib.ptr(p2), 1024)
 
 
+def _row_slab(bm, row_bytes):
+    """mpx_row_slab (csrc/common.h): the rows one launch of a row-blocked GEMM covers."""
+    blocks = 65528
+    if row_bytes > 0:
+        blocks = min(blocks, ((2**32 - 8192) // row_bytes // bm) & ~7)
+    return max(blocks, 8) * bm
+
+
+# a wide row stride keeps the slab of an entry that reaches its rows through 32-bit buffer offsets small: 4 MB fp32 rows
+# (2 MB pairs rows) -> 8 row blocks per launch.  The fp32-row bf16x3 entries slab by the grid limit alone (8 387 584 rows).
+SLAB_LD = (1 << 20) - 64
+SLAB_CASES = [  # (entry, K, rows past the first slab)
+    ("mpx_linear", 16, 300),  # DMA tile kernel on both slabs
+    ("mpx_linear", 20, 5),  # register-staged tile kernel; the 5-row remainder runs on the gemv kernel
+    ("mpx_linear_dact", 16, 300),
+    ("mpx_linear_rowmax", 16, 256),
+    ("mpx_linear_segmax", 20, 77),
+    ("mpx_linear_bf16x3", 4, 300),
+    ("mpx_linear_bf16x3_to_pairs", 4, 300),
+    ("mpx_linear_rowmax_bf16x3", 4, 128),
+    ("mpx_linear_segmax_bf16x3", 4, 77),
+    ("mpx_linear_bf16x3_dact", 4, 300),
+    ("mpx_linear_bf16x3_pairs:y", 16, 300),
+    ("mpx_linear_bf16x3_pairs:y_pairs", 16, 300),
+    ("mpx_linear_rowmax_bf16x3_pairs:y", 16, 128),
+    ("mpx_linear_rowmax_bf16x3_pairs:y_pairs", 16, 128),
+]
+
+
+@pytest.fixture
+def free_device_memory():
+    yield
+    torch.cuda.empty_cache()  # (a case holds up to ~6 GB)
+
+
+@pytest.mark.parametrize("case,K,r", SLAB_CASES, ids=[f"{c}-K{k}-r{r}" for c, k, r in SLAB_CASES])
+def test_dense_row_slabs_equal_one_call_per_slab(case, K, r, free_device_memory):
+    """A dense entry given more rows than one launch covers walks them in slabs (common.h: mpx_row_slab).  Its output
+    equals, bit for bit, the same entry called on the rows of each slab separately (segmax: pooled values and arg rows
+    of the per-slab calls merged, the first row winning a tie)."""
+    from mpinets_amd import _lib
+
+    entry, _, out = case.partition(":")
+    pairs_in = entry.endswith("bf16x3_pairs")
+    fp32 = "bf16x3" not in entry
+    pooled = "rowmax" in entry
+    N = 64 if fp32 or pairs_in else 16
+    if pairs_in:
+        ld, esz, slab = SLAB_LD, 2, _row_slab(256, 2 * SLAB_LD)
+    elif fp32:
+        ld, esz, slab = SLAB_LD, 4, _row_slab(128, 4 * SLAB_LD)
+    else:
+        ld, esz, slab = K, 4, _row_slab(128, 0)
+    M = slab + r
+    torch.manual_seed(31)
+    x = torch.empty((M, ld), dtype=torch.bfloat16 if pairs_in else torch.float32, device=dev())
+    if pairs_in:
+        x[:, :2 * K] = _pairs_of(torch.randn((M, K), device=dev()))
+    else:
+        x[:, :K] = torch.randn((M, K), device=dev())
+    w = torch.randn((N, K), device=dev()) / K**0.5
+    wp = w if fp32 else _pairs_of(w)
+    b = torch.randn(N, device=dev())
+    xp = lambda m0: _lib.ptr(x) + m0 * ld * esz  # noqa: E731
+
+    if "segmax" in entry:
+        seg = (torch.arange(M, device=dev(), dtype=torch.int32) // 37).contiguous()  # a segment straddles the slab edge
+
+        def segmax(m0, m):
+            s = (seg[m0:m0 + m] - seg[m0]).contiguous()
+            Q = int(s[-1]) + 1
+            keys = torch.empty((Q, N), dtype=torch.int64, device=dev())
+            p = torch.empty((Q, N), device=dev())
+            a = torch.empty((Q, N), dtype=torch.int64, device=dev())
+            _lib.call(entry, xp(m0), ld, _lib.ptr(wp), _lib.ptr(b), m, N, K, 2, _lib.ptr(s), Q, _lib.ptr(keys), _lib.ptr(p), N,
+                      _lib.ptr(a))
+            return p, a + m0
+
+        p_one, a_one = segmax(0, M)
+        p_ref = torch.full_like(p_one, -float("inf"))
+        a_ref = torch.full_like(a_one, -1)
+        for m0 in range(0, M, slab):
+            p, a = segmax(m0, min(slab, M - m0))
+            q0 = int(seg[m0])
+            better = p > p_ref[q0:q0 + p.shape[0]]  # (ties: the earlier slab holds the first row)
+            p_ref[q0:q0 + p.shape[0]][better] = p[better]
+            a_ref[q0:q0 + p.shape[0]][better] = a[better]
+        assert torch.equal(p_one, p_ref) and torch.equal(a_one, a_ref)
+        return
+
+    rows = M // 128 if pooled else M
+    if out == "y_pairs" or entry.endswith("to_pairs"):
+        ldo, osz = 2 * N, 2  # (N a multiple of 16: no pad columns)
+        mk = lambda: torch.zeros((rows, ldo), dtype=torch.bfloat16, device=dev())  # noqa: E731
+    else:
+        ldo, osz = N, 4
+        mk = lambda: torch.zeros((rows, ldo), device=dev())  # noqa: E731
+    dof = torch.randn((M, N), device=dev())
+
+    def run(y, m0, m):
+        yp = _lib.ptr(y) + (m0 // 128 if pooled else m0) * ldo * osz
+        if "dact" in entry:
+            _lib.call(entry, xp(m0), ld, _lib.ptr(wp), m, N, K, _lib.ptr(dof) + m0 * N * 4, N, 1, yp, ldo)
+        elif pairs_in:
+            o = (yp, ldo, None, 0) if out == "y" else (None, 0, yp, ldo)
+            _lib.call(entry, xp(m0), ld, _lib.ptr(wp), _lib.ptr(b), m, N, K, 128 if pooled else 2, *o)
+        else:
+            _lib.call(entry, xp(m0), ld, _lib.ptr(wp), _lib.ptr(b), m, N, K, 128 if pooled else 2, yp, ldo)
+
+    one, ref = mk(), mk()
+    run(one, 0, M)
+    for m0 in range(0, M, slab):
+        run(ref, m0, min(slab, M - m0))
+    assert torch.equal(one, ref)
+    assert bool(ref.any())
+
+
 def test_policy_forward_bf16x3_fused_front_and_pairs_on_and_off_agree():
     """The policy forward in bf16x3 with the group-all MLP layer by layer through pairs == with fp32 rows, bit for bit; the
     default -- its first two layers as ONE kernel (mpx_sa3_front_bf16x3: another order of the 16 products inside an MFMA
