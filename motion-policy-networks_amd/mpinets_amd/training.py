@@ -15,10 +15,20 @@ import torch
 from . import shard
 
 
+def _path_modules(model):
+    """The modules whose ``forward`` takes the differentiable path or the inference path by their OWN ``training`` flag:
+    the policy, its point-cloud encoder and the encoder's set-abstraction modules.  One of them left in ``eval()`` would
+    run the inference kernels inside the step and leave its weights without gradients."""
+    enc = getattr(model, "point_cloud_encoder", None)
+    return (model,) if enc is None else (model, enc, *enc.SA_modules)
+
+
 def train_step(model, optimizer: torch.optim.Optimizer, batch: Dict[str, torch.Tensor], batch_idx: int = 0,
                gradient_clip_val: float = 1.0) -> torch.Tensor:
     """One optimisation step; returns the detached loss of this rank's batch."""
-    if not model.training:  # (Module.train() walks every submodule: 0.25 ms of a 4 ms step at the reference's batch of 10)
+    # (Module.train() walks every submodule: 0.25 ms of a 4 ms step at the reference's batch of 10 -- only when a module
+    # that picks its path by its own flag is not in training mode)
+    if not all(m.training for m in _path_modules(model)):
         model.train()
     optimizer.zero_grad(set_to_none=True)
     loss = model.training_step(batch, batch_idx)

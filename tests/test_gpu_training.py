@@ -510,3 +510,34 @@ def test_groupnorm_leaky_backward_matches_torch():
         (torch.nn.functional.leaky_relu(gd(xd), 0.01) * g.double().cpu()).sum().backward()
         for a, b in zip(got, (xd.grad, gd.weight.grad, gd.bias.grad)):
             assert (a.double().cpu() - b).abs().max() <= 2e-5 * max(b.abs().max().item(), 1.0), (M, C)
+
+
+@pytest.mark.parametrize("left_in_eval", ["point_cloud_encoder", "point_cloud_encoder.SA_modules.1"])
+def test_train_step_trains_a_submodule_left_in_eval(left_in_eval):
+    """``train_step`` with the point-cloud encoder (or one set-abstraction module) in ``eval()``: the modules that pick
+    their path by their own ``training`` flag are put back in training mode, so every parameter gets a gradient, the same
+    as a fully-train step's -- bit for bit except SA1's, which sit behind the float-atomic scatter into f1 (any
+    summation order) and are held to 1e-5 of their largest element."""
+    from mpinets_amd.model import TrainingMotionPolicyNetwork
+    from mpinets_amd.training import train_step
+
+    batch = small_batch(4, 7)
+    grads = {}
+    for mode in ("train", left_in_eval):
+        torch.manual_seed(0)
+        np.random.seed(0)
+        tm = TrainingMotionPolicyNetwork(2048, 1.0, 5.0).to(dev()).train()
+        if mode != "train":
+            tm.get_submodule(mode).eval()
+        opt = torch.optim.SGD(tm.parameters(), lr=0.0)
+        train_step(tm, opt, {k: v.clone() for k, v in batch.items()}, gradient_clip_val=None)
+        assert all(m.training for m in tm.modules())
+        grads[mode] = {n: None if p.grad is None else p.grad.clone() for n, p in tm.named_parameters()}
+    ref, got = grads["train"], grads[left_in_eval]
+    missing = [n for n, g in got.items() if g is None]
+    assert not missing, f"no gradient after train_step with {left_in_eval} in eval(): {missing}"
+    for n, g in got.items():
+        if ".SA_modules.0." in n:
+            assert (g - ref[n]).abs().max() <= 1e-5 * ref[n].abs().max(), n
+        else:
+            assert torch.equal(g, ref[n]), n
