@@ -51,10 +51,25 @@ void mpx_set_error(const char *fmt, ...);
 
 static inline hipStream_t mpx_s(mpx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 // The 8 unit-queue counters (one per XCD) of `stream` on the current device, zeroed on that stream in front of the launch
-// that uses them (sa_mlp_bf16.hip; nullptr on failure).  Persistent grouped-MLP kernels take their work units from it.
+// that uses them (unit_queue.hip; nullptr on failure).  Persistent grouped-MLP kernels take their work units from it.
 unsigned int *mpx_unit_queue_for(hipStream_t stream, int *exhausted);
 int mpx_unit_queue_slots();
 void mpx_unit_queue_set_slots(int n);
+// CUs of the current device (asked once per device; 0 if the runtime cannot say)
+inline int mpx_cu_count() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  int n = cus[dev & 63].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+    cus[dev & 63].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+// THE grouped-MLP modules the fused SA kernels are built for, (C, c1, c2, c3): every dispatch and size query expands this
+#define MPX_SA_SHAPES(X) X(1, 64, 64, 64) X(64, 128, 128, 256)
+#define MPX_SA_SHAPE_IS(a, b, c, d) (C == a && c1 == b && c2 == c && c3 == d)
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ---- host helpers shared across files ----------------------------------------------------------------------------------
@@ -190,6 +205,45 @@ __device__ __forceinline__ float mpx_max_across_halves(float v) {
   const unsigned u = __float_as_uint(v);
   const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);  // r[0] = {lo, lo}, r[1] = {hi, hi}
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
+// ---- the fused set-abstraction kernels' shared vocabulary (sa_mlp.hip: fp32, sa_mlp_bf16.hip: bf16x3) ----------------------
+// The vector types, the weight packs' "no channel" marker and the operand-tile loads that both files use.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#define PAD_CH (-1)  // "no input channel" in the weight packs' channel maps
+
+// 16-byte buffer load: wave-uniform descriptor + scalar byte offset + per-lane byte offset.  All
+// address arithmetic stays on the scalar unit (no 64-bit VGPR pointers to keep alive or spill).
+__device__ __forceinline__ float4 bload16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
+  const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+  return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
+}
+// the bias of output tile `ot` as an accumulator tile: register r holds channel ot*32 + (r&3) + 8*(r>>2) + 4*half
+// (bias_tile: from the weight pack in global memory; bias_tile_lds: from a copy in LDS)
+__device__ __forceinline__ f32x16 bias_tile(__amdgpu_buffer_rsrc_t rsrc, int bias_off_bytes, int ot, int half) {
+  f32x16 v;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float4 q = bload16(rsrc, half * 16, bias_off_bytes + (ot * 32 + 8 * g) * 4);
+    v[4 * g + 0] = q.x;
+    v[4 * g + 1] = q.y;
+    v[4 * g + 2] = q.z;
+    v[4 * g + 3] = q.w;
+  }
+  return v;
+}
+__device__ __forceinline__ f32x16 bias_tile_lds(const float *bias_lds, int ot, int half) {
+  f32x16 v;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float4 q = *reinterpret_cast<const float4 *>(bias_lds + ot * 32 + 8 * g + 4 * half);
+    v[4 * g + 0] = q.x;
+    v[4 * g + 1] = q.y;
+    v[4 * g + 2] = q.z;
+    v[4 * g + 3] = q.w;
+  }
+  return v;
 }
 
 // 3x4 rigid transform: r[9] row-major rotation, t[3]

@@ -491,9 +491,8 @@ MPX_EXPORT int mpx_linear(const float *x, int ldx, const float *w, const float *
   if (M == 0) return 0;
   // short K, 128 outputs: a row per lane, W in registers (every M: one rounding order; a few rows take the gemv kernel)
   if (!gemv_fits(M, K) && rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy)) {
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
+    int cus = mpx_cu_count();
+    if (cus <= 0) cus = 256;
     const int64_t tiles = ((int64_t)M + 31) / 32, waves = (int64_t)cus * 4 * MPX_ROWLANE_WAVES;
     hipLaunchKernelGGL((linear_rowlane_kernel<34>), dim3((unsigned)(tiles < waves ? tiles : waves)), dim3(64), 0, mpx_s(stream), x,
                        ldx, w, (int64_t)M, y, ldy);

@@ -28,30 +28,14 @@
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define PAD_CH (-1)
 constexpr int SA_MAX_NSAMPLE = 256;  // slots per neighbourhood the packed kernels index their row map for
 // queries per unit of the large launches (A/B builds: narrow module 16 / 32: 10.38 / 10.14 ms -- the tail of a unit's last
 // tile is 2.7 instead of 5.5 % of its rows; wide module 8 / 16: 46.6 / 46.8 ms -- its units are already 16 tiles)
-#ifndef MPX_SA1_Q
-#define MPX_SA1_Q 32
-#endif
-#ifndef MPX_SA2_Q
-#define MPX_SA2_Q 8
-#endif
-#ifndef MPX_SA1_GR
-#define MPX_SA1_GR 2
-#endif
-#ifndef MPX_SA_SPREAD
-#define MPX_SA_SPREAD 1
-#endif
-// narrow module: pool through LDS float-max atomics into a [Q][C3] block that is written out once per unit, instead of
-// merging the row groups in registers with a flush at every query boundary (round 6: 10.06 -> 9.61 ms at 8192 environments;
-// 0 = the register merge, which also serves neighbourhoods of more than 128 slots and unaligned output rows)
-#ifndef MPX_SA1_LDSPOOL
-#define MPX_SA1_LDSPOOL 1
-#endif
+constexpr int SA1_Q = 32, SA2_Q = 8;
+// rows of a neighbourhood are rounded up to GR (repeating its first member): 4 for the wide module (62 rows per query on
+// the bench scenes: 2 % of padding, eight pooling groups per tile), 2 for the narrow one (15 rows per query: the padding
+// was 9 % of its matrix work; sixteen pooling groups per tile instead of eight cost less than that)
+constexpr int SA1_GR = 2, SA2_GR = 4;
 
 template <int CF, int C1, int C2, int C3>
 struct SaCfg {
@@ -115,29 +99,6 @@ __global__ void __launch_bounds__(256)
 // ---- the fused kernel ----------------------------------------------------------------------------------
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// 16-byte buffer load: wave-uniform descriptor + scalar byte offset + per-lane byte offset.  All
-// address arithmetic stays on the scalar unit (no 64-bit VGPR pointers to keep alive or spill).
-__device__ __forceinline__ float4 bload16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-  const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-  return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
-}
-
-__device__ __forceinline__ f32x16 bias_tile(__amdgpu_buffer_rsrc_t rsrc, int bias_off_bytes, int ot, int half) {
-  // register r of a tile holds channel ot*32 + (r&3) + 8*(r>>2) + 4*half
-  f32x16 v;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4 q = bload16(rsrc, half * 16, bias_off_bytes + (ot * 32 + 8 * g) * 4);
-    v[4 * g + 0] = q.x;
-    v[4 * g + 1] = q.y;
-    v[4 * g + 2] = q.z;
-    v[4 * g + 3] = q.w;
-  }
-  return v;
 }
 
 __device__ __forceinline__ float comp(const float4 &q, int i) {
@@ -322,16 +283,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF == 1
                          int out_stride, int bpe, const float *__restrict__ pre_rows, const float *__restrict__ ctr,
                          int append_centre, unsigned int *__restrict__ queue) {
   using Cfg = SaCfg<CF, C1, C2, C3>;
-  // rows of a neighbourhood are rounded up to GR (repeating its first member): 4 for the wide module (62 rows per query on
-  // the bench scenes: 2 % of padding, eight pooling groups per tile), 2 for the narrow one (15 rows per query: the padding
-  // was 9 % of its matrix work; sixteen pooling groups per tile instead of eight cost less than that)
-  constexpr int GR = CF == 1 ? MPX_SA1_GR : 4, NGRP = 32 / GR;
+  constexpr int GR = CF == 1 ? SA1_GR : SA2_GR, NGRP = 32 / GR;
   static_assert(GR == 2 || GR == 4, "pooling groups of 2 or 4 rows");
   __shared__ float ctr_s[FACT ? Q * C1 : 1];
-  // LPOOL: a lane's row groups go to their query's row of pool_s by ds_max_f32 (16 rows x 2 output tiles of the narrow
-  // module = 2.1 queries per tile on the bench scenes: the register merge below walked 16 groups with a readlane, a compare
-  // and a select each and flushed at every boundary -- 3 VALU per MFMA on the counters against 0.8 inside the stream)
-  constexpr bool LPOOL = CF == 1 && !FACT && MPX_SA1_LDSPOOL != 0 && MAXNS <= 128;
+  // LPOOL (the narrow module): a lane's row groups go to their query's row of pool_s by ds_max_f32, a [Q][C3] block that is
+  // written out once per unit (16 rows x 2 output tiles = 2.1 queries per tile on the bench scenes: the register merge
+  // below walked 16 groups with a readlane, a compare and a select each and flushed at every boundary -- 3 VALU per MFMA on
+  // the counters against 0.8 inside the stream; round 6: 10.06 -> 9.61 ms at 8192 environments).  The register merge
+  // serves neighbourhoods of more than 128 slots and unaligned output rows.
+  constexpr bool LPOOL = CF == 1 && !FACT && MAXNS <= 128;
   __shared__ __attribute__((aligned(16))) float pool_s[LPOOL ? Q * C3 : 1];
   __shared__ __attribute__((aligned(16))) unsigned char qmap_s[Q * MAXNS / GR + 32];  // (row group -> query; rows per query <= nsample <= MAXNS)
   // biases in LDS: they initialise the accumulators at every tile and are added at every flush -- as global loads
@@ -369,7 +329,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF == 1
   // prefetches the first chunk of the next tile (same addresses; also across units).  Only the very first chunk of a
   // wave is exposed.
   constexpr int G1 = FACT ? 0 : Cfg::S1 / 4, G2 = Cfg::S2 / 4, G3 = Cfg::S3 / 4, GT = G1 + G2 + G3;
-  constexpr bool LAZY = FACT && MPX_SA_SPREAD;  // (the factored wide module; C1 / 8 = 16 float4 per gathered row half)
+  constexpr bool LAZY = FACT;  // (the factored wide module; C1 / 8 = 16 float4 per gathered row half)
   constexpr int CH = 4, NC0 = (GT + CH - 1) / CH, NC = NC0 + (NC0 & 1);  // even: the ring parity repeats per tile
   constexpr int GPT = Cfg::KS2 / 4;                                      // weight groups per layer-3 output tile
   float4 ring[2][CH];
@@ -451,20 +411,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF == 1
   if (lane < 32 / GR) qmap_s[total / GR + lane] = (unsigned char)(nq - 1);
 
   __syncthreads();  // (biases / query terms visible; a one-wave workgroup: no more than the LDS wait)
-  // register r of a tile holds channel ot*32 + (r&3) + 8*(r>>2) + 4*half
-  auto bias_lds = [&](const float *bs, int ot) __attribute__((always_inline)) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 q = *reinterpret_cast<const float4 *>(bs + ot * 32 + 8 * g + 4 * half);
-      v[4 * g + 0] = q.x;
-      v[4 * g + 1] = q.y;
-      v[4 * g + 2] = q.z;
-      v[4 * g + 3] = q.w;
-    }
-    return v;
-  };
-
+  auto bias_lds = [&](const float *bs, int ot) __attribute__((always_inline)) { return bias_tile_lds(bs, ot, half); };
   const int qbase = (int)q0;  // query ids fit 31 bits (checked by the launcher)
   if constexpr (!FACT) {
     // columns [C3, C3+4) of this wave's output rows <- [centre xyz | 0]: the rows become the operand [f | xyz | 0] of
@@ -760,7 +707,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF == 1
       // (a cluster of memory instructions costs matrix-pipe time even with other waves on the SIMD: measured on the
       // group-all kernel, sa3_chain.hip, 0.90 -> 0.98 of the matrix floor inside the layer loops)
       // (the narrow first module, four waves per SIMD, did not gain: 10.8 -> 11.0 ms; it keeps the compiler's order)
-      if constexpr (MPX_SA_SPREAD && CF != 1) {
+      if constexpr (CF != 1) {
         constexpr int c_ot1 = (G1 + G2 + GPT) / CH;  // first chunk of the second output tile of layer 3
         if (LAZY && c >= c_ot1 && c < c_ot1 + 4) {   // these chunks also carry a quarter of the next tile's gather
 #pragma unroll
@@ -798,18 +745,28 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF == 1
 }
 
 // ---- host entry points -----------------------------------------------------------------------------------
-// wave slots of the current device for a one-wave workgroup at `per_cu` waves per CU (the persistent launches' grid;
-// a multiple of 8: the hardware deals workgroups to the XCDs round-robin)
-static int64_t sa_wave_slots(int per_cu) {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  int n = cus[dev & 63].load(std::memory_order_relaxed);
-  if (n == 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
-    cus[dev & 63].store(n, std::memory_order_relaxed);
+// The launch plan of the packed kernel at Q queries per unit: units of whole environments per XCD when the grid is regular
+// (bpe; npoint % Q == 0, B % 8 == 0), and with many units per wave slot (per_cu one-wave workgroups per CU) the persistent
+// form: one workgroup per slot -- a multiple of 8: the hardware deals workgroups to the XCDs round-robin -- and the units
+// from the device-side queue.  A stream without a private queue slot keeps one unit per wave.
+struct SaPlan {
+  int64_t grid;
+  int bpe;
+  unsigned int *queue;
+};
+template <int Q>
+static int sa_plan(int64_t nq, int B, int npoint, int per_cu, mpx_stream_t stream, const char *name, SaPlan *p) {
+  p->grid = (nq + Q - 1) / Q;
+  p->bpe = (npoint % Q == 0 && B % 8 == 0) ? npoint / Q : 0;
+  p->queue = nullptr;
+  const int64_t slots = ((int64_t)mpx_cu_count() * per_cu) & ~(int64_t)7;
+  if (slots > 0 && p->grid >= 4 * slots) {
+    int exhausted = 0;
+    p->queue = mpx_unit_queue_for(mpx_s(stream), &exhausted);
+    MPX_REQUIRE(p->queue || exhausted, "%s: cannot reset the unit queue", name);
+    if (p->queue) p->grid = slots;
   }
-  return ((int64_t)n * per_cu) & ~(int64_t)7;
+  return 0;
 }
 template <int CF, int C1, int C2, int C3>
 static int launch_sa(const float *xyz, int stride, const float *new_xyz, int new_stride, const float *feat,
@@ -824,39 +781,26 @@ static int launch_sa(const float *xyz, int stride, const float *new_xyz, int new
     // queries per wave: 8-16 tiles of work on typical scenes.  A small batch (a single planning problem up to a few
     // dozen) would leave most CUs idle at that size, so it runs QS queries per wave instead: same rows, same
     // arithmetic per row (bit-identical results), 4x the waves and a quarter of the latency.
-    constexpr int QL = CF == 1 ? MPX_SA1_Q : 8, QS = CF == 1 ? 4 : 2;
+    constexpr int QL = CF == 1 ? SA1_Q : 8, QS = CF == 1 ? 4 : 2;
     int rc = 0;
     auto go = [&](auto qtag) {
       constexpr int Q = decltype(qtag)::value;
-      int64_t nw = (nq + Q - 1) / Q;
-      // whole environments per XCD when the grid is regular (npoint % Q == 0, B % 8 == 0)
-      const int bpe = (npoint % Q == 0 && B % 8 == 0) ? npoint / Q : 0;
-      unsigned int *queue = nullptr;
-      const int64_t slots = sa_wave_slots(CF == 1 ? 16 : 8);
-      if (slots > 0 && nw >= 4 * slots) {  // many units per wave slot: one workgroup per slot, units from the device-side queue
-        int exhausted = 0;
-        queue = mpx_unit_queue_for(mpx_s(stream), &exhausted);
-        if (!queue && !exhausted) {
-          mpx_set_error("mpx_sa_mlp: cannot reset the unit queue");
-          rc = 1;
-          return;
-        }
-        if (queue) nw = slots;  // (no private slot left for this stream: one unit per wave, no queue)
-      }
+      SaPlan plan;
+      if ((rc = sa_plan<Q>(nq, B, npoint, CF == 1 ? 16 : 8, stream, "mpx_sa_mlp", &plan))) return;
       // (the narrow module with <= 128 slots per neighbourhood and 16-byte aligned output rows: the form with the small
       // row map that pools through LDS, see LPOOL in the kernel)
       bool lpool = false;
-      if constexpr (CF == 1 && MPX_SA1_LDSPOOL != 0) {
+      if constexpr (CF == 1) {
         lpool = nsample <= 128 && out_stride % 4 == 0 && ((uintptr_t)out & 15) == 0;
         if (lpool)
-          hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false, 128>), dim3((unsigned)nw), dim3(64), 0,
+          hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false, 128>), dim3((unsigned)plan.grid), dim3(64), 0,
                              mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint,
-                             nsample, wpack, out, out_stride, bpe, nullptr, nullptr, append_centre, queue);
+                             nsample, wpack, out, out_stride, plan.bpe, nullptr, nullptr, append_centre, plan.queue);
       }
       if (!lpool)
-        hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false>), dim3((unsigned)nw), dim3(64), 0,
+        hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false>), dim3((unsigned)plan.grid), dim3(64), 0,
                            mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint,
-                           nsample, wpack, out, out_stride, bpe, nullptr, nullptr, append_centre, queue);
+                           nsample, wpack, out, out_stride, plan.bpe, nullptr, nullptr, append_centre, plan.queue);
     };
     if (nq >= 1024 * QL) go(std::integral_constant<int, QL>{});
     else go(std::integral_constant<int, QS>{});
@@ -868,14 +812,6 @@ static int launch_sa(const float *xyz, int stride, const float *new_xyz, int new
   }
   MPX_LAUNCH_CHECK("mpx_sa_mlp");
 }
-
-#define SA_DISPATCH(CALL)                                                          \
-  if (C == 1 && c1 == 64 && c2 == 64 && c3 == 64) { CALL(1, 64, 64, 64); }         \
-  else if (C == 64 && c1 == 128 && c2 == 128 && c3 == 256) { CALL(64, 128, 128, 256); } \
-  else {                                                                           \
-    mpx_set_error("mpx_sa: unsupported MLP (C=%d, %d, %d, %d)", C, c1, c2, c3);    \
-    return 1;                                                                      \
-  }
 
 MPX_EXPORT int mpx_sa_mlp(const float *xyz, int stride, const float *new_xyz, int new_stride,
                           const float *feat, int feat_stride, int C, const int32_t *idx, const int32_t *cnt, int B,
@@ -889,9 +825,11 @@ MPX_EXPORT int mpx_sa_mlp(const float *xyz, int stride, const float *new_xyz, in
   MPX_REQUIRE(((uintptr_t)wpack & 15) == 0, "mpx_sa_mlp: wpack must be 16-byte aligned");
   if (B == 0 || npoint == 0) return 0;
 #define CALL(a, b, c, d) \
-  return launch_sa<a, b, c, d>(xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, B, N, npoint, nsample, wpack, out, out_stride, append_centre, stream)
-  SA_DISPATCH(CALL)
+  if (MPX_SA_SHAPE_IS(a, b, c, d)) return launch_sa<a, b, c, d>(xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, B, N, npoint, nsample, wpack, out, out_stride, append_centre, stream);
+  MPX_SA_SHAPES(CALL)
 #undef CALL
+  mpx_set_error("mpx_sa: unsupported MLP (C=%d, %d, %d, %d)", C, c1, c2, c3);
+  return 1;
 }
 
 MPX_EXPORT int mpx_sa_mlp_factored(const float *pre, const float *ctr, const int32_t *idx, const int32_t *cnt, int B,
@@ -911,25 +849,13 @@ MPX_EXPORT int mpx_sa_mlp_factored(const float *pre, const float *ctr, const int
   int rc = 0;
   auto go = [&](auto qtag) {  // queries per wave: 8, or 2 / 1 for small batches (see launch_sa)
     constexpr int Q = decltype(qtag)::value;
-    int64_t nw = (nq + Q - 1) / Q;
-    const int bpe = (npoint % Q == 0 && B % 8 == 0) ? npoint / Q : 0;
-    unsigned int *queue = nullptr;
-    const int64_t slots = sa_wave_slots(8);
-    if (slots > 0 && nw >= 4 * slots) {  // (see launch_sa)
-      int exhausted = 0;
-      queue = mpx_unit_queue_for(mpx_s(stream), &exhausted);
-      if (!queue && !exhausted) {
-        mpx_set_error("mpx_sa_mlp_factored: cannot reset the unit queue");
-        rc = 1;
-        return;
-      }
-      if (queue) nw = slots;  // (no private slot left for this stream: one unit per wave, no queue)
-    }
-    hipLaunchKernelGGL((sa_mlp_packed_kernel<64, 128, 128, 256, Q, true>), dim3((unsigned)nw), dim3(64), 0,
+    SaPlan plan;
+    if ((rc = sa_plan<Q>(nq, B, npoint, 8, stream, "mpx_sa_mlp_factored", &plan))) return;
+    hipLaunchKernelGGL((sa_mlp_packed_kernel<64, 128, 128, 256, Q, true>), dim3((unsigned)plan.grid), dim3(64), 0,
                        mpx_s(stream), nullptr, 0, nullptr, 0, nullptr, 0, idx, cnt, nq, N, npoint, nsample, wpack, out,
-                       out_stride, bpe, pre, ctr, 0, queue);
+                       out_stride, plan.bpe, pre, ctr, 0, plan.queue);
   };
-  if (nq >= 1024 * MPX_SA2_Q) go(std::integral_constant<int, MPX_SA2_Q>{});
+  if (nq >= 1024 * SA2_Q) go(std::integral_constant<int, SA2_Q>{});
   else if (nq >= 1024) go(std::integral_constant<int, 2>{});
   else go(std::integral_constant<int, 1>{});  // a handful of problems: one query (1-2 tiles) per wave
   if (rc) return rc;
@@ -937,9 +863,9 @@ MPX_EXPORT int mpx_sa_mlp_factored(const float *pre, const float *ctr, const int
 }
 
 MPX_EXPORT int64_t mpx_sa_pack_size(int C, int c1, int c2, int c3) {
-#define CALL(a, b, c, d) return SaCfg<a, b, c, d>::TOTAL
-  if (C == 1 && c1 == 64 && c2 == 64 && c3 == 64) { CALL(1, 64, 64, 64); }
-  else if (C == 64 && c1 == 128 && c2 == 128 && c3 == 256) { CALL(64, 128, 128, 256); }
+#define CALL(a, b, c, d) \
+  if (MPX_SA_SHAPE_IS(a, b, c, d)) return SaCfg<a, b, c, d>::TOTAL;
+  MPX_SA_SHAPES(CALL)
 #undef CALL
   return -1;
 }
@@ -956,7 +882,10 @@ static int launch_pack(const float *w1, const float *b1, const float *w2, const 
 MPX_EXPORT int mpx_sa_pack_weights(const float *w1, const float *b1, const float *w2, const float *b2,
                                    const float *w3, const float *b3, int C, int c1, int c2, int c3,
                                    float *wpack, mpx_stream_t stream) {
-#define CALL(a, b, c, d) return launch_pack<a, b, c, d>(w1, b1, w2, b2, w3, b3, wpack, stream)
-  SA_DISPATCH(CALL)
+#define CALL(a, b, c, d) \
+  if (MPX_SA_SHAPE_IS(a, b, c, d)) return launch_pack<a, b, c, d>(w1, b1, w2, b2, w3, b3, wpack, stream);
+  MPX_SA_SHAPES(CALL)
 #undef CALL
+  mpx_set_error("mpx_sa: unsupported MLP (C=%d, %d, %d, %d)", C, c1, c2, c3);
+  return 1;
 }

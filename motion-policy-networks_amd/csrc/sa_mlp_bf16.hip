@@ -17,26 +17,14 @@
 // split into packed bf16 hi/lo pairs in place and are the next layer's B operand as they are.
 #include "common.h"
 
-#include <mutex>
-#include <unordered_map>
-
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#define PAD_CH (-1)
-#ifndef MPX_BF16_G
-#define MPX_BF16_G 8
-#endif
-#ifndef MPX_BF16_WAVES
-#define MPX_BF16_WAVES 8
-#endif
-constexpr int G = MPX_BF16_G;             // step-tiles per chunk
+constexpr int G = 8;                      // step-tiles per chunk
 constexpr int TILE_BYTES = 2048;          // w_hi (64 lanes x 16 B) + w_lo
 constexpr int CHUNK_BYTES = G * TILE_BYTES;
-constexpr int WAVES = MPX_BF16_WAVES;
+constexpr int WAVES = 8;                  // lockstep waves per workgroup
 
 template <int CF, int C1, int C2, int C3>
 struct BCfg {
@@ -148,24 +136,6 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf16x8 &hi, bf16x8 &
   }
 }
 
-__device__ __forceinline__ float4 bload16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-  const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-  return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
-}
-
-__device__ __forceinline__ f32x16 bias_tile(__amdgpu_buffer_rsrc_t rsrc, int bias_off_bytes, int ot, int half) {
-  f32x16 v;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4 q = bload16(rsrc, half * 16, bias_off_bytes + (ot * 32 + 8 * g) * 4);
-    v[4 * g + 0] = q.x;
-    v[4 * g + 1] = q.y;
-    v[4 * g + 2] = q.z;
-    v[4 * g + 3] = q.w;
-  }
-  return v;
-}
-
 // relu + split one accumulator tile into the two K16 operand pairs of the next layer
 __device__ __forceinline__ void relu_split_tile(const f32x16 &acc, bf16x8 (&hi)[2], bf16x8 (&lo)[2]) {
 #pragma unroll
@@ -253,19 +223,6 @@ struct RawIn {
     }
   }
 };
-
-__device__ __forceinline__ f32x16 bias_tile_lds(const float *bias_lds, int ot, int half) {
-  f32x16 v;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4 q = *reinterpret_cast<const float4 *>(bias_lds + ot * 32 + 8 * g + 4 * half);
-    v[4 * g + 0] = q.x;
-    v[4 * g + 1] = q.y;
-    v[4 * g + 2] = q.z;
-    v[4 * g + 3] = q.w;
-  }
-  return v;
-}
 
 // Q queries per wave; their DISTINCT neighbours (count from the ball query; padding repeats the first
 // neighbour, and max-pooling is idempotent) are rounded up to multiples of 4 rows and packed back to
@@ -525,14 +482,11 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 // 32-row tiles exactly as above, reads every weight operand from LDS (lane-linear 16-byte reads), and keeps the same
 // arithmetic (split products, fp32 accumulate, exact fp32 bias) and operand layouts -- the pack of mpx_sa_pack_bf16x3 is
 // used as it is.  Four waves per SIMD cover each other's gather / split / pooling phases.
-#ifndef MPX_RES_OCC
-#define MPX_RES_OCC 4
-#endif
 namespace res {
-constexpr int WV = 4;
+constexpr int WV = 4, OCC = 4;  // waves per workgroup; waves per SIMD
 }
 template <int CF, int C1, int C2, int C3, int Q, bool ONE_ENV>
-__global__ void __launch_bounds__(64 * res::WV) __attribute__((amdgpu_waves_per_eu(MPX_RES_OCC, MPX_RES_OCC)))
+__global__ void __launch_bounds__(64 * res::WV) __attribute__((amdgpu_waves_per_eu(res::OCC, res::OCC)))
     sa_mlp_bf16_resident_kernel(const float *__restrict__ xyz, int stride, const float *__restrict__ new_xyz,
                                 int new_stride, const float *__restrict__ feat, int feat_stride,
                                 const int32_t *__restrict__ idx, const int32_t *__restrict__ cnt, int64_t n_query, int N,
@@ -828,52 +782,6 @@ static_assert(Cfg::ST2 == 32 && Cfg::ST3 == 64 && Cfg::KS1 == 8 && Cfg::KS2 == 8
 }  // namespace v2
 
 #define V2_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-// Unit queues of the persistent kernel: 8 counters (one per XCD) per launch, in device memory that belongs to the
-// library image (nothing is allocated).  ONE SLOT PER (device, stream): the launches of a stream are ordered (memset,
-// kernel, memset, kernel, ...), so they can share a slot, and launches on different streams never alias -- two engines
-// that share a model on two streams each get their own counters.  The slot is zeroed on the
-// launch stream in front of the kernel (stream-ordered, hipGraph-capturable).  Limits, stated in include/mpinets_hip.h:
-// 256 distinct (device, stream) handles per process get a slot; a later handle gets NONE (`*exhausted` = 1, nullptr):
-// slots are never shared between streams -- two persistent kernels on one set of counters would each skip the units
-// the other claimed and leave output rows unwritten -- so the fp32 launchers fall back to their one-unit-per-wave
-// grids and the bf16x3 launcher reports an error.  A captured graph bakes its capture stream's slot in, so two graphs
-// captured on the SAME stream must not be replayed concurrently on different streams.
-__device__ unsigned int sa2_unit_queues[256 * 8];
-unsigned int *mpx_unit_queue_for(hipStream_t stream, int *exhausted) {
-  static std::mutex mu;
-  static std::unordered_map<unsigned long long, int> slot_of;  // (device << 56) ^ stream handle -> slot
-  static unsigned int *base[64];
-  if (exhausted) *exhausted = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  unsigned int *q;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    unsigned int *&b = base[dev & 63];
-    if (!b) {
-      void *p = nullptr;
-      if (hipGetSymbolAddress(&p, HIP_SYMBOL(sa2_unit_queues)) != hipSuccess) return nullptr;
-      b = static_cast<unsigned int *>(p);
-    }
-    const unsigned long long key = ((unsigned long long)(dev & 63) << 56) ^ (unsigned long long)(uintptr_t)stream;
-    auto it = slot_of.find(key);
-    if (it == slot_of.end()) {
-      if (slot_of.size() >= (size_t)mpx_unit_queue_slots()) {
-        if (exhausted) *exhausted = 1;
-        return nullptr;
-      }
-      it = slot_of.emplace(key, (int)slot_of.size()).first;
-    }
-    q = b + 8 * it->second;
-  }
-  if (hipMemsetAsync(q, 0, 8 * sizeof(unsigned int), stream) != hipSuccess) return nullptr;
-  return q;
-}
-// (verification hook: tests shrink the slot count to reach the exhausted path without creating 256 streams)
-static std::atomic<int> unit_queue_slots{256};
-int mpx_unit_queue_slots() { return unit_queue_slots.load(); }
-void mpx_unit_queue_set_slots(int n) { unit_queue_slots.store(n < 0 ? 0 : n > 256 ? 256 : n); }
 
 template <bool PROBE = false>
 __global__ void __launch_bounds__(64 * v2::WV) __attribute__((amdgpu_waves_per_eu(1, 1)))
@@ -1352,14 +1260,6 @@ __global__ void __launch_bounds__(64 * v2::WV) __attribute__((amdgpu_waves_per_e
 }
 
 // ---- host entry points --------------------------------------------------------------------------------------------
-#define SA_DISPATCH(CALL)                                                                   \
-  if (C == 1 && c1 == 64 && c2 == 64 && c3 == 64) { CALL(1, 64, 64, 64); }                  \
-  else if (C == 64 && c1 == 128 && c2 == 128 && c3 == 256) { CALL(64, 128, 128, 256); }     \
-  else {                                                                                    \
-    mpx_set_error("mpx_sa (bf16x3): unsupported MLP (C=%d, %d, %d, %d)", C, c1, c2, c3);    \
-    return 1;                                                                               \
-  }
-
 // Which kernel serves mpx_sa_mlp_bf16x3: the weight-resident one for the first module (pack fits LDS) up to 128 slots
 // per neighbourhood, the lockstep one otherwise.  ONE predicate for the launcher and for mpx_sa_mlp_bf16x3_wants_order.
 static bool bf16_uses_resident(int C, int c1, int c2, int c3, int nsample) {
@@ -1381,14 +1281,13 @@ static int launch_sa_bf16(const float *xyz, int stride, const float *new_xyz, in
       const int row16 = (feat == xyz + 3 && stride == 4 && feat_stride == 4 && ((uintptr_t)xyz & 15) == 0) ? 1 : 0;
       const dim3 grid((unsigned)((nq + per_wg - 1) / per_wg));
       const unsigned char *wp = static_cast<const unsigned char *>(wpack);
-      if (npoint % Q == 0)  // a wave's queries share their environment
-        hipLaunchKernelGGL((sa_mlp_bf16_resident_kernel<CF, C1, C2, C3, Q, true>), grid, dim3(64 * res::WV), 0, mpx_s(stream),
-                           xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint, nsample, wp, out,
-                           out_stride, wpe, row16, append_centre);
-      else
-        hipLaunchKernelGGL((sa_mlp_bf16_resident_kernel<CF, C1, C2, C3, Q, false>), grid, dim3(64 * res::WV), 0, mpx_s(stream),
-                           xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint, nsample, wp, out,
-                           out_stride, wpe, row16, append_centre);
+      auto go = [&](auto one_env) {  // ONE_ENV: a wave's queries share their environment
+        hipLaunchKernelGGL((sa_mlp_bf16_resident_kernel<CF, C1, C2, C3, Q, decltype(one_env)::value>), grid, dim3(64 * res::WV), 0,
+                           mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint, nsample,
+                           wp, out, out_stride, wpe, row16, append_centre);
+      };
+      if (npoint % Q == 0) go(std::true_type{});
+      else go(std::false_type{});
       MPX_LAUNCH_CHECK("mpx_sa_mlp_bf16x3");
     }
   }
@@ -1423,34 +1322,24 @@ MPX_EXPORT int mpx_sa_mlp_bf16x3_factored(const float *pre, const float *ctr, co
   const int64_t nq = (int64_t)B * npoint;
   MPX_REQUIRE(nq < ((int64_t)1 << 31), "mpx_sa_mlp_bf16x3_factored: too many query points");
   (void)order;  // the persistent kernel takes its units from a device-side queue: no sorting pass
-  static int cus[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!cus[dev & 63]) {
-    int n = 0;
-    MPX_REQUIRE(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0,
-                "mpx_sa_mlp_bf16x3_factored: cannot query the CU count");
-    cus[dev & 63] = n;
-  }
-  const int grid = cus[dev & 63];
+  const int grid = mpx_cu_count();
+  MPX_REQUIRE(grid > 0, "mpx_sa_mlp_bf16x3_factored: cannot query the CU count");
   const int xcd_aware = (B % 8 == 0 && grid % 8 == 0 && npoint % v2::Q == 0) ? 1 : 0;
-  MPX_LDS_LIMIT_ONCE(sa2_bf16x3_persistent_kernel<false>, v2::LDS_BYTES, "mpx_sa_mlp_bf16x3_factored");
   int exhausted = 0;
   unsigned int *queue = mpx_unit_queue_for(mpx_s(stream), &exhausted);
   MPX_REQUIRE(queue != nullptr, exhausted ? "mpx_sa_mlp_bf16x3_factored: no unit-queue slot left for this stream (256 "
                                             "distinct streams per process; reuse streams)"
                                           : "mpx_sa_mlp_bf16x3_factored: cannot reset the unit queue");
-  if (g_sa2_probe) {  // (measurement only: mpx_sa2_bf16x3_set_probe)
-    MPX_LDS_LIMIT_ONCE(sa2_bf16x3_persistent_kernel<true>, v2::LDS_BYTES, "mpx_sa_mlp_bf16x3_factored");
-    hipLaunchKernelGGL(sa2_bf16x3_persistent_kernel<true>, dim3(grid), dim3(64 * v2::WV), v2::LDS_BYTES, mpx_s(stream), idx, cnt,
+  auto go = [&](auto probe_tag, long long *probe) -> int {
+    constexpr bool PROBE = decltype(probe_tag)::value;
+    MPX_LDS_LIMIT_ONCE(sa2_bf16x3_persistent_kernel<PROBE>, v2::LDS_BYTES, "mpx_sa_mlp_bf16x3_factored");
+    hipLaunchKernelGGL(sa2_bf16x3_persistent_kernel<PROBE>, dim3(grid), dim3(64 * v2::WV), v2::LDS_BYTES, mpx_s(stream), idx, cnt,
                        nq, N, npoint, nsample, static_cast<const unsigned char *>(wpack), out, out_stride, pre, ctr, xcd_aware,
-                       queue, g_sa2_probe);
+                       queue, probe);
     MPX_LAUNCH_CHECK("mpx_sa_mlp_bf16x3_factored");
-  }
-  hipLaunchKernelGGL(sa2_bf16x3_persistent_kernel<false>, dim3(grid), dim3(64 * v2::WV), v2::LDS_BYTES, mpx_s(stream), idx, cnt,
-                     nq, N, npoint, nsample, static_cast<const unsigned char *>(wpack), out, out_stride, pre, ctr, xcd_aware,
-                     queue, (long long *)nullptr);
-  MPX_LAUNCH_CHECK("mpx_sa_mlp_bf16x3_factored");
+  };
+  // (PROBE, measurement only: mpx_sa2_bf16x3_set_probe)
+  return g_sa2_probe ? go(std::true_type{}, g_sa2_probe) : go(std::false_type{}, (long long *)nullptr);
 }
 
 // measurement only: route the next launches of the persistent kernel through its PROBE instantiation,
@@ -1473,9 +1362,11 @@ MPX_EXPORT int mpx_sa_mlp_bf16x3(const float *xyz, int stride, const float *new_
   MPX_REQUIRE(((uintptr_t)wpack & 15) == 0, "mpx_sa_mlp_bf16x3: wpack must be 16-byte aligned");
   if (B == 0 || npoint == 0) return 0;
 #define CALL(a, b, c, d) \
-  return launch_sa_bf16<a, b, c, d>(xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, order, B, N, npoint, nsample, wpack, out, out_stride, append_centre, stream)
-  SA_DISPATCH(CALL)
+  if (MPX_SA_SHAPE_IS(a, b, c, d)) return launch_sa_bf16<a, b, c, d>(xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, order, B, N, npoint, nsample, wpack, out, out_stride, append_centre, stream);
+  MPX_SA_SHAPES(CALL)
 #undef CALL
+  mpx_set_error("mpx_sa (bf16x3): unsupported MLP (C=%d, %d, %d, %d)", C, c1, c2, c3);
+  return 1;
 }
 
 // 1: mpx_sa_mlp_bf16x3 walks the queries in the caller's `order` for this module (the lockstep kernel: balanced
@@ -1485,8 +1376,10 @@ MPX_EXPORT int mpx_sa_mlp_bf16x3_wants_order(int C, int c1, int c2, int c3, int 
 }
 
 MPX_EXPORT int64_t mpx_sa_pack_bf16x3_size(int C, int c1, int c2, int c3) {
-  if (C == 1 && c1 == 64 && c2 == 64 && c3 == 64) return BCfg<1, 64, 64, 64>::TOTAL_BYTES;
-  if (C == 64 && c1 == 128 && c2 == 128 && c3 == 256) return BCfg<64, 128, 128, 256>::TOTAL_BYTES;
+#define CALL(a, b, c, d) \
+  if (MPX_SA_SHAPE_IS(a, b, c, d)) return BCfg<a, b, c, d>::TOTAL_BYTES;
+  MPX_SA_SHAPES(CALL)
+#undef CALL
   return -1;
 }
 
@@ -1503,7 +1396,10 @@ static int launch_pack_bf16(const float *w1, const float *b1, const float *w2, c
 MPX_EXPORT int mpx_sa_pack_bf16x3(const float *w1, const float *b1, const float *w2, const float *b2,
                                   const float *w3, const float *b3, int C, int c1, int c2, int c3, void *wpack,
                                   mpx_stream_t stream) {
-#define CALL(a, b, c, d) return launch_pack_bf16<a, b, c, d>(w1, b1, w2, b2, w3, b3, wpack, stream)
-  SA_DISPATCH(CALL)
+#define CALL(a, b, c, d) \
+  if (MPX_SA_SHAPE_IS(a, b, c, d)) return launch_pack_bf16<a, b, c, d>(w1, b1, w2, b2, w3, b3, wpack, stream);
+  MPX_SA_SHAPES(CALL)
 #undef CALL
+  mpx_set_error("mpx_sa (bf16x3): unsupported MLP (C=%d, %d, %d, %d)", C, c1, c2, c3);
+  return 1;
 }

@@ -59,23 +59,31 @@ def demangle_head(sym):
     return f"{name}<{', '.join(vals)}>"
 
 
+def code_objects(so_path, tmp):
+    """-> paths of the gfx950 code objects of ``so_path`` (one per translation unit), unbundled into directory ``tmp``."""
+    paths = []
+    fb = os.path.join(tmp, "fatbin")
+    subprocess.run([_tool("llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", so_path, os.path.join(tmp, "so")],
+                   check=True, capture_output=True)
+    data = open(fb, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), data)]
+    assert starts and starts[0] == 0, "no offload bundle at the start of .hip_fatbin"
+    for i, s in enumerate(starts):
+        e = starts[i + 1] if i + 1 < len(starts) else len(data)
+        bpath, cpath = os.path.join(tmp, f"b{i}"), os.path.join(tmp, f"b{i}.co")
+        with open(bpath, "wb") as f:
+            f.write(data[s:e])
+        subprocess.run([_tool("clang-offload-bundler"), "--type=o", "--unbundle", f"--targets={TARGET}",
+                        f"--input={bpath}", f"--output={cpath}"], check=True, capture_output=True)
+        paths.append(cpath)
+    return paths
+
+
 def kernel_metadata(so_path):
     """-> {mangled kernel name: {metadata field: value string}} over every gfx950 code object in ``so_path``."""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        fb = os.path.join(tmp, "fatbin")
-        subprocess.run([_tool("llvm-objcopy"), "--dump-section", f".hip_fatbin={fb}", so_path, os.path.join(tmp, "so")],
-                       check=True, capture_output=True)
-        data = open(fb, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), data)]
-        assert starts and starts[0] == 0, "no offload bundle at the start of .hip_fatbin"
-        for i, s in enumerate(starts):
-            e = starts[i + 1] if i + 1 < len(starts) else len(data)
-            bpath, cpath = os.path.join(tmp, f"b{i}"), os.path.join(tmp, f"b{i}.co")
-            with open(bpath, "wb") as f:
-                f.write(data[s:e])
-            subprocess.run([_tool("clang-offload-bundler"), "--type=o", "--unbundle", f"--targets={TARGET}",
-                            f"--input={bpath}", f"--output={cpath}"], check=True, capture_output=True)
+        for cpath in code_objects(so_path, tmp):
             notes = subprocess.run([_tool("llvm-readelf"), "--notes", cpath], check=True, capture_output=True,
                                    text=True).stdout
             # amdhsa.kernels is a YAML list: an entry starts at "  - .<key>", its scalar fields sit at 4 spaces

@@ -65,15 +65,15 @@ CASES = [
 ]
 
 # ---- constants of the C launchers (each one: where it is defined) -----------------------------------------------------
-MPX_SA1_Q = 32                          # csrc/sa_mlp.hip:38  (#define MPX_SA1_Q)
-MPX_SA2_Q = 8                           # csrc/sa_mlp.hip:41  (#define MPX_SA2_Q)
-SA1_QS = 4                              # csrc/sa_mlp.hip:827 (QS = CF == 1 ? 4 : 2) -- SA1's small-batch queries per wave
-SA2_QS = (2, 1)                         # csrc/sa_mlp.hip:932-934 (mpx_sa_mlp_factored: 2 at nq >= 1024, else 1)
-SA1_SLOTS_PER_CU = 16                   # csrc/sa_mlp.hip:835 (sa_wave_slots(CF == 1 ? 16 : 8))
-SA2_SLOTS_PER_CU = 8                    # csrc/sa_mlp.hip:917 (sa_wave_slots(8))
+MPX_SA1_Q = 32                          # csrc/sa_mlp.hip:34  (constexpr int SA1_Q)
+MPX_SA2_Q = 8                           # csrc/sa_mlp.hip:34  (constexpr int SA2_Q)
+SA1_QS = 4                              # csrc/sa_mlp.hip:784 (QS = CF == 1 ? 4 : 2) -- SA1's small-batch queries per wave
+SA2_QS = (2, 1)                         # csrc/sa_mlp.hip:858-860 (mpx_sa_mlp_factored: 2 at nq >= 1024, else 1)
+SA1_SLOTS_PER_CU = 16                   # csrc/sa_mlp.hip:789 (sa_plan<Q>(..., CF == 1 ? 16 : 8, ...): wave slots per CU)
+SA2_SLOTS_PER_CU = 8                    # csrc/sa_mlp.hip:853 (sa_plan<Q>(..., 8, ...))
 SA3_CHAIN_MIN_BATCH = 256               # csrc/policy.hip:137, model.py:39
-BF16_SA1_Q, BF16_RES_WV = 16, 4         # csrc/sa_mlp_bf16.hip:1376 (Q), :532 (res::WV) -- the weight-resident SA1 kernel
-BF16_SA2_Q = 8                          # csrc/sa_mlp_bf16.hip:816 (v2::Q) -- the persistent SA2 kernel
+BF16_SA1_Q, BF16_RES_WV = 16, 4         # csrc/sa_mlp_bf16.hip:1276 (Q), :486 (res::WV) -- the weight-resident SA1 kernel
+BF16_SA2_Q = 8                          # csrc/sa_mlp_bf16.hip:770 (v2::Q) -- the persistent SA2 kernel
 PAIRS_BM = 256                          # csrc/dense_bf16.hip:253 (Y_BM)
 
 
