@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340: mpx_pool_wgrad / mpx_pool_wgrad_scratch / mpx_pool_dgrad, mpx_linear_segmax / mpx_linear_segmax_bf16x3, mpx_pack_rows_ld / mpx_pack_rows_grad_ld (additions only);
+int mpx_version(void); /* 340 (unchanged: an addition, no caller of an earlier 340 library needs rebuilding): mpx_franka_ik, struct mpx_ik_options;
+                          340: mpx_pool_wgrad / mpx_pool_wgrad_scratch / mpx_pool_dgrad, mpx_linear_segmax / mpx_linear_segmax_bf16x3, mpx_pack_rows_ld / mpx_pack_rows_grad_ld (additions only);
                           330: mpx_sa3_front_bf16x3 / _pack / _pack_size / _w3_pairs (additions), the measurement hooks mpx_sa3_chain_probe / mpx_sa2_bf16x3_set_probe /
                           mpx_sa3_front_bf16x3_probe declared, mpx_sa_mlp_bf16x3_factored refuses nsample > 128;
                           320: mpx_linear_dact, mpx_segment_max_grad_act, mpx_linear_bf16x3_dact, mpx_linear_wgrad_bf16x3 (additions only); mpx_franka_collision accepts
@@ -129,6 +130,50 @@ int mpx_trajectory_metrics(const float *traj, const int32_t *lengths, const floa
                            const float *limits, int B, int T, float finger, float *pos_err_cm,
                            float *orient_err_deg, float *path_pos, float *path_orient_deg,
                            int32_t *limit_violation, int32_t *self_collision, mpx_stream_t stream);
+
+/* Batched collision-free inverse kinematics (robofin FrankaRobot.ik / FrankaRealRobot.collision_free_ik, called by the
+ * reference's problem generators: data_pipeline/environments/tabletop_environment.py:395, cubby_environment.py:546,
+ * dresser_environment.py:496).  Damped least squares with restarts: one wave per problem, MPX_IK_SEEDS = 64 starts, one
+ * per lane.  Start 0 is row b of q_init (NULL: the neutral pose), clamped into the limits; starts 1..63 are uniform in
+ * the limits, drawn from Philox keyed by (seed, GLOBAL problem id = env_offset + b, start), so a shard of a larger
+ * batch computes what one process computes.  Every start runs `iterations` steps
+ *   dq = J^T (J J^T + lambda^2 I)^-1 [p_t - p ; rotvec(R_t R^T)],  dq scaled to max |dq_j| <= step_clip,  q clamped to limits
+ * and CONVERGED means: the right_gripper frame that mpx_franka_fk computes for the final q is within pos_tol [m] and
+ * rot_tol [rad] of the target (angle = atan2(|vee(E - E^T)| / 2, (trace E - 1) / 2), E = R_t R^T; tested in float32 as
+ * error <= tol * MPX_IK_ACCEPT_SHARE (- MPX_IK_ACCEPT_ANGLE_MARGIN for the angle), so that a caller who re-checks the
+ * frame in other arithmetic finds it inside the tolerances as stated).  Converged starts are then tested in start order against the problem's primitives
+ * (min(cuboid_sdf, cylinder_sdf)(sphere centre) <= sph_radii[s] + clearance is a hit: with clearance 0 the test of
+ * mpx_franka_collision) and, with check_self, against the self-collision model of mpx_trajectory_metrics; the result is
+ * the LOWEST start that converged and has no hit.
+ *   target_poses [B,4,4] row-major (right_gripper), limits [7,2], sphere table as for mpx_franka_collision (S <= 64,
+ *   S = 0 with M1 = M2 = 0: no environment test), cub_* [B,M1,..] / cyl_* [B,M2,..] as for mpx_franka_collision
+ *   (M1, M2 <= 64; zero-volume rows are skipped).
+ *   q_out [B,7]; status int32 [B]: 0 solved, 1 some start converged but every converged start has a hit, 2 no start
+ *   converged; rows with status != 0 are NaN.
+ *   all_q [B,64,7] (optional): every start's final q, converged or not.  all_status int32 [B,64] (optional): bit 0
+ *   converged, bit 1 environment hit, bit 2 self hit; when it is passed EVERY converged start is tested (otherwise the
+ *   sweep stops at the first free one); q_out and status do not depend on it.                                        */
+#define MPX_IK_SEEDS 64
+#define MPX_IK_DEFAULT_ITERATIONS 64
+#define MPX_IK_DEFAULT_LAMBDA 0.05f
+#define MPX_IK_DEFAULT_STEP_CLIP 0.5f
+#define MPX_IK_DEFAULT_POS_TOL 1e-3f          /* 1 mm */
+#define MPX_IK_DEFAULT_ROT_TOL 8.7266463e-3f  /* 0.5 degrees */
+#define MPX_IK_ACCEPT_SHARE 0.9999f
+#define MPX_IK_ACCEPT_ANGLE_MARGIN 2e-6f
+typedef struct mpx_ik_options { /* NULL options: the defaults above, clearance 0, check_self 0 */
+  int iterations;               /* >= 1, the same for every start (no early exit)  */
+  float lambda, step_clip;      /* damping (> 0) and the largest joint step [rad]  */
+  float pos_tol, rot_tol;       /* acceptance: metres, radians                    */
+  float clearance;              /* added to every sphere radius in the environment test */
+  int check_self;               /* non-zero: also reject self collisions          */
+} mpx_ik_options;
+int mpx_franka_ik(const float *target_poses, int B, float finger, const float *limits, const float *q_init,
+                  const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                  const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                  const float *cyl_radii, const float *cyl_heights, int M2, const mpx_ik_options *options,
+                  uint64_t seed, int64_t env_offset, float *q_out, int32_t *status, float *all_q,
+                  int32_t *all_status, mpx_stream_t stream);
 
 /* ---- split-bf16 ("bf16x3") dense layers: the opt-in fast mode of mpx_linear / mpx_linear_rowmax ------
  * Every fp32 product is evaluated as x_hi*w_hi + x_hi*w_lo + x_lo*w_hi on the bf16 matrix cores (fp32

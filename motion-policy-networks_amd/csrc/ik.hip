@@ -1,0 +1,314 @@
+// ik.hip -- batched collision-free inverse kinematics of the Franka Panda.
+//
+// Replaces (reference call sites; the implementation is robofin's ikfast wrapper + a PyBullet test per draw):
+//   FrankaRealRobot.collision_free_ik(sim, arm, selfcc, pose, retries=1000)
+//                                data_pipeline/environments/tabletop_environment.py:395,
+//                                cubby_environment.py:546, dresser_environment.py:496
+//   FrankaRobot.ik / FrankaRealRobot.ik (robofin)
+//
+// Damped least squares with restarts.  One wave per problem, one lane per restart ("seed"), everything a lane iterates on
+// in registers, one instruction stream: the iteration count is an argument and there is no early exit, so the 64 lanes
+// never diverge.  Per iteration: FK (franka_fk_visit, keeping the seven joint origins, their z axes and right_gripper),
+// e = [p_t - p ; rotvec(R_t R^T)], the geometric Jacobian J[:, j] = [z_j x (p - o_j) ; z_j],
+// dq = J^T (J J^T + lambda^2 I)^-1 e through an unrolled 6x6 Cholesky (positive definite for lambda > 0: no pivoting),
+// the step scaled so that max |dq_j| <= step_clip, q clamped into the limits.
+// A lane is ACCEPTED when one more FK of its final q -- the code mpx_franka_fk runs -- is within pos_tol / rot_tol of the
+// target.  Accepted lanes are then visited in lane order and the WAVE tests one candidate together: lane = collision
+// sphere against the problem's live primitives (compacted into LDS once, sdf_device.h forms, `sdf <= radius + clearance`
+// is a hit: with clearance 0 exactly mpx_franka_collision's test), then the body-cylinder self test of
+// trajectory_metrics_kernel (franka.hip).  The first candidate without a hit is the result: "the lowest seed that
+// converges and is free".
+#include "common.h"
+#include "sdf_device.h"
+#include "philox.h"
+
+enum { STREAM_IK = 13 };
+constexpr int IK_FRAME_FLOATS = MPX_NUM_FRAMES * 12;
+
+// rotvec of E = A B^T (row-major 3x3 each): w = sin(theta) axis from the antisymmetric part, theta = atan2(|w|, cos).
+// Returns theta.  (|w| -> 0 with cos < 0, a half turn about an unknown axis, yields a zero vector: such a lane moves on
+// its position error and leaves the half turn within a step.)
+__device__ __forceinline__ float ik_rotvec(const float *a, const float *b, float (&w)[3]) {
+  float E[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      E[3 * i + k] = mpx_fma(a[3 * i + 2], b[3 * k + 2], mpx_fma(a[3 * i + 1], b[3 * k + 1], a[3 * i] * b[3 * k]));
+  w[0] = 0.5f * (E[7] - E[5]);
+  w[1] = 0.5f * (E[2] - E[6]);
+  w[2] = 0.5f * (E[3] - E[1]);
+  const float c = 0.5f * ((E[0] + E[4] + E[8]) - 1.0f);
+  const float s = sqrtf(mpx_fma(w[2], w[2], mpx_fma(w[1], w[1], w[0] * w[0])));
+  const float theta = atan2f(s, c);
+  const float k = s > 1e-7f ? theta / s : 1.0f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] *= k;
+  return theta;
+}
+
+__global__ void __launch_bounds__(64)
+    franka_ik_kernel(const float *__restrict__ targets, float finger, const float *__restrict__ limits,
+                     const float *__restrict__ q_init, const float *__restrict__ sc, const float *__restrict__ sr,
+                     const int32_t *__restrict__ sl, int S, const float *__restrict__ cub_f,
+                     const float *__restrict__ cub_d, int M1, const float *__restrict__ cyl_f,
+                     const float *__restrict__ cyl_r, const float *__restrict__ cyl_h, int M2, mpx_ik_options opt,
+                     uint32_t seed_lo, uint32_t seed_hi, uint32_t env0, float *__restrict__ q_out,
+                     int32_t *__restrict__ status, float *__restrict__ all_q, int32_t *__restrict__ all_status) {
+  __shared__ __attribute__((aligned(16))) float prim_rows[128 * 16];  // live cuboids from row 0, live cylinders from row 64
+  __shared__ float frames[IK_FRAME_FLOATS];                           // the candidate under test
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float *tg = targets + (size_t)b * 16;  // (wave-uniform: scalar loads)
+  const float Rt[9] = {tg[0], tg[1], tg[2], tg[4], tg[5], tg[6], tg[8], tg[9], tg[10]};
+  const float pt[3] = {tg[3], tg[7], tg[11]};
+  float lo[7], hi[7], q[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
+
+  // ---- starts: lane 0 from the caller (or the neutral pose), the others uniform in the limits -----------------------------
+  {
+    const float neutral[7] = {0.00f, -1.3f, 0.00f, -2.87f, 0.00f, 2.00f, 0.75f};  // franka_tables.DEFAULT_Q
+    const Philox r0 = philox4x32(2u * (uint32_t)lane, env0 + (uint32_t)b, STREAM_IK, 0u, seed_lo, seed_hi);
+    const Philox r1 = philox4x32(2u * (uint32_t)lane + 1u, env0 + (uint32_t)b, STREAM_IK, 0u, seed_lo, seed_hi);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      const float u = u01(j < 4 ? r0.c[j] : r1.c[j - 4]);
+      const float drawn = lo[j] + u * (hi[j] - lo[j]);
+      const float given = q_init ? q_init[(size_t)b * 7 + j] : neutral[j];
+      q[j] = fminf(fmaxf(lane == 0 ? given : drawn, lo[j]), hi[j]);
+    }
+  }
+
+  // ---- damped least squares ----------------------------------------------------------------------------------------------
+  const float lam2 = opt.lambda * opt.lambda;
+  for (int it = 0; it < opt.iterations; ++it) {
+    float o[7][3], z[7][3];
+    Rigid eff;
+    franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
+      constexpr int id = decltype(ID)::value;
+      if constexpr (id >= 1 && id <= 7) {
+        o[id - 1][0] = g.t[0], o[id - 1][1] = g.t[1], o[id - 1][2] = g.t[2];
+        z[id - 1][0] = g.r[2], z[id - 1][1] = g.r[5], z[id - 1][2] = g.r[8];
+      }
+      if constexpr (id == 14) eff = g;
+    });
+    float e[6];
+    {
+      float w[3];
+      ik_rotvec(Rt, eff.r, w);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) e[i] = pt[i] - eff.t[i], e[3 + i] = w[i];
+    }
+    float J[6][7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      const float dx = eff.t[0] - o[j][0], dy = eff.t[1] - o[j][1], dz = eff.t[2] - o[j][2];
+      J[0][j] = mpx_fma(z[j][1], dz, -(z[j][2] * dy));
+      J[1][j] = mpx_fma(z[j][2], dx, -(z[j][0] * dz));
+      J[2][j] = mpx_fma(z[j][0], dy, -(z[j][1] * dx));
+      J[3][j] = z[j][0], J[4][j] = z[j][1], J[5][j] = z[j][2];
+    }
+    // A = J J^T + lambda^2 I = L L^T (lower triangle in place), then L y' = e, L^T y = y'
+    float L[6][6], inv[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int k = 0; k <= i; ++k) {
+        float acc = i == k ? lam2 : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) acc = mpx_fma(J[i][j], J[k][j], acc);
+        L[i][k] = acc;
+      }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      float d = L[k][k];
+#pragma unroll
+      for (int m = 0; m < k; ++m) d = mpx_fma(-L[k][m], L[k][m], d);
+      const float root = sqrtf(d);
+      inv[k] = 1.0f / root;
+      L[k][k] = root;
+#pragma unroll
+      for (int i = k + 1; i < 6; ++i) {
+        float v = L[i][k];
+#pragma unroll
+        for (int m = 0; m < k; ++m) v = mpx_fma(-L[i][m], L[k][m], v);
+        L[i][k] = v * inv[k];
+      }
+    }
+    float y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      float v = e[i];
+#pragma unroll
+      for (int m = 0; m < i; ++m) v = mpx_fma(-L[i][m], y[m], v);
+      y[i] = v * inv[i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+      float v = y[i];
+#pragma unroll
+      for (int m = i + 1; m < 6; ++m) v = mpx_fma(-L[m][i], y[m], v);
+      y[i] = v * inv[i];
+    }
+    float dq[7], big = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      float v = 0.0f;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) v = mpx_fma(J[i][j], y[i], v);
+      dq[j] = v;
+      big = fmaxf(big, __builtin_fabsf(v));
+    }
+    const float scale = big > opt.step_clip ? opt.step_clip / big : 1.0f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) q[j] = fminf(fmaxf(q[j] + dq[j] * scale, lo[j]), hi[j]);
+  }
+
+  // ---- acceptance: one more FK of the final q (the chain mpx_franka_fk evaluates) ------------------------------------------
+  bool conv;
+  {
+    Rigid eff;
+    franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
+      if constexpr (decltype(ID)::value == 14) eff = g;
+    });
+    const float dx = pt[0] - eff.t[0], dy = pt[1] - eff.t[1], dz = pt[2] - eff.t[2];
+    const float perr = sqrtf(mpx_fma(dz, dz, mpx_fma(dy, dy, dx * dx)));
+    float w[3];
+    const float theta = ik_rotvec(Rt, eff.r, w);
+    // (the margins -- 1e-4 relative, 2e-6 rad: tens of times the float32 rounding of perr and theta -- make the
+    // acceptance hold for a caller who re-checks the SAME frame in other arithmetic, e.g. float64)
+    conv = perr <= opt.pos_tol * MPX_IK_ACCEPT_SHARE && theta <= opt.rot_tol * MPX_IK_ACCEPT_SHARE - MPX_IK_ACCEPT_ANGLE_MARGIN;
+  }
+
+  // ---- live primitives, compacted into LDS rows [R | Rt (3 x 4 floats) | sizes] ---------------------------------------------
+  const float *cf = cub_f + (size_t)b * M1 * 16;
+  const float *cd = cub_d + (size_t)b * M1 * 3;
+  const float *yf = cyl_f + (size_t)b * M2 * 16;
+  const float *yr = cyl_r + (size_t)b * M2;
+  const float *yh = cyl_h + (size_t)b * M2;
+  bool clive = false, ylive = false;
+  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, r0 = 0.0f, h0 = 0.0f;
+  if (lane < M1) {
+    c0 = cd[3 * lane + 0], c1 = cd[3 * lane + 1], c2 = cd[3 * lane + 2];
+    clive = !(mpx_is_zero(c0) || mpx_is_zero(c1) || mpx_is_zero(c2));
+  }
+  if (lane < M2) {
+    r0 = yr[lane], h0 = yh[lane];
+    ylive = !(mpx_is_zero(r0) || mpx_is_zero(h0));
+  }
+  const unsigned long long cmask = __builtin_amdgcn_ballot_w64(clive), ymask = __builtin_amdgcn_ballot_w64(ylive);
+  const int n_cub = __builtin_popcountll(cmask), n_cyl = __builtin_popcountll(ymask);
+  const unsigned long long below = ((unsigned long long)1 << lane) - 1;
+  if (clive) {
+    float *dst = prim_rows + 16 * __builtin_popcountll(cmask & below);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dst[k] = cf[16 * lane + k];
+    dst[12] = c0, dst[13] = c1, dst[14] = c2;
+  }
+  if (ylive) {
+    float *dst = prim_rows + 16 * (64 + __builtin_popcountll(ymask & below));
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dst[k] = yf[16 * lane + k];
+    dst[12] = r0, dst[13] = h0;
+  }
+  __syncthreads();
+
+  // ---- candidates in lane order: the wave tests one at a time, lane = collision sphere ----------------------------------------
+  const unsigned long long accepted = __builtin_amdgcn_ballot_w64(conv);
+  const bool test_env = S > 0 && n_cub + n_cyl > 0, test_self = opt.check_self != 0;
+  const bool test_all = all_status != nullptr;  // every seed's bits are wanted: no stop at the first free one
+  int winner = -1;
+  bool my_env = false, my_self = false;
+  if (!test_env && !test_self) {
+    winner = accepted ? (int)__builtin_ctzll(accepted) : -1;
+  } else {
+    unsigned long long todo = accepted;
+    while (todo) {
+      const int c = (int)__builtin_ctzll(todo);  // (wave-uniform)
+      todo &= todo - 1;
+      if (lane == c) franka_fk_frames(q, finger, frames);
+      __syncthreads();
+      bool hit = false;
+      if (test_env && lane < S) {
+        float x, y, zz;
+        rigid_apply(frames + 12 * sl[lane], sc[3 * lane + 0], sc[3 * lane + 1], sc[3 * lane + 2], x, y, zz);
+        float best = __builtin_inff();
+        for (int m = 0; m < n_cub; ++m) {
+          const float *row = prim_rows + 16 * m;
+          best = fminf(best, cuboid_sdf_live(row, row[12], row[13], row[14], x, y, zz));
+        }
+        for (int m = 0; m < n_cyl; ++m) {
+          const float *row = prim_rows + 16 * (64 + m);
+          best = fminf(best, cylinder_sdf_live(row, row[12], row[13], x, y, zz));
+        }
+        hit = best <= sr[lane] + opt.clearance;
+      }
+      bool self = false;
+      if (test_self && lane < 4) {  // trajectory_metrics_kernel's model: link7 / hand / fingertips against the base segment
+        const int link = lane == 0 ? 7 : lane == 1 ? 9 : lane == 2 ? 12 : 13;
+        const float radius = lane == 0 ? 0.1f : 0.01f;
+        const float *p = frames + 12 * link + 9;
+        const float zc = fminf(fmaxf(p[2], -0.3f), 0.333f);
+        const float dz = p[2] - zc;
+        const float d = sqrtf(mpx_fma(dz, dz, mpx_fma(p[1], p[1], p[0] * p[0])));
+        self = d < 0.15f + radius;
+      }
+      const bool any_env = __any(hit), any_self = __any(self);
+      if (lane == c) my_env = any_env, my_self = any_self;
+      __syncthreads();  // (the next candidate overwrites `frames`)
+      if (!any_env && !any_self && winner < 0) {
+        winner = c;
+        if (!test_all) break;
+      }
+    }
+  }
+
+  // ---- results ----------------------------------------------------------------------------------------------------------------
+  if (all_q) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j) all_q[((size_t)b * 64 + lane) * 7 + j] = q[j];
+  }
+  if (all_status) all_status[(size_t)b * 64 + lane] = (conv ? 1 : 0) | (my_env ? 2 : 0) | (my_self ? 4 : 0);
+  if (winner >= 0) {
+    if (lane == winner) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j) q_out[(size_t)b * 7 + j] = q[j];
+    }
+  } else if (lane < 7) {
+    q_out[(size_t)b * 7 + lane] = __builtin_nanf("");
+  }
+  if (lane == 0) status[b] = winner >= 0 ? 0 : accepted ? 1 : 2;
+}
+
+MPX_EXPORT int mpx_franka_ik(const float *target_poses, int B, float finger, const float *limits, const float *q_init,
+                             const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                             const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                             const float *cyl_radii, const float *cyl_heights, int M2, const mpx_ik_options *options,
+                             uint64_t seed, int64_t env_offset, float *q_out, int32_t *status, float *all_q,
+                             int32_t *all_status, mpx_stream_t stream) {
+  mpx_ik_options opt = {MPX_IK_DEFAULT_ITERATIONS, MPX_IK_DEFAULT_LAMBDA, MPX_IK_DEFAULT_STEP_CLIP, MPX_IK_DEFAULT_POS_TOL,
+                        MPX_IK_DEFAULT_ROT_TOL, 0.0f, 0};
+  if (options) opt = *options;
+  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "mpx_franka_ik: negative size");
+  MPX_REQUIRE(S <= MPX_IK_SEEDS, "mpx_franka_ik: S = %d collision spheres, at most %d (one lane each)", S, MPX_IK_SEEDS);
+  MPX_REQUIRE(M1 <= 64 && M2 <= 64, "mpx_franka_ik: at most 64 cuboids and 64 cylinders per problem (%d, %d)", M1, M2);
+  MPX_REQUIRE(opt.iterations >= 1, "mpx_franka_ik: iterations = %d, need >= 1", opt.iterations);
+  MPX_REQUIRE(opt.lambda > 0.0f, "mpx_franka_ik: lambda must be > 0 (the 6x6 solve has no pivoting)");
+  MPX_REQUIRE(opt.step_clip > 0.0f, "mpx_franka_ik: step_clip must be > 0");
+  MPX_REQUIRE(opt.pos_tol >= 0.0f && opt.rot_tol >= 0.0f, "mpx_franka_ik: negative tolerance");
+  MPX_REQUIRE(opt.clearance == opt.clearance, "mpx_franka_ik: clearance is NaN");
+  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "mpx_franka_ik: env_offset + B exceeds 2^32");
+  if (B == 0) return 0;
+  MPX_REQUIRE(q_out && status, "mpx_franka_ik: NULL output (q_out, status)");
+  MPX_REQUIRE(target_poses && limits, "mpx_franka_ik: NULL operand (target_poses, limits)");
+  MPX_REQUIRE(M1 == 0 || (cub_inv_frames && cub_dims), "mpx_franka_ik: M1 > 0 without cuboid arrays");
+  MPX_REQUIRE(M2 == 0 || (cyl_inv_frames && cyl_radii && cyl_heights), "mpx_franka_ik: M2 > 0 without cylinder arrays");
+  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_ik: S > 0 without the sphere table");
+  MPX_REQUIRE(M1 + M2 == 0 || S > 0, "mpx_franka_ik: primitives without collision spheres to test them with");
+  hipLaunchKernelGGL(franka_ik_kernel, dim3((unsigned)B), dim3(64), 0, mpx_s(stream), target_poses, finger, limits, q_init,
+                     sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii,
+                     cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, q_out, status,
+                     all_q, all_status);
+  MPX_LAUNCH_CHECK("mpx_franka_ik");
+}

@@ -35,6 +35,7 @@ PROTOTYPES = {
     "mpx_joint_step": [P, P, P, I, P, P, P, P],
     "mpx_franka_success": [P, P, I, F, F, F, P, P, P, P, P],
     "mpx_trajectory_metrics": [P, P, P, P, I, I, F, P, P, P, P, P, P, P],
+    "mpx_franka_ik": [P, I, F, P, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P],
     "mpx_collision_hinge": [P, L, I, I, I, P, P, I, P, P, P, I, F, P, P, L, I, P],
     "mpx_point_match": [P, P, I, I, F, F, P, P, P],
     "mpx_franka_cloud_grad": [P, I, F, P, P, P, I, P, L, I, P, P],
@@ -111,6 +112,13 @@ PROTOTYPES = {
 }
 RESTYPES = {"mpx_last_error": c_char_p, "mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
             "mpx_linear_wgrad_scratch": c_int64, "mpx_pool_wgrad_scratch": c_int64, "mpx_linear_workspace": c_int64, "mpx_policy_workspace": c_int64, "mpx_rollout_workspace": c_int64}
+
+
+class IkOptions(ctypes.Structure):
+    """``mpx_ik_options`` (include/mpinets_hip.h); the defaults are the header's MPX_IK_DEFAULT_*."""
+    _fields_ = [("iterations", c_int), ("lambda_", c_float), ("step_clip", c_float), ("pos_tol", c_float),
+                ("rot_tol", c_float), ("clearance", c_float), ("check_self", c_int)]
+
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -56,6 +56,18 @@ JOINT_LIMITS_PUBLISHED = np.array(
     dtype=np.float64,
 )
 
+def limits_float32_inward(limits) -> np.ndarray:
+    """[7,2] joint limits as float32 that never lie OUTSIDE the float64 ones: where the nearest float32 of a lower limit
+    is below it (or of an upper limit above it) the next float32 toward the interval is taken.  A configuration clamped
+    to these in float32 arithmetic satisfies the limits as given (``FrankaRobot.within_limits``)."""
+    lim = np.asarray(limits, dtype=np.float64)
+    f = lim.astype(np.float32)
+    lo, hi = f[:, 0], f[:, 1]
+    lo = np.where(lo.astype(np.float64) < lim[:, 0], np.nextafter(lo, np.float32(np.inf)), lo)
+    hi = np.where(hi.astype(np.float64) > lim[:, 1], np.nextafter(hi, np.float32(-np.inf)), hi)
+    return np.stack([lo, hi], axis=1).astype(np.float32)
+
+
 # /root/reference/config/franka_robot_description.yaml:44-46
 DEFAULT_Q = np.array([0.00, -1.3, 0.00, -2.87, 0.00, 2.00, 0.75], dtype=np.float64)
 # /root/reference/config/franka_robot_description.yaml:51-53

@@ -11,6 +11,7 @@ repo's (``franka_tables.py``) -- see that file for what is [EXT-RECALL] and what
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
@@ -57,6 +58,29 @@ class FrankaRobot:
         m[:3, 3] = frames[9:]
         return _SE3Lite(m)
 
+    @classmethod
+    def ik(cls, pose, q_init=None, seed: int = 0, device: Union[str, torch.device] = "cuda:0", **options):
+        """One right_gripper pose (4x4, or an SE3-like with ``.matrix``) -> a numpy ``[7]`` inside ``cls.JOINT_LIMITS``
+        that reaches it, or ``None`` (robofin's ``ik`` returns a list of solutions; ``franka_ik(..., return_all=True)``
+        gives every start's result)."""
+        return cls.collision_free_ik(pose, None, None, q_init=q_init, seed=seed, device=device,
+                                     **{"check_self": False, **options})
+
+    @classmethod
+    def collision_free_ik(cls, pose, cuboids=None, cylinders=None, q_init=None, seed: int = 0,
+                          device: Union[str, torch.device] = "cuda:0", **options):
+        """robofin's ``collision_free_ik(sim, arm, selfcc, pose, retries)`` for one pose: the lowest of 64 starts that
+        reaches ``pose`` and is free of ``cuboids`` / ``cylinders`` (``geometry.TorchCuboids`` / ``TorchCylinders`` with a
+        batch of one, standing in for the PyBullet ``sim`` / ``arm``) and of the self-collision model (``selfcc``:
+        ``check_self=True`` here whether or not primitives are passed; ``check_self=False`` turns it off).  The result
+        satisfies ``cls.within_limits``.  Returns a numpy ``[7]`` or ``None``."""
+        m = np.asarray(getattr(pose, "matrix", pose), dtype=np.float32).reshape(1, 4, 4)
+        dev = torch.device(device)
+        qi = None if q_init is None else torch.as_tensor(np.asarray(q_init, dtype=np.float32)).reshape(1, 7).to(dev)
+        q, status = franka_ik(torch.from_numpy(m).to(dev), cuboids, cylinders, q_init=qi, limits=cls.JOINT_LIMITS,
+                              seed=seed, **{"check_self": True, **options})
+        return q[0].cpu().numpy().astype(np.float64) if int(status[0]) == 0 else None
+
 
 class FrankaRealRobot(FrankaRobot):
     JOINT_LIMITS = ft.JOINT_LIMITS_REAL
@@ -70,6 +94,83 @@ def franka_fk(q: torch.Tensor, finger: float = ft.FINGER_OPENING) -> torch.Tenso
     out = torch.empty((q.size(0), ft.NUM_FRAMES, 12), dtype=torch.float32, device=q.device)
     _lib.call("mpx_franka_fk", _lib.ptr(qc), q.size(0), float(finger), _lib.ptr(out))
     return out
+
+
+IK_SEEDS = 64  # MPX_IK_SEEDS: starts per problem, one per lane
+IK_SOLVED, IK_IN_COLLISION, IK_NOT_CONVERGED = 0, 1, 2  # status values of ``franka_ik``
+IK_BIT_CONVERGED, IK_BIT_ENV_HIT, IK_BIT_SELF_HIT = 1, 2, 4  # per-start bits of ``return_all``
+IK_DEFAULTS = dict(iterations=64, damping=0.05, step_clip=0.5, pos_tol=1e-3, rot_tol=float(np.radians(0.5)),
+                   clearance=0.0)
+_ik_tables: dict = {}
+
+
+def _ik_sphere_table(device: torch.device, with_base_link: bool):
+    key = (device, bool(with_base_link))
+    if key not in _ik_tables:
+        c, r, l, _ = ft.collision_sphere_table(with_base_link)
+        _ik_tables[key] = tuple(torch.from_numpy(a).to(device) for a in (c, r, l))
+    return _ik_tables[key]
+
+
+def franka_ik(target_poses: torch.Tensor, cuboids=None, cylinders=None, q_init: Optional[torch.Tensor] = None,
+              limits=ft.JOINT_LIMITS_REAL, seed: int = 0, env_offset: int = 0, with_base_link: bool = False,
+              return_all: bool = False, finger: float = ft.FINGER_OPENING, **options):
+    """Batched collision-free inverse kinematics on the GPU (csrc/ik.hip: damped least squares, 64 starts per pose).
+
+    :param target_poses: [B,4,4] right_gripper poses
+    :param cuboids, cylinders: ``geometry.TorchCuboids`` / ``TorchCylinders`` (batch B) or None, as for
+        ``FrankaCollisionSampler.check``
+    :param limits: [7,2]; cast to float32 toward the inside of the interval, so every returned joint satisfies them as given
+    :param q_init: [B,7] first start of every problem (default: the neutral pose); the other 63 are uniform in ``limits``,
+        drawn from Philox keyed by (``seed``, ``env_offset`` + row, start)
+    :param options: ``iterations`` (64), ``damping`` (0.05; the C struct's ``lambda``), ``step_clip`` (0.5 rad), ``pos_tol``
+        (1e-3 m), ``rot_tol`` (radians; 0.5 degrees), ``clearance`` (0 m), ``check_self`` (default: on when primitives are
+        passed, off in free space)
+    :returns: ``q`` [B,7] (NaN rows where ``status`` != 0) and ``status`` int32 [B]: 0 solved, 1 every converged start
+        collides, 2 nothing converged; with ``return_all`` also ``all_q`` [B,64,7] and ``all_status`` int32 [B,64] (bit 0
+        converged, bit 1 environment hit, bit 2 self hit)."""
+    _lib.require_cuda(target_poses, q_init)
+    assert target_poses.ndim == 3 and target_poses.shape[1:] == (4, 4)
+    B, dev = target_poses.size(0), target_poses.device
+    tp = _lib.f32c(target_poses)
+    # float32 limits rounded INWARD: a joint left on a limit by the kernel's clamp is inside the limits as passed
+    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
+    assert lim.shape == (7, 2)
+    qi = None
+    if q_init is not None:
+        assert q_init.shape == (B, 7)
+        qi = _lib.f32c(q_init)
+    opts = dict(IK_DEFAULTS, check_self=cuboids is not None or cylinders is not None)
+    if "lambda" in options:
+        options["damping"] = options.pop("lambda")
+    unknown = set(options) - set(opts)
+    if unknown:
+        raise TypeError(f"franka_ik: unknown option(s) {sorted(unknown)}")
+    opts.update(options)
+    copt = _lib.IkOptions(int(opts["iterations"]), float(opts["damping"]), float(opts["step_clip"]), float(opts["pos_tol"]),
+                          float(opts["rot_tol"]), float(opts["clearance"]), int(bool(opts["check_self"])))
+    cf = cd = yf = yr = yh = sc = sr = sl = None
+    M1 = M2 = S = 0
+    if cuboids is not None:
+        assert cuboids.centers.size(0) == B
+        M1 = cuboids.centers.size(1)
+        cf, cd = cuboids.inv_frames, _lib.f32c(cuboids.dims)
+    if cylinders is not None:
+        assert cylinders.centers.size(0) == B
+        M2 = cylinders.centers.size(1)
+        yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
+    if M1 + M2 > 0:
+        sc, sr, sl = _ik_sphere_table(dev, with_base_link)
+        S = int(sc.size(0))
+    q = torch.empty((B, 7), dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    all_q = torch.empty((B, IK_SEEDS, 7), dtype=torch.float32, device=dev) if return_all else None
+    all_status = torch.empty((B, IK_SEEDS), dtype=torch.int32, device=dev) if return_all else None
+    _lib.call("mpx_franka_ik", _lib.ptr(tp), B, float(finger), _lib.ptr(lim), _lib.ptr(qi), _lib.ptr(sc), _lib.ptr(sr),
+              _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
+              ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(q), _lib.ptr(status),
+              _lib.ptr(all_q), _lib.ptr(all_status))
+    return (q, status, all_q, all_status) if return_all else (q, status)
 
 
 def frames_to_matrix(frames: torch.Tensor) -> torch.Tensor:

@@ -237,9 +237,44 @@ def linear_trajectories(B: int, T: int, seed: int = 0) -> np.ndarray:
     return (a[:, None] * (1 - s) + b[:, None] * s).astype(np.float32)
 
 
+def _collision_free_problems(prims: Dict[str, torch.Tensor], q_draw: torch.Tensor, q_target: torch.Tensor, seed: int,
+                             env_offset: int, max_redraws: int):
+    """``make_problem_batch(collision_free=True)``: -> start q, the configuration whose FK is the goal pose, the goal's
+    collision-free solution and the ``valid`` mask.  Every draw is keyed by (seed, attempt, GLOBAL row), so a shard
+    gets the rows one process would get."""
+    from .geometry import TorchCuboids, TorchCylinders
+    from .robot import franka_fk, franka_ik, frames_to_matrix
+
+    B, dev = q_draw.size(0), q_draw.device
+    cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
+    cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
+                         prims["cylinder_quats"])
+
+    def pose(qq):
+        return frames_to_matrix(franka_fk(qq)[:, ft.LINK_ID["right_gripper"]])
+
+    q_start, q_goal, q_pose = q_draw.clone(), torch.full_like(q_target, float("nan")), q_target.clone()
+    valid = torch.zeros(B, dtype=torch.bool, device=dev)
+    # (every attempt solves all B rows, not only the still invalid ones: the draws are keyed by the global row, a launch
+    # over 8192 problems takes 1.4 ms, and a gather would have to carry the row ids into the kernel)
+    for a in range(max_redraws + 1):
+        s_a = seed + 7919 * a
+        src_start = q_draw if a == 0 else torch.from_numpy(random_configurations(env_offset + B, s_a)[env_offset:]).to(dev)
+        src_goal = q_target if a == 0 else torch.from_numpy(random_configurations(env_offset + B, s_a + 7)[env_offset:]).to(dev)
+        qs, ss = franka_ik(pose(src_start), cub, cyl, seed=s_a, env_offset=env_offset)
+        qg, sg = franka_ik(pose(src_goal), cub, cyl, seed=s_a + 7, env_offset=env_offset)
+        ok = (ss == 0) & (sg == 0) & ~valid
+        q_start[ok], q_goal[ok], q_pose[ok] = qs[ok], qg[ok], src_goal[ok]
+        valid |= ok
+        if B == 0 or bool(valid.all()):
+            break
+    return q_start, q_pose, q_goal, valid
+
+
 def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop",), M1: int = 16, M2: int = 16,
                        scene_pool: Optional[int] = None, device_clouds: bool = False, env_offset: int = 0,
-                       total_envs: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                       total_envs: Optional[int] = None, collision_free: bool = False,
+                       max_redraws: int = 4) -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -248,7 +283,14 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     Sharding: the batch is rows ``[env_offset, env_offset + B)`` of a GLOBAL batch of ``total_envs`` problems
     (default ``env_offset + B``) that depends on ``seed`` only -- every rank passes the same seed and its own offset
     and gets exactly the rows one process would generate (scenes, configurations, targets and, with
-    ``device_clouds``, the scene clouds, whose draws are keyed by the global environment id)."""
+    ``device_clouds``, the scene clouds, whose draws are keyed by the global environment id).
+
+    ``collision_free`` (default off: start and goal are plain uniform draws, tested against nothing): the problem the
+    reference's generators pose.  The goal is the drawn pose SOLVED against the scene by ``robot.franka_ik`` (``q_goal``),
+    the start is ``franka_ik`` of a second drawn pose; a problem whose start or goal has no collision-free solution is
+    redrawn, up to ``max_redraws`` times, each time from fresh draws and the next Philox stream.  ``valid`` (bool [B])
+    marks the problems that ended with both; the others keep their unchecked first draws as start and target pose, and
+    their ``q_goal`` row is NaN."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     dev = torch.device(device)
@@ -263,6 +305,9 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     q = torch.from_numpy(random_configurations(env_offset + B, seed)[env_offset:]).to(dev)
     q_target = torch.from_numpy(random_configurations(env_offset + B, seed + 7)[env_offset:]).to(dev)
     lim = torch.as_tensor(ft.JOINT_LIMITS_REAL, dtype=torch.float32, device=dev)
+    if collision_free:
+        q, q_target, q_goal, valid = _collision_free_problems(out, q, q_target, seed, env_offset, max_redraws)
+        out.update(q_goal=q_goal, valid=valid)
     state = np.random.get_state()
     np.random.seed(seed)
     sampler = FrankaSampler(dev)
