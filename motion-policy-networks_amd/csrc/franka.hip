@@ -555,12 +555,21 @@ MPX_EXPORT int mpx_franka_success(const float *q, const float *target_poses, int
 // (config/franka_fabric_config.yaml:120-140: body cylinder (0,0,-0.3)-(0,0,0.333) r 0.15 vs spheres on
 // link7 (r 0.1), hand and finger tips (r 0.01)); the reference Evaluator asks PyBullet meshes instead.
 // `lengths` (optional) = number of valid waypoints per trajectory (>= 1); later rows are ignored.
-__device__ __forceinline__ float rot_angle_deg(const float *a, const float *b) {  // angle of A B^T, row-major 3x3
+// Angle of E = A B^T (row-major 3x3 each) in degrees: sine from the antisymmetric part of E, cosine from its trace,
+// angle = atan2(sine, cosine) -- the form of ik_rotvec (ik.hip).  Well conditioned at every angle; acos of the trace alone
+// turns the few-ulp error of a float32 trace into percents of the small angle between two consecutive waypoints (always
+// upward: up to 10 degrees over a 2000-waypoint path) and loses half the digits near 180 degrees.
+__device__ __forceinline__ float rot_angle_deg(const float *a, const float *b) {
+  auto e = [&](int i, int k) __attribute__((always_inline)) {
+    return mpx_fma(a[3 * i + 2], b[3 * k + 2], mpx_fma(a[3 * i + 1], b[3 * k + 1], a[3 * i] * b[3 * k]));
+  };
+  const float w0 = 0.5f * (e(2, 1) - e(1, 2)), w1 = 0.5f * (e(0, 2) - e(2, 0)), w2 = 0.5f * (e(1, 0) - e(0, 1));
   float tr = 0.0f;
 #pragma unroll
   for (int i = 0; i < 9; ++i) tr = mpx_fma(a[i], b[i], tr);
-  const float c = fminf(fmaxf((tr - 1.0f) * 0.5f, -1.0f), 1.0f);
-  return acosf(c) * 57.29577951308232f;
+  const float c = (tr - 1.0f) * 0.5f;
+  const float s = sqrtf(mpx_fma(w2, w2, mpx_fma(w1, w1, w0 * w0)));
+  return atan2f(s, c) * 57.29577951308232f;
 }
 
 __global__ void __launch_bounds__(64)

@@ -7,10 +7,14 @@ under the reference's names:
 
 =================================  ==============================================================
 ``position_error`` [cm]            ``check_final_position`` (metrics.py:338-347)
-``orientation_error`` [deg]        ``check_final_orientation`` (metrics.py:349-361)
+``orientation_error`` [deg]        ``check_final_orientation`` (metrics.py:349-361); the angle of R_eff R_t^T as
+                                   atan2(|antisymmetric part|, (trace - 1) / 2): good to ~1e-5 deg at every angle
+                                   (acos of the float32 trace is not, near 0 and 180 deg)
 ``eff_position_path_length`` [m]   ``calculate_eff_path_lengths`` (metrics.py:410-434)
-``eff_orientation_path_length``    same, degrees
-``joint_limit_violation``          ``violates_joint_limits`` (metrics.py:311-322), published limits
+``eff_orientation_path_length``    same, degrees: the sum of the same angle between consecutive waypoints
+``joint_limit_violation``          ``violates_joint_limits`` (metrics.py:311-322), published limits; the float32
+                                   limits handed to the kernel are rounded INWARD, so the flag is the float64
+                                   comparison of the float32 waypoint with the limits as published
 ``collision``                      swept-sphere SDF check of ``model.py:293-314`` -- NOT PyBullet/Lula
 ``self_collision``                 body-cylinder vs end-link spheres of ``config/franka_fabric_config.yaml``
                                    -- NOT PyBullet
@@ -60,7 +64,8 @@ class BatchedEvaluator:
     def __init__(self, device, finger: float = ft.FINGER_OPENING):
         self.device = torch.device(device)
         self.finger = float(finger)
-        self.limits = torch.as_tensor(ft.JOINT_LIMITS_PUBLISHED, dtype=torch.float32, device=self.device).contiguous()
+        # (float32 limits that never lie outside the float64 ones: a waypoint the kernel passes satisfies the limits as given)
+        self.limits = torch.as_tensor(ft.limits_float32_inward(ft.JOINT_LIMITS_PUBLISHED), device=self.device).contiguous()
         self.collision_sampler = FrankaCollisionSampler(self.device, with_base_link=False, finger=finger)
 
     @torch.no_grad()

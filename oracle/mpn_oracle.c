@@ -695,11 +695,21 @@ ORC_API void orc_success(const float *eff_frames, const float *targets, int B, f
  * is the engine's sphere-vs-body-cylinder model from config/franka_fabric_config.yaml:120-140
  * (the reference asks PyBullet): PARITY UNPINNED for that flag.
  * ---------------------------------------------------------------------------------------- */
+/* angle of E = A B^T: sine from the antisymmetric part of E, cosine from its trace, atan2 (franka.hip rot_angle_deg;
+ * held to float64 by tests/float64_metrics.py, which this mirror cannot do) */
+static float orc_dot_row(const float *a, const float *b, int i, int k) {
+  return fmaf(a[3 * i + 2], b[3 * k + 2], fmaf(a[3 * i + 1], b[3 * k + 1], a[3 * i] * b[3 * k]));
+}
+
 static float orc_rot_angle_deg(const float *a, const float *b) {
+  float w0 = 0.5f * (orc_dot_row(a, b, 2, 1) - orc_dot_row(a, b, 1, 2));
+  float w1 = 0.5f * (orc_dot_row(a, b, 0, 2) - orc_dot_row(a, b, 2, 0));
+  float w2 = 0.5f * (orc_dot_row(a, b, 1, 0) - orc_dot_row(a, b, 0, 1));
   float tr = 0.0f;
   for (int i = 0; i < 9; ++i) tr = fmaf(a[i], b[i], tr);
-  float c = fminf(fmaxf((tr - 1.0f) * 0.5f, -1.0f), 1.0f);
-  return acosf(c) * 57.29577951308232f;
+  float c = (tr - 1.0f) * 0.5f;
+  float s = sqrtf(fmaf(w2, w2, fmaf(w1, w1, w0 * w0)));
+  return atan2f(s, c) * 57.29577951308232f;
 }
 
 ORC_API void orc_trajectory_metrics(const float *traj, const int32_t *lengths, const float *targets,

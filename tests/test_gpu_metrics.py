@@ -1,7 +1,13 @@
 """Row N3: batched trajectory metrics vs the oracle (and vs hand-checkable cases)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import float64_metrics as fm  # noqa: E402  (the bars: 4x the float32-vs-float64 difference of the restatement)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,13 +38,16 @@ def test_trajectory_metrics_match_oracle(oracle):
     ev = BatchedEvaluator(dev())
     got = ev.evaluate_trajectories(tt, targets, torch.from_numpy(lengths).to(dev()), cub, cyl)
     ref = oracle.trajectory_metrics(traj, lengths, targets.cpu().numpy(), ft.JOINT_LIMITS_PUBLISHED)
-    for k, tol in (("position_error", 1e-3), ("orientation_error", 2e-2), ("eff_position_path_length", 1e-4),
-                   ("eff_orientation_path_length", 0.2)):
-        np.testing.assert_allclose(got[k].cpu().numpy(), ref[k], rtol=1e-4, atol=tol, err_msg=k)
+    # orientation: kernel and mirror are each within one bar of float64 (tests/test_gpu_metrics_float64.py holds the
+    # kernel there), so within two bars of each other -- 1.4e-4 and 9.3e-4 deg where acos of the trace needed 2e-2 and 0.2
+    for k, rtol, tol in (("position_error", 1e-4, 1e-3), ("orientation_error", 0, 2 * fm.BARS["traj_orientation_error"]),
+                         ("eff_position_path_length", 1e-4, 1e-4),
+                         ("eff_orientation_path_length", 0, 2 * fm.BARS["traj_eff_orientation_path_length"][150])):
+        np.testing.assert_allclose(got[k].cpu().numpy(), ref[k], rtol=rtol, atol=tol, err_msg=k)
     np.testing.assert_array_equal(got["joint_limit_violation"].cpu().numpy(), ref["joint_limit_violation"])
     np.testing.assert_array_equal(got["self_collision"].cpu().numpy(), ref["self_collision"])
     assert bool(got["joint_limit_violation"][1]) == (lengths[1] > 10)
-    assert got["position_error"][3] < 1e-3 and got["orientation_error"][3] < 0.1
+    assert got["position_error"][3] < 1e-3 and got["orientation_error"][3] < 1e-3
     assert got["eff_position_path_length"][2] == 0  # a single waypoint has no path
     # collision flag = the fused swept-sphere check on the valid part of each trajectory
     frozen = traj.copy()
@@ -160,9 +169,13 @@ def test_batched_evaluator_matches_the_reference_evaluator(metrics_golden):
                                    dt=float(g["dt"]))
     c = lambda k: got[k].cpu().numpy()
     np.testing.assert_allclose(c("position_error"), g["m_position_error"], rtol=0, atol=2e-3)
-    np.testing.assert_allclose(c("orientation_error"), g["m_orientation_error"], rtol=0, atol=6e-2)
+    # degrees: the kernel's bar against float64 (40 waypoints: the bar of T = 50) + what the float32 FK behind the recorded
+    # results allows (float64_metrics.GOLDEN_ATOL) -- 9.8e-5 and 2.8e-4 deg where acos of the trace needed 6e-2 and 5e-2
+    np.testing.assert_allclose(c("orientation_error"), g["m_orientation_error"], rtol=0,
+                               atol=fm.BARS["traj_orientation_error"] + fm.GOLDEN_ATOL["orientation_error"])
     np.testing.assert_allclose(c("eff_position_path_length"), g["m_eff_position_path_length"], rtol=1e-5, atol=1e-5)
-    np.testing.assert_allclose(c("eff_orientation_path_length"), g["m_eff_orientation_path_length"], rtol=1e-4, atol=5e-2)
+    np.testing.assert_allclose(c("eff_orientation_path_length"), g["m_eff_orientation_path_length"], rtol=0,
+                               atol=fm.BARS["traj_eff_orientation_path_length"][50] + fm.GOLDEN_ATOL["eff_orientation_path_length"])
     np.testing.assert_array_equal(c("joint_limit_violation"), g["m_joint_limit_violation"].astype(bool))
     # the negative volume around the final position of environments 0, 3, 6, 9 contains the TARGET only for 6 (which ends
     # on its target): the reference's evaluate_trajectory drops such volumes first (metrics.py:507-512); check_final_region
