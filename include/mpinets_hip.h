@@ -29,7 +29,7 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: an addition, no caller of an earlier 340 library needs rebuilding): mpx_franka_ik, struct mpx_ik_options;
+int mpx_version(void); /* 340 (unchanged: an addition, no caller of an earlier 340 library needs rebuilding): mpx_franka_ik, struct mpx_ik_options, mpx_franka_plan, struct mpx_plan_options;
                           340: mpx_pool_wgrad / mpx_pool_wgrad_scratch / mpx_pool_dgrad, mpx_linear_segmax / mpx_linear_segmax_bf16x3, mpx_pack_rows_ld / mpx_pack_rows_grad_ld (additions only);
                           330: mpx_sa3_front_bf16x3 / _pack / _pack_size / _w3_pairs (additions), the measurement hooks mpx_sa3_chain_probe / mpx_sa2_bf16x3_set_probe /
                           mpx_sa3_front_bf16x3_probe declared, mpx_sa_mlp_bf16x3_factored refuses nsample > 128;
@@ -174,6 +174,71 @@ int mpx_franka_ik(const float *target_poses, int B, float finger, const float *l
                   const float *cyl_radii, const float *cyl_heights, int M2, const mpx_ik_options *options,
                   uint64_t seed, int64_t env_offset, float *q_out, int32_t *status, float *all_q,
                   int32_t *all_status, mpx_stream_t stream);
+
+/* Batched collision-free trajectory planning between two configurations (what the reference's data generator asks of OMPL
+ * AIT* + Geometric Fabrics and then filters with verify_trajectory, data_pipeline/gen_data.py:106-153, 396-430).  This is a
+ * LOCAL optimiser, not AIT*: covariant gradient descent (CHOMP form) on a T-waypoint joint-space trajectory with fixed
+ * endpoints, K = options->candidates candidates per problem; one workgroup per problem, one wave per candidate, one lane
+ * per waypoint.  A returned trajectory is valid by THIS library's sphere model (mpx_franka_collision's spheres against
+ * the primitives, mpx_trajectory_metrics' self test), not by PyBullet's meshes.
+ *   Candidates.  L_t = q_start + s_t (q_goal - q_start), s_t = t / (T-1).  Candidate 0 is L; candidate k >= 1 is
+ *   L_t + sin(pi s_t) delta_k, delta_k[j] = spread (2u - 1) (hi_j - lo_j) / 2, clamped into the limits.  u = u01 of word
+ *   j (j < 4) of Philox4x32-10(counter = {2k, GLOBAL problem id = env_offset + b, stream 14, 0}, key = seed) or word j - 4
+ *   of the block with counter word 0 = 2k + 1: a shard of a larger batch computes what one process computes.  Waypoints 0
+ *   and T-1 are never touched: they come back bit-equal to q_start / q_goal.
+ *   One iteration, for every interior waypoint t = 1..n (n = T-2), all from the trajectory of the previous iteration:
+ *     x_s = the sphere centre mpx_franka_spheres computes; d_s = min over live primitives of sdf(x_s) - r_s - clearance;
+ *     c'(d) = -1 (d < 0), (d - epsilon) / epsilon (0 <= d < epsilon), 0 otherwise; n_s = gradient at x_s of the arg-min
+ *     primitive's SDF (ties: lowest index, cuboids before cylinders; the derivative of the function mpx_cuboid_sdf /
+ *     mpx_cylinder_sdf evaluate, pulled to the world by the transpose of the stored inverse frame's 3x3);
+ *     g_t[j] = sum_s c'(d_s) n_s . (z_j x (x_s - o_j)) over the revolute joints j upstream of the sphere's link;
+ *     q_t <- clamp(q_t - step (smooth_weight (q_t - L_t) + sum_u M[t,u] g_u), lo, hi),
+ *     M[t,u] = min(t,u) (n + 1 - max(t,u)) / (n + 1): the inverse of the fixed-endpoint velocity-smoothness metric A
+ *     (tridiagonal 2, -1), for which A^-1 grad(smoothness) = q - L.
+ *   Every candidate runs `iterations` steps (0: the candidates as drawn), no early exit.
+ *   Validity.  Every segment is split into `substeps` pieces: refined configuration r = t substeps + i is
+ *   fma((float)i / (float)substeps, q_{t+1} - q_t, q_t) in float32 (i = 0: q_t itself), r = 0 .. (T-1) substeps.  A
+ *   candidate is INVALID if a refined configuration has a sphere with sdf <= r_s + clearance + check_margin (bit 0 of
+ *   all_status), or, with check_self, a self-test sphere closer than 0.15 + radius + check_margin to the base segment
+ *   (mpx_trajectory_metrics' model; bit 1), or if a third difference ((q3-q2)-(q2-q1)) - ((q2-q1)-(q1-q0)) of its T
+ *   waypoints exceeds max_jerk * 0.9999 in absolute value (gen_data.py:82, 327-344; bit 2).  check_margin makes a caller
+ *   who interpolates and judges in other arithmetic agree (an ulp of q moves a sphere by ~1e-7 m).
+ *   The result is the LOWEST valid candidate.  status int32 [B]: 0 solved; 1 no valid candidate; 2 an endpoint is not
+ *   finite, outside the limits or itself invalid by the tests above (no planning is done).  traj rows with status != 0
+ *   are NaN; choice (optional int32 [B]) is the candidate taken or -1; all_traj [B,K,T,7] / all_status int32 [B,K]
+ *   (optional) hold every candidate's final trajectory and bits (status 2: all_traj NaN, all_status 7).
+ *   q_start, q_goal [B,7]; limits [7,2]; sphere table and primitives exactly as for mpx_franka_ik (S <= 64,
+ *   M1, M2 <= 64, zero-volume rows skipped, S = 0 with M1 = M2 = 0: no environment term); 2 <= T <= MPX_PLAN_MAX_T.    */
+#define MPX_PLAN_MAX_T 64
+#define MPX_PLAN_MAX_CANDIDATES 16
+#define MPX_PLAN_DEFAULT_CANDIDATES 8
+#define MPX_PLAN_DEFAULT_ITERATIONS 20
+#define MPX_PLAN_DEFAULT_STEP 2e-4f
+#define MPX_PLAN_DEFAULT_SMOOTH_WEIGHT 20.0f
+#define MPX_PLAN_DEFAULT_EPSILON 0.05f
+#define MPX_PLAN_DEFAULT_SPREAD 0.5f
+#define MPX_PLAN_DEFAULT_SUBSTEPS 4
+#define MPX_PLAN_DEFAULT_CHECK_MARGIN 1e-4f
+#define MPX_PLAN_DEFAULT_MAX_JERK 0.15f
+#define MPX_PLAN_JERK_SHARE 0.9999f
+typedef struct mpx_plan_options { /* NULL options: the defaults above, clearance 0, check_self 1 */
+  int candidates;                 /* 1 .. MPX_PLAN_MAX_CANDIDATES                                  */
+  int iterations;                 /* >= 0, the same for every candidate (no early exit)            */
+  float step, smooth_weight;      /* step > 0; smooth_weight >= 0 pulls toward the straight line   */
+  float epsilon;                  /* > 0: width [m] of the band in which an obstacle repels         */
+  float spread;                   /* candidates >= 1: amplitude, as a share of the half joint range */
+  int substeps;                   /* >= 1: pieces per segment in the validity sweep                */
+  float check_margin;             /* >= 0 [m], added to the radii in the validity sweep only       */
+  float clearance;                /* [m], added to the radii in the cost AND the validity sweep    */
+  float max_jerk;                 /* largest third difference [rad]                                */
+  int check_self;                 /* non-zero: self collisions invalidate a candidate              */
+} mpx_plan_options;
+int mpx_franka_plan(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                    const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                    const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                    const float *cyl_radii, const float *cyl_heights, int M2, const mpx_plan_options *options,
+                    uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *choice, float *all_traj,
+                    int32_t *all_status, mpx_stream_t stream);
 
 /* ---- split-bf16 ("bf16x3") dense layers: the opt-in fast mode of mpx_linear / mpx_linear_rowmax ------
  * Every fp32 product is evaluated as x_hi*w_hi + x_hi*w_lo + x_lo*w_hi on the bf16 matrix cores (fp32

@@ -7,7 +7,7 @@
 //
 // All three reduce per environment inside one workgroup in a fixed order (no atomics: results
 // are run-to-run identical); the mean over the batch is left to the caller ([B] partial sums).
-#include "sdf_device.h"
+#include "sdf_grad_device.h"
 
 
 
@@ -31,35 +31,6 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float *lds /* >= NV * 
 #pragma unroll
   for (int i = 0; i < NV; ++i) v[i] = lds[i];
   __syncthreads();
-}
-
-__device__ __forceinline__ float sgn(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
-
-// gradient of the 2-norm-of-positive-parts + clamped-max "box" distance w.r.t. d (n = 2 or 3);
-// mirrors autograd of geometry.py:276-284 (norm has zero gradient at the origin; max picks the first index)
-template <int ND>
-__device__ __forceinline__ void box_grad(const float (&d)[ND], float (&g)[ND]) {
-  float n2 = 0.0f;
-#pragma unroll
-  for (int i = 0; i < ND; ++i) {
-    float m = fmaxf(d[i], 0.0f);
-    n2 = mpx_fma(m, m, n2);
-  }
-  const float outside = sqrtf(n2);
-  int arg = 0;
-  float mx = d[0];
-#pragma unroll
-  for (int i = 1; i < ND; ++i)
-    if (d[i] > mx) {
-      mx = d[i];
-      arg = i;
-    }
-#pragma unroll
-  for (int i = 0; i < ND; ++i) {
-    float gi = (outside > 0.0f && d[i] > 0.0f) ? d[i] / outside : 0.0f;
-    if (mx < 0.0f && i == arg) gi += 1.0f;
-    g[i] = gi;
-  }
 }
 
 // ---- collision hinge ---------------------------------------------------------------------------------

@@ -1,0 +1,367 @@
+// plan.hip -- batched collision-free trajectory planning of the Franka Panda between two configurations.
+//
+// Stands where the reference's data generator calls OMPL's AIT* and Geometric Fabrics and then filters with
+// verify_trajectory (data_pipeline/gen_data.py:106-153, 396-430).  It is NOT that planner: it is a local optimiser,
+// covariant gradient descent (CHOMP form) from K starting trajectories, and "valid" means valid by this library's sphere
+// model.  The contract (candidates, one iteration, validity, the choice) is stated in include/mpinets_hip.h.
+//
+// One workgroup per problem, one wave per candidate, lane = waypoint (T <= 64).  FK, the sphere loop and the gradient of
+// a waypoint stay in the lane's registers: franka_fk_visit hands over each frame as it exists, the lane then walks the
+// sphere table (wave-uniform: scalar loads) for the spheres of that link, tests them against the problem's live primitives
+// (compacted into LDS once per workgroup, as ik.hip does) and adds c'(d) n . (z_j x (x - o_j)) for the joints upstream.
+// g goes to LDS once per iteration for the M g product (n x 7 FMAs per lane, M in LDS, broadcast reads of g).
+// The validity sweep reuses the mapping with lane = refined configuration, in passes of 64.
+#include "common.h"
+#include "sdf_grad_device.h"
+#include "philox.h"
+
+enum { STREAM_PLAN = 14 };
+enum { PLAN_BIT_ENV = 1, PLAN_BIT_SELF = 2, PLAN_BIT_JERK = 4 };
+
+// the centre of a table sphere on a frame held in registers: rigid_apply's operations in rigid_apply's order
+__device__ __forceinline__ void plan_apply(const Rigid &g, float x, float y, float z, float &ox, float &oy, float &oz) {
+  ox = mpx_fma(g.r[2], z, mpx_fma(g.r[1], y, g.r[0] * x)) + g.t[0];
+  oy = mpx_fma(g.r[5], z, mpx_fma(g.r[4], y, g.r[3] * x)) + g.t[1];
+  oz = mpx_fma(g.r[8], z, mpx_fma(g.r[7], y, g.r[6] * x)) + g.t[2];
+}
+
+// min over the live primitives (LDS rows [R | Rt (3 x 4 floats) | sizes]; cuboids from row 0, cylinders from row 64) and
+// the row that attains it: the first minimum, cuboids before cylinders (-1: no live primitive)
+__device__ __forceinline__ float plan_min_sdf(const float *prim_rows, int n_cub, int n_cyl, float x, float y, float z,
+                                              int &arg) {
+  float best = __builtin_inff();
+  arg = -1;
+  for (int m = 0; m < n_cub; ++m) {
+    const float *row = prim_rows + 16 * m;
+    const float v = cuboid_sdf_live(row, row[12], row[13], row[14], x, y, z);
+    if (v < best) best = v, arg = m;
+  }
+  for (int m = 0; m < n_cyl; ++m) {
+    const float *row = prim_rows + 16 * (64 + m);
+    const float v = cylinder_sdf_live(row, row[12], row[13], x, y, z);
+    if (v < best) best = v, arg = 64 + m;
+  }
+  return best;
+}
+
+// bits PLAN_BIT_ENV / PLAN_BIT_SELF of one configuration
+__device__ __forceinline__ int plan_config_bits(const float *q, float finger, const float *__restrict__ sc,
+                                                const float *__restrict__ sr, const int32_t *__restrict__ sl, int S,
+                                                const float *prim_rows, int n_cub, int n_cyl, float reach, bool test_self,
+                                                float self_margin) {
+  int bits = 0;
+  const bool test_env = S > 0 && n_cub + n_cyl > 0;
+  franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
+    constexpr int id = decltype(ID)::value;
+    if (test_env) {
+      for (int s = 0; s < S; ++s) {
+        if (sl[s] != id) continue;  // (wave-uniform)
+        float x, y, z;
+        plan_apply(g, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, z);
+        int arg;
+        const float best = plan_min_sdf(prim_rows, n_cub, n_cyl, x, y, z, arg);
+        if (best <= sr[s] + reach) bits |= PLAN_BIT_ENV;
+      }
+    }
+    if constexpr (id == 7 || id == 9 || id == 12 || id == 13) {  // trajectory_metrics_kernel's self model
+      if (test_self) {
+        const float radius = id == 7 ? 0.1f : 0.01f;
+        const float zc = fminf(fmaxf(g.t[2], -0.3f), 0.333f);
+        const float dz = g.t[2] - zc;
+        const float d = sqrtf(mpx_fma(dz, dz, mpx_fma(g.t[1], g.t[1], g.t[0] * g.t[0])));
+        if (d < 0.15f + radius + self_margin) bits |= PLAN_BIT_SELF;
+      }
+    }
+  });
+  return bits;
+}
+
+// MAXK: the most candidates a launch may carry.  Up to 8 waves per workgroup leave a wave 256 VGPRs (no spills); 16
+// leave it 128, where the seven joint frames no longer fit and a few values go to scratch.
+template <int MAXK>
+__global__ void __launch_bounds__(64 * MAXK)
+    franka_plan_kernel(const float *__restrict__ q_start, const float *__restrict__ q_goal, int T, float finger,
+                       const float *__restrict__ limits, const float *__restrict__ sc, const float *__restrict__ sr,
+                       const int32_t *__restrict__ sl, int S, const float *__restrict__ cub_f,
+                       const float *__restrict__ cub_d, int M1, const float *__restrict__ cyl_f,
+                       const float *__restrict__ cyl_r, const float *__restrict__ cyl_h, int M2, mpx_plan_options opt,
+                       uint32_t seed_lo, uint32_t seed_hi, uint32_t env0, float *__restrict__ traj,
+                       int32_t *__restrict__ status, int32_t *__restrict__ choice, float *__restrict__ all_traj,
+                       int32_t *__restrict__ all_status) {
+  // LDS: [128 primitive rows x 16 | M: T x T | per candidate: 64 waypoints x 7 (g, then the trajectory) | K bits]
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float *prim_rows = lds;
+  float *Mtab = lds + 128 * 16;
+  const int K = opt.candidates;
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // candidate of this wave
+  float *buf = Mtab + T * T + k * 64 * 7;
+  int *cand_bits = reinterpret_cast<int *>(Mtab + T * T + K * 64 * 7);
+  const int n = T - 2;
+  const int t = lane < T ? lane : T - 1;  // (lanes past the trajectory repeat the goal and never store)
+
+  float lo[7], hi[7], qs[7], qg[7];
+  bool bad_end = false;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
+    qs[j] = q_start[(size_t)b * 7 + j], qg[j] = q_goal[(size_t)b * 7 + j];
+    bad_end |= !(qs[j] >= lo[j] && qs[j] <= hi[j]) || !(qg[j] >= lo[j] && qg[j] <= hi[j]);  // (NaN fails both)
+  }
+
+  // ---- live primitives, compacted into LDS rows [R | Rt (3 x 4 floats) | sizes] (wave 0) ------------------------------------
+  const float *cf = cub_f + (size_t)b * M1 * 16;
+  const float *cd = cub_d + (size_t)b * M1 * 3;
+  const float *yf = cyl_f + (size_t)b * M2 * 16;
+  const float *yr = cyl_r + (size_t)b * M2;
+  const float *yh = cyl_h + (size_t)b * M2;
+  bool clive = false, ylive = false;
+  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, r0 = 0.0f, h0 = 0.0f;
+  if (lane < M1) {
+    c0 = cd[3 * lane + 0], c1 = cd[3 * lane + 1], c2 = cd[3 * lane + 2];
+    clive = !(mpx_is_zero(c0) || mpx_is_zero(c1) || mpx_is_zero(c2));
+  }
+  if (lane < M2) {
+    r0 = yr[lane], h0 = yh[lane];
+    ylive = !(mpx_is_zero(r0) || mpx_is_zero(h0));
+  }
+  const unsigned long long cmask = __builtin_amdgcn_ballot_w64(clive), ymask = __builtin_amdgcn_ballot_w64(ylive);
+  const int n_cub = __builtin_popcountll(cmask), n_cyl = __builtin_popcountll(ymask);  // (every wave: the same counts)
+  const unsigned long long below = ((unsigned long long)1 << lane) - 1;
+  if (k == 0 && clive) {
+    float *dst = prim_rows + 16 * __builtin_popcountll(cmask & below);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dst[i] = cf[16 * lane + i];
+    dst[12] = c0, dst[13] = c1, dst[14] = c2;
+  }
+  if (k == 0 && ylive) {
+    float *dst = prim_rows + 16 * (64 + __builtin_popcountll(ymask & below));
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dst[i] = yf[16 * lane + i];
+    dst[12] = r0, dst[13] = h0;
+  }
+  // M[t,u] = min(t,u) (n + 1 - max(t,u)) / (n + 1): an exact integer product, one division
+  for (int i = threadIdx.x; i < T * T; i += blockDim.x) {
+    const int a = i / T, c = i - a * T;
+    const int mn = a < c ? a : c, mx = a < c ? c : a;
+    Mtab[i] = (float)(mn * (n + 1 - mx)) / (float)(n + 1);
+  }
+  __syncthreads();
+
+  const bool test_env = S > 0 && n_cub + n_cyl > 0, test_self = opt.check_self != 0;
+  const float reach = opt.clearance + opt.check_margin;
+
+  // ---- endpoints: an invalid one ends the problem (block-uniform: every wave computes the same answer) --------------------
+  if (!bad_end) {  // (the limits test is wave-uniform)
+    int e = 0;
+    if (lane < 2)
+      e = plan_config_bits(lane == 0 ? qs : qg, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self,
+                           opt.check_margin);
+    bad_end = __any(e != 0);
+  }
+  if (bad_end) {
+    const float nan = __builtin_nanf("");
+    if (k == 0) {
+      for (int i = lane; i < T * 7; i += 64) traj[(size_t)b * T * 7 + i] = nan;
+      if (lane == 0) {
+        status[b] = 2;
+        if (choice) choice[b] = -1;
+      }
+    }
+    if (all_traj)
+      for (int i = lane; i < T * 7; i += 64) all_traj[((size_t)b * K + k) * T * 7 + i] = nan;
+    if (all_status && lane == 0) all_status[(size_t)b * K + k] = PLAN_BIT_ENV | PLAN_BIT_SELF | PLAN_BIT_JERK;
+    return;
+  }
+
+  // ---- this lane's waypoint of candidate k ---------------------------------------------------------------------------------
+  float L[7], q[7];
+  {
+    const float s = (float)t / (float)(T - 1);
+    float bump, unused;
+    mpx_sincos(3.14159265358979323846f * s, bump, unused);
+    const Philox p0 = philox4x32(2u * (uint32_t)k, env0 + (uint32_t)b, STREAM_PLAN, 0u, seed_lo, seed_hi);
+    const Philox p1 = philox4x32(2u * (uint32_t)k + 1u, env0 + (uint32_t)b, STREAM_PLAN, 0u, seed_lo, seed_hi);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      const float line = mpx_fma(s, qg[j] - qs[j], qs[j]);
+      L[j] = t == 0 ? qs[j] : t == T - 1 ? qg[j] : line;
+      const float u = u01(j < 4 ? p0.c[j] : p1.c[j - 4]);
+      const float delta = (opt.spread * mpx_fma(2.0f, u, -1.0f)) * ((hi[j] - lo[j]) * 0.5f);
+      const float moved = fminf(fmaxf(mpx_fma(bump, delta, L[j]), lo[j]), hi[j]);
+      q[j] = (k == 0 || t == 0 || t == T - 1) ? L[j] : moved;
+    }
+  }
+  const bool interior = lane >= 1 && lane <= n;
+
+  // ---- covariant gradient descent ------------------------------------------------------------------------------------------
+  const float inv_eps = 1.0f / opt.epsilon;
+  for (int it = 0; it < opt.iterations; ++it) {
+    float g[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (test_env) {
+      float o[7][3], z[7][3];
+      franka_fk_visit(q, finger, [&](auto ID, const Rigid &fr) __attribute__((always_inline)) {
+        constexpr int id = decltype(ID)::value;
+        if constexpr (id >= 1 && id <= 7) {
+          o[id - 1][0] = fr.t[0], o[id - 1][1] = fr.t[1], o[id - 1][2] = fr.t[2];
+          z[id - 1][0] = fr.r[2], z[id - 1][1] = fr.r[5], z[id - 1][2] = fr.r[8];
+        }
+        if constexpr (id >= 1) {  // (link0 does not move)
+          constexpr int nj = id < 7 ? id : 7;
+          for (int s = 0; s < S; ++s) {
+            if (sl[s] != id) continue;  // (wave-uniform)
+            float x, y, zz;
+            plan_apply(fr, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, zz);
+            int arg;
+            const float best = plan_min_sdf(prim_rows, n_cub, n_cyl, x, y, zz, arg);
+            const float d = (best - sr[s]) - opt.clearance;
+            if (d < opt.epsilon) {  // (d = +inf without a live primitive)
+              const float cp = d < 0.0f ? -1.0f : (d - opt.epsilon) * inv_eps;
+              const float *row = prim_rows + 16 * arg;
+              float px, py, pz, l0, l1, l2, nx, ny, nz;
+              mpx_project(row, x, y, zz, px, py, pz);
+              if (arg < 64)
+                cuboid_sdf_grad_local(px, py, pz, row[12], row[13], row[14], l0, l1, l2);
+              else
+                cylinder_sdf_grad_local(px, py, pz, row[12], row[13], l0, l1, l2);
+              sdf_grad_to_world(row, l0, l1, l2, nx, ny, nz);
+              nx *= cp, ny *= cp, nz *= cp;
+#pragma unroll
+              for (int j = 0; j < nj; ++j) {
+                const float rx = x - o[j][0], ry = y - o[j][1], rz = zz - o[j][2];
+                const float cx = mpx_fma(z[j][1], rz, -(z[j][2] * ry));
+                const float cy = mpx_fma(z[j][2], rx, -(z[j][0] * rz));
+                const float cz = mpx_fma(z[j][0], ry, -(z[j][1] * rx));
+                g[j] += mpx_fma(nz, cz, mpx_fma(ny, cy, nx * cx));
+              }
+            }
+          }
+        }
+      });
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) buf[lane * 7 + j] = g[j];
+    // (buf belongs to this wave alone, so a wave-level barrier would do; the workgroup barrier is legal -- every wave runs
+    // the same iteration count and the bad-endpoint return is block-uniform -- and couples the candidates' progress, at
+    // two barriers per ~20 k instructions of an iteration.  The looser form is unmeasured.)
+    __syncthreads();
+    float acc[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (test_env) {
+      for (int u = 1; u <= n; ++u) {
+        const float m = Mtab[u * T + t];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) acc[j] = mpx_fma(m, buf[u * 7 + j], acc[j]);
+      }
+    }
+    if (interior) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        const float dir = mpx_fma(opt.smooth_weight, q[j] - L[j], acc[j]);
+        q[j] = fminf(fmaxf(mpx_fma(-opt.step, dir, q[j]), lo[j]), hi[j]);
+      }
+    }
+    __syncthreads();  // (the next iteration overwrites buf)
+  }
+
+  // ---- validity: jerk of the T waypoints, then the refined configurations, lane = configuration -------------------------------
+#pragma unroll
+  for (int j = 0; j < 7; ++j) buf[lane * 7 + j] = q[j];
+  __syncthreads();
+  int bits = 0;
+  if (lane + 3 < T) {
+    const float lim = opt.max_jerk * MPX_PLAN_JERK_SHARE;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      const float q0 = buf[lane * 7 + j], q1 = buf[(lane + 1) * 7 + j], q2 = buf[(lane + 2) * 7 + j],
+                  q3 = buf[(lane + 3) * 7 + j];
+      const float v0 = q1 - q0, v1 = q2 - q1, v2 = q3 - q2;
+      const float jerk = (v2 - v1) - (v1 - v0);
+      if (!(__builtin_fabsf(jerk) <= lim)) bits |= PLAN_BIT_JERK;
+    }
+  }
+  if (test_env || test_self) {
+    const int R = (T - 1) * opt.substeps + 1;
+    for (int r0_ = 0; r0_ < R; r0_ += 64) {
+      const int r = r0_ + lane;
+      if (r < R) {
+        const int seg = r / opt.substeps, i = r - seg * opt.substeps;
+        float qq[7];
+        if (i == 0) {
+#pragma unroll
+          for (int j = 0; j < 7; ++j) qq[j] = buf[seg * 7 + j];
+        } else {
+          const float f = (float)i / (float)opt.substeps;
+#pragma unroll
+          for (int j = 0; j < 7; ++j) qq[j] = mpx_fma(f, buf[(seg + 1) * 7 + j] - buf[seg * 7 + j], buf[seg * 7 + j]);
+        }
+        bits |= plan_config_bits(qq, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) bits |= __shfl_xor(bits, o);
+  if (lane == 0) cand_bits[k] = bits;
+  __syncthreads();
+
+  // ---- the lowest valid candidate ----------------------------------------------------------------------------------------------
+  int winner = -1;
+  for (int c = K - 1; c >= 0; --c)
+    if (cand_bits[c] == 0) winner = c;
+  if (all_traj && lane < T) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j) all_traj[(((size_t)b * K + k) * T + lane) * 7 + j] = q[j];
+  }
+  if (all_status && lane == 0) all_status[(size_t)b * K + k] = bits;
+  if (lane < T && (winner == k || (winner < 0 && k == 0))) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j) traj[((size_t)b * T + lane) * 7 + j] = winner < 0 ? __builtin_nanf("") : q[j];
+  }
+  if (k == 0 && lane == 0) {
+    status[b] = winner >= 0 ? 0 : 1;
+    if (choice) choice[b] = winner;
+  }
+}
+
+MPX_EXPORT int mpx_franka_plan(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                               const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                               const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                               const float *cyl_radii, const float *cyl_heights, int M2, const mpx_plan_options *options,
+                               uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *choice,
+                               float *all_traj, int32_t *all_status, mpx_stream_t stream) {
+  mpx_plan_options opt = {MPX_PLAN_DEFAULT_CANDIDATES,   MPX_PLAN_DEFAULT_ITERATIONS, MPX_PLAN_DEFAULT_STEP,
+                          MPX_PLAN_DEFAULT_SMOOTH_WEIGHT, MPX_PLAN_DEFAULT_EPSILON,    MPX_PLAN_DEFAULT_SPREAD,
+                          MPX_PLAN_DEFAULT_SUBSTEPS,      MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f,
+                          MPX_PLAN_DEFAULT_MAX_JERK,      1};
+  if (options) opt = *options;
+  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "mpx_franka_plan: negative size");
+  MPX_REQUIRE(T >= 2 && T <= MPX_PLAN_MAX_T, "mpx_franka_plan: T = %d waypoints, need 2 .. %d (one lane each)", T,
+              MPX_PLAN_MAX_T);
+  MPX_REQUIRE(opt.candidates >= 1 && opt.candidates <= MPX_PLAN_MAX_CANDIDATES,
+              "mpx_franka_plan: candidates = %d, need 1 .. %d (one wave each)", opt.candidates, MPX_PLAN_MAX_CANDIDATES);
+  MPX_REQUIRE(S <= 64, "mpx_franka_plan: S = %d collision spheres, at most 64", S);
+  MPX_REQUIRE(M1 <= 64 && M2 <= 64, "mpx_franka_plan: at most 64 cuboids and 64 cylinders per problem (%d, %d)", M1, M2);
+  MPX_REQUIRE(opt.iterations >= 0, "mpx_franka_plan: iterations = %d, need >= 0", opt.iterations);
+  MPX_REQUIRE(opt.step > 0.0f, "mpx_franka_plan: step must be > 0");
+  MPX_REQUIRE(opt.epsilon > 0.0f, "mpx_franka_plan: epsilon must be > 0");
+  MPX_REQUIRE(opt.smooth_weight >= 0.0f, "mpx_franka_plan: smooth_weight must be >= 0");
+  MPX_REQUIRE(opt.substeps >= 1 && opt.substeps <= 64, "mpx_franka_plan: substeps = %d, need 1 .. 64", opt.substeps);
+  MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "mpx_franka_plan: negative check_margin or max_jerk");
+  MPX_REQUIRE(opt.clearance == opt.clearance && opt.spread == opt.spread, "mpx_franka_plan: clearance or spread is NaN");
+  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "mpx_franka_plan: env_offset + B exceeds 2^32");
+  if (B == 0) return 0;
+  MPX_REQUIRE(traj && status, "mpx_franka_plan: NULL output (traj, status)");
+  MPX_REQUIRE(q_start && q_goal && limits, "mpx_franka_plan: NULL operand (q_start, q_goal, limits)");
+  MPX_REQUIRE(M1 == 0 || (cub_inv_frames && cub_dims), "mpx_franka_plan: M1 > 0 without cuboid arrays");
+  MPX_REQUIRE(M2 == 0 || (cyl_inv_frames && cyl_radii && cyl_heights), "mpx_franka_plan: M2 > 0 without cylinder arrays");
+  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_plan: S > 0 without the sphere table");
+  MPX_REQUIRE(M1 + M2 == 0 || S > 0, "mpx_franka_plan: primitives without collision spheres to test them with");
+  const int K = opt.candidates;
+  const size_t lds = sizeof(float) * ((size_t)128 * 16 + (size_t)T * T + (size_t)K * 64 * 7) + sizeof(int) * K;  // <= 53 312 B
+  auto kernel = K <= 8 ? franka_plan_kernel<8> : franka_plan_kernel<MPX_PLAN_MAX_CANDIDATES>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64 * K), lds, mpx_s(stream), q_start, q_goal, T, finger, limits,
+                     sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii,
+                     cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, traj, status,
+                     choice, all_traj, all_status);
+  MPX_LAUNCH_CHECK("mpx_franka_plan");
+}

@@ -36,6 +36,7 @@ PROTOTYPES = {
     "mpx_franka_success": [P, P, I, F, F, F, P, P, P, P, P],
     "mpx_trajectory_metrics": [P, P, P, P, I, I, F, P, P, P, P, P, P, P],
     "mpx_franka_ik": [P, I, F, P, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P],
+    "mpx_franka_plan": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P],
     "mpx_collision_hinge": [P, L, I, I, I, P, P, I, P, P, P, I, F, P, P, L, I, P],
     "mpx_point_match": [P, P, I, I, F, F, P, P, P],
     "mpx_franka_cloud_grad": [P, I, F, P, P, P, I, P, L, I, P, P],
@@ -118,6 +119,13 @@ class IkOptions(ctypes.Structure):
     """``mpx_ik_options`` (include/mpinets_hip.h); the defaults are the header's MPX_IK_DEFAULT_*."""
     _fields_ = [("iterations", c_int), ("lambda_", c_float), ("step_clip", c_float), ("pos_tol", c_float),
                 ("rot_tol", c_float), ("clearance", c_float), ("check_self", c_int)]
+
+
+class PlanOptions(ctypes.Structure):
+    """``mpx_plan_options`` (include/mpinets_hip.h); the defaults are the header's MPX_PLAN_DEFAULT_*."""
+    _fields_ = [("candidates", c_int), ("iterations", c_int), ("step", c_float), ("smooth_weight", c_float),
+                ("epsilon", c_float), ("spread", c_float), ("substeps", c_int), ("check_margin", c_float),
+                ("clearance", c_float), ("max_jerk", c_float), ("check_self", c_int)]
 
 
 _lib: Optional[ctypes.CDLL] = None

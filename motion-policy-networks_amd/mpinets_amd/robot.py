@@ -173,6 +173,71 @@ def franka_ik(target_poses: torch.Tensor, cuboids=None, cylinders=None, q_init: 
     return (q, status, all_q, all_status) if return_all else (q, status)
 
 
+PLAN_SOLVED, PLAN_NO_VALID_CANDIDATE, PLAN_BAD_ENDPOINT = 0, 1, 2  # status values of ``franka_plan``
+PLAN_BIT_ENV_HIT, PLAN_BIT_SELF_HIT, PLAN_BIT_JERK = 1, 2, 4  # per-candidate bits of ``return_all``
+# MPX_PLAN_DEFAULT_* (include/mpinets_hip.h; profiles/plan_timing.md holds the table behind iterations / step / smooth_weight)
+PLAN_DEFAULTS = dict(candidates=8, iterations=20, step=2e-4, smooth_weight=20.0, epsilon=0.05, spread=0.5, substeps=4,
+                     check_margin=1e-4, clearance=0.0, max_jerk=0.15, check_self=True)
+
+
+def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
+                env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                finger: float = ft.FINGER_OPENING, **options):
+    """Batched collision-free trajectories from ``q_start`` to ``q_goal`` on the GPU (csrc/plan.hip): covariant gradient
+    descent on ``T`` waypoints from ``candidates`` starting trajectories per problem (the straight line, and the line bent
+    by Philox draws keyed by (``seed``, ``env_offset`` + row, candidate)), then a validity sweep of every candidate; the
+    result is the lowest valid one.  A LOCAL optimiser, not the reference's AIT*: it can fail where a sampling planner
+    succeeds, and "valid" means free by this engine's sphere model (``FrankaCollisionSampler`` / ``BatchedEvaluator``).
+
+    :param q_start, q_goal: [B,7], inside ``limits`` and collision free (e.g. from ``franka_ik``)
+    :param cuboids, cylinders: ``geometry.TorchCuboids`` / ``TorchCylinders`` (batch B) or None, as for ``franka_ik``
+    :param limits: [7,2]; cast to float32 toward the inside of the interval, as ``franka_ik`` does
+    :param options: the fields of ``mpx_plan_options``, see ``PLAN_DEFAULTS``
+    :returns: ``traj`` [B,T,7] (NaN rows where ``status`` != 0; waypoints 0 and T-1 are bit-equal to the inputs) and
+        ``status`` int32 [B]: 0 solved, 1 no valid candidate, 2 an endpoint is non-finite, outside the limits or in
+        collision.  "In collision" is the validity sweep's own test, which adds ``check_margin`` (1e-4 m) to the sphere
+        radii AND to the self-collision distances: an endpoint that ``FrankaCollisionSampler.check`` or
+        ``mpx_trajectory_metrics`` accepts by less than that margin is refused with status 2.  With ``return_all`` also ``choice`` int32 [B], ``all_traj`` [B,K,T,7] and ``all_status`` int32 [B,K] (bit 0
+        environment hit, bit 1 self hit, bit 2 jerk)."""
+    _lib.require_cuda(q_start, q_goal)
+    assert q_start.ndim == 2 and q_start.size(1) == 7 and q_goal.shape == q_start.shape
+    B, dev = q_start.size(0), q_start.device
+    qs, qg = _lib.f32c(q_start), _lib.f32c(q_goal)
+    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
+    assert lim.shape == (7, 2)
+    unknown = set(options) - set(PLAN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"franka_plan: unknown option(s) {sorted(unknown)}")
+    o = dict(PLAN_DEFAULTS, **options)
+    copt = _lib.PlanOptions(int(o["candidates"]), int(o["iterations"]), float(o["step"]), float(o["smooth_weight"]),
+                            float(o["epsilon"]), float(o["spread"]), int(o["substeps"]), float(o["check_margin"]),
+                            float(o["clearance"]), float(o["max_jerk"]), int(bool(o["check_self"])))
+    cf = cd = yf = yr = yh = sc = sr = sl = None
+    M1 = M2 = S = 0
+    if cuboids is not None:
+        assert cuboids.centers.size(0) == B
+        M1 = cuboids.centers.size(1)
+        cf, cd = cuboids.inv_frames, _lib.f32c(cuboids.dims)
+    if cylinders is not None:
+        assert cylinders.centers.size(0) == B
+        M2 = cylinders.centers.size(1)
+        yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
+    if M1 + M2 > 0:
+        sc, sr, sl = _ik_sphere_table(dev, with_base_link)
+        S = int(sc.size(0))
+    K = max(int(o["candidates"]), 0)
+    traj = torch.empty((B, T, 7), dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    choice = torch.empty(B, dtype=torch.int32, device=dev) if return_all else None
+    all_traj = torch.empty((B, K, T, 7), dtype=torch.float32, device=dev) if return_all else None
+    all_status = torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None
+    _lib.call("mpx_franka_plan", _lib.ptr(qs), _lib.ptr(qg), B, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
+              _lib.ptr(sr), _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
+              ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(traj), _lib.ptr(status),
+              _lib.ptr(choice), _lib.ptr(all_traj), _lib.ptr(all_status))
+    return (traj, status, choice, all_traj, all_status) if return_all else (traj, status)
+
+
 def frames_to_matrix(frames: torch.Tensor) -> torch.Tensor:
     """[...,12] -> [...,4,4]."""
     m = torch.zeros(frames.shape[:-1] + (4, 4), dtype=frames.dtype, device=frames.device)

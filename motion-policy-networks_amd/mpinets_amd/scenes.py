@@ -271,10 +271,43 @@ def _collision_free_problems(prims: Dict[str, torch.Tensor], q_draw: torch.Tenso
     return q_start, q_pose, q_goal, valid
 
 
+EXPERT_LENGTH = 50  # the reference's SEQUENCE_LENGTH (data_pipeline/gen_data.py)
+
+
+def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
+                         seed: int, env_offset: int) -> Dict[str, torch.Tensor]:
+    from .geometry import TorchCuboids, TorchCylinders
+    from .robot import franka_plan
+
+    cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
+    cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
+                         prims["cylinder_quats"])
+    # (invalid rows have a NaN goal: the kernel reports status 2 and writes a NaN row for them)
+    traj, status = franka_plan(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
+    return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
+
+
+_DATASET_KEYS = {"cuboid_dims": "cuboid_dims", "cuboid_centers": "cuboid_centers", "cuboid_quats": "cuboid_quaternions",
+                 "cylinder_radii": "cylinder_radii", "cylinder_heights": "cylinder_heights",
+                 "cylinder_centers": "cylinder_centers", "cylinder_quats": "cylinder_quaternions"}
+
+
+def problems_to_dataset(prob: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
+    """The ``expert_valid`` rows of ``make_problem_batch(collision_free=True, expert=True)`` under the HDF5 key names of
+    the reference's dataset (``data.PointCloudTrajectoryDataset(mapping, "global_solutions", ...)`` reads them): float32
+    numpy arrays ``cuboid_{dims,centers,quaternions}``, ``cylinder_{radii,heights,centers,quaternions}``,
+    ``global_solutions`` [N,50,7]."""
+    assert "expert_valid" in prob, "problems_to_dataset needs make_problem_batch(collision_free=True, expert=True)"
+    keep = prob["expert_valid"]
+    out = {dst: prob[src][keep].detach().cpu().numpy().astype(np.float32) for src, dst in _DATASET_KEYS.items()}
+    out["global_solutions"] = prob["global_solutions"][keep].detach().cpu().numpy().astype(np.float32)
+    return out
+
+
 def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop",), M1: int = 16, M2: int = 16,
                        scene_pool: Optional[int] = None, device_clouds: bool = False, env_offset: int = 0,
                        total_envs: Optional[int] = None, collision_free: bool = False,
-                       max_redraws: int = 4) -> Dict[str, torch.Tensor]:
+                       max_redraws: int = 4, expert: bool = False) -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -290,8 +323,15 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     the start is ``franka_ik`` of a second drawn pose; a problem whose start or goal has no collision-free solution is
     redrawn, up to ``max_redraws`` times, each time from fresh draws and the next Philox stream.  ``valid`` (bool [B])
     marks the problems that ended with both; the others keep their unchecked first draws as start and target pose, and
-    their ``q_goal`` row is NaN."""
+    their ``q_goal`` row is NaN.
+
+    ``expert`` (with ``collision_free``): also plans a demonstration from ``q`` to ``q_goal`` with ``robot.franka_plan``
+    (a local optimiser standing in for the reference's AIT* + Geometric Fabrics; valid by this engine's sphere model):
+    ``global_solutions`` [B,50,7] and ``expert_valid`` = ``valid`` & planned (bool [B]); the other rows are NaN.  The
+    candidate draws are keyed by the global row, so shards agree."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
+
+    assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
 
     dev = torch.device(device)
     total = env_offset + B if total_envs is None else int(total_envs)
@@ -308,6 +348,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if collision_free:
         q, q_target, q_goal, valid = _collision_free_problems(out, q, q_target, seed, env_offset, max_redraws)
         out.update(q_goal=q_goal, valid=valid)
+        if expert:
+            out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset))
     state = np.random.get_state()
     np.random.seed(seed)
     sampler = FrankaSampler(dev)
