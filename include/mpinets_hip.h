@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: an addition, no caller of an earlier 340 library needs rebuilding): mpx_franka_ik, struct mpx_ik_options, mpx_franka_plan, struct mpx_plan_options;
+int mpx_version(void); /* 340 (unchanged: an addition, no caller of an earlier 340 library needs rebuilding): mpx_ball_query_set;
+                          340 (unchanged, likewise): mpx_franka_ik, struct mpx_ik_options, mpx_franka_plan, struct mpx_plan_options;
                           340: mpx_pool_wgrad / mpx_pool_wgrad_scratch / mpx_pool_dgrad, mpx_linear_segmax / mpx_linear_segmax_bf16x3, mpx_pack_rows_ld / mpx_pack_rows_grad_ld (additions only);
                           330: mpx_sa3_front_bf16x3 / _pack / _pack_size / _w3_pairs (additions), the measurement hooks mpx_sa3_chain_probe / mpx_sa2_bf16x3_set_probe /
                           mpx_sa3_front_bf16x3_probe declared, mpx_sa_mlp_bf16x3_factored refuses nsample > 128;
@@ -498,6 +499,19 @@ int mpx_ball_query(const float *new_xyz, int new_stride, const float *xyz, int s
 int mpx_ball_query_hits(const float *new_xyz, int new_stride, const float *xyz, int stride, int B,
                         int N, int npoint, float radius, int nsample, int32_t *idx, int32_t *cnt,
                         mpx_stream_t stream);
+
+/* The hit slots as a SET: cnt[b, j] is that of mpx_ball_query, and idx[b, j, 0 .. max(cnt, 1)) holds exactly the indices
+ * mpx_ball_query_hits writes there, in UNSPECIFIED order (an empty row gets its slot 0 = 0); every other slot is left
+ * untouched.  For consumers that reduce over the listed neighbours with a max and therefore consume no order: the fused
+ * grouped-MLP kernels with counts (mpx_sa_mlp / _factored / _bf16x3 / _bf16x3_factored) evaluate each listed neighbour as
+ * an independent row and max-pool, so their output is bit-identical to the ordered rows' (max(+0, -0) may be either zero,
+ * but relu(x + b3) follows and maps both to the same bits).  A query with more than nsample hits still keeps the nsample
+ * SMALLEST indices.  The bucketed search (2048 <= N <= 8192, small radius) hands out slots in arrival order and skips
+ * its per-row sort: the ORDER inside a row is not reproducible from run to run; counts, sets and consumers' outputs are.
+ * The other search kernels emit index order by construction.  cnt is required; nsample <= 256.                       */
+int mpx_ball_query_set(const float *new_xyz, int new_stride, const float *xyz, int stride, int B,
+                       int N, int npoint, float radius, int nsample, int32_t *idx, int32_t *cnt,
+                       mpx_stream_t stream);
 
 /* order[i] = query ids (0..n-1) sorted by DEcreasing number of rows they contribute to the packed
  * SA kernels, 4*ceil(clamp(cnt,1,nsample)/4) (ties in unspecified order).  scratch: int32[128]

@@ -894,6 +894,17 @@ __global__ void __launch_bounds__(256)
 // than nsample hits needs the nsample SMALLEST indices: it is redone by one wave scanning the whole cloud in index
 // order with ballot-ordered compaction (rare: a dense cluster such as the target gripper cloud).
 // Same distance arithmetic, same strict comparison, so idx and cnt are bit-identical to the brute-force kernel.
+//
+// SET (mpx_ball_query_set): the row is a SET of hits, in no particular order.  Its consumers -- the fused grouped-MLP
+// kernels given `cnt` -- evaluate every listed neighbour as a row of its own (the same k-order of every dot product
+// whatever tile row it lands in) and reduce with a max, and a max over a set does not depend on the order of its members.
+// (max(+0, -0) may return either zero, but the pooled value goes through relu(x + b3) next, which maps both to the same
+// bits; rounding a neighbourhood up to GR rows repeats the member in slot 0, and any member is idempotent under max.)
+// So the walk's hit() stores straight to the global row at the slot its LDS counter hands out: no LDS hit buffer, no
+// sort, no second pass over the rows.  The one place where order carries information stays: a query with more than
+// nsample hits keeps the nsample SMALLEST indices, through the same whole-cloud redo.  The slots of a row therefore
+// differ from run to run (atomic arrival order); the counts, the set in slots [0, max(cnt, 1)) and every consumer's
+// output do not.
 constexpr int BQG = 48;            // columns per side
 #ifndef MPX_BQG_THREADS
 #define MPX_BQG_THREADS 1024
@@ -943,6 +954,7 @@ __device__ __forceinline__ void bq_sort_rows(int j, int jn_left, const unsigned 
   }
 }
 
+template <bool SET>
 __global__ void __launch_bounds__(BQG_THREADS)
     ball_query_grid_kernel(const float *__restrict__ new_xyz, int new_stride, const float *__restrict__ xyz, int stride,
                            int N, int npoint, float radius2, float inv_h, int nsample, int32_t *__restrict__ idx,
@@ -953,8 +965,8 @@ __global__ void __launch_bounds__(BQG_THREADS)
   unsigned short *cstart = reinterpret_cast<unsigned short *>(ccount + BQG * BQG);  // [G*G + 1]
   unsigned short *qcnt = cstart + BQG * BQG + 2;                                    // [npoint] hits per query
   unsigned short *ovf = qcnt + ((npoint + 1) & ~1);                                 // [npoint] overflowing queries
-  unsigned short *hbuf = ovf + ((npoint + 1) & ~1);                                 // [npoint][BQ_HC] first hits of a row
-  int *cnt_s = reinterpret_cast<int *>(hbuf + (size_t)npoint * BQ_HC);              // [npoint] hits found so far (atomic)
+  unsigned short *hbuf = ovf + ((npoint + 1) & ~1);                                 // [npoint][BQ_HC] first hits of a row (none if SET)
+  int *cnt_s = reinterpret_cast<int *>(hbuf + (SET ? (size_t)0 : (size_t)npoint * BQ_HC));  // [npoint] hits found so far (atomic)
   __shared__ float red[2 * (BQG_THREADS / 64)];
   __shared__ int scan_s[BQG_THREADS / 64];
   __shared__ int n_ovf;
@@ -1057,8 +1069,12 @@ __global__ void __launch_bounds__(BQG_THREADS)
     int32_t *out = rows + (size_t)j * nsample;
     auto hit = [&](int k) __attribute__((always_inline)) {
       const int slot = atomicAdd(&cnt_s[j], 1);
-      if (slot < BQ_HC) hbuf[j * BQ_HC + slot] = (unsigned short)k;
-      else if (slot < nsample) out[slot] = k;
+      if constexpr (SET) {
+        if (slot < nsample) out[slot] = k;
+      } else {
+        if (slot < BQ_HC) hbuf[j * BQ_HC + slot] = (unsigned short)k;
+        else if (slot < nsample) out[slot] = k;
+      }
     };
     for (int gx = x0; gx <= x1; ++gx) {
       // columns y0..y1 of one x are adjacent in the sorted order: one contiguous range, halved between the two lanes
@@ -1091,7 +1107,12 @@ __global__ void __launch_bounds__(BQG_THREADS)
   for (int j = tid; j < npoint; j += BQG_THREADS) {
     const int c = cnt_s[j];
     if (c > nsample) ovf[atomicAdd(&n_ovf, 1)] = (unsigned short)j;  // needs the nsample SMALLEST indices: redone below
-    qcnt[j] = (unsigned short)(c < nsample ? c : nsample);
+    if constexpr (SET) {  // the row is final unless it overflowed: its count, and slot 0 of an empty row
+      cnt_out[(size_t)b * npoint + j] = c < nsample ? c : nsample;
+      if (c == 0) rows[(size_t)j * nsample] = 0;
+    } else {
+      qcnt[j] = (unsigned short)(c < nsample ? c : nsample);
+    }
   }
   __threadfence_block();
   __syncthreads();
@@ -1113,12 +1134,13 @@ __global__ void __launch_bounds__(BQG_THREADS)
       const unsigned long long m = __ballot(hit);
       const int pos = have + __popcll(m & ((1ull << lane) - 1ull));
       if (hit && pos < nsample) {
-        if (pos < BQ_HC) hbuf[j * BQ_HC + pos] = (unsigned short)k;
+        if (!SET && pos < BQ_HC) hbuf[j * BQ_HC + pos] = (unsigned short)k;
         else out[pos] = k;
       }
       have += __popcll(m);
     }
   }
+  if constexpr (SET) return;  // (every row is complete in global memory: nothing to sort)
   __threadfence_block();
   __syncthreads();
 
@@ -1186,7 +1208,7 @@ __global__ void __launch_bounds__(BQG_THREADS)
 }
 
 static int ball_query_impl(const float *new_xyz, int new_stride, const float *xyz, int stride, int B, int N, int npoint,
-                           float radius, int nsample, int32_t *idx, int32_t *cnt, int pad, mpx_stream_t stream) {
+                           float radius, int nsample, int32_t *idx, int32_t *cnt, int pad, bool set, mpx_stream_t stream) {
   MPX_REQUIRE(B >= 0 && N >= 0 && npoint >= 0 && nsample >= 0, "mpx_ball_query: negative size");
   MPX_REQUIRE(stride >= 3 && new_stride >= 3, "mpx_ball_query: stride < 3");
   if (B == 0 || npoint == 0 || nsample == 0) return 0;
@@ -1194,7 +1216,7 @@ static int ball_query_impl(const float *new_xyz, int new_stride, const float *xy
     for (int64_t b0 = 0; b0 < B; b0 += MPX_GRID_Y)
       if (int rc = ball_query_impl(new_xyz + b0 * npoint * new_stride, new_stride, xyz + b0 * N * stride, stride,
                                    (int)(B - b0 < MPX_GRID_Y ? B - b0 : MPX_GRID_Y), N, npoint, radius, nsample,
-                                   idx + b0 * npoint * nsample, cnt ? cnt + b0 * npoint : nullptr, pad, stream))
+                                   idx + b0 * npoint * nsample, cnt ? cnt + b0 * npoint : nullptr, pad, set, stream))
         return rc;
     return 0;
   }
@@ -1203,13 +1225,20 @@ static int ball_query_impl(const float *new_xyz, int new_stride, const float *xy
   const int fast = g_variant[MPX_VARIANT_BALL_QUERY].load(std::memory_order_relaxed);
   if (fast && N >= 2048 && N <= 8192 && nsample <= 128 && nsample > BQ_HC && npoint <= 4096 && radius > 0.0f &&
       radius * BQG < 4.0f) {  // columns of side ~radius must still resolve the scene (48 x radius < 4 m)
+    // (set == true: hits go straight to their global rows, so there is no [npoint][BQ_HC] hit buffer)
     const size_t lds = (size_t)4 * N * 4 + (size_t)BQG * BQG * 4 + (size_t)(BQG * BQG + 2) * 2 +
-                       (size_t)((npoint + 1) & ~1) * 2 * 2 + (size_t)npoint * BQ_HC * 2 + (size_t)npoint * 4;
+                       (size_t)((npoint + 1) & ~1) * 2 * 2 + (set ? 0 : (size_t)npoint * BQ_HC * 2) + (size_t)npoint * 4;
     if (lds <= 158 * 1024) {
-      MPX_LDS_LIMIT_ONCE(ball_query_grid_kernel, 158 * 1024, "mpx_ball_query");
       const float inv_h = 1.0f / (radius * 1.0001f);
-      hipLaunchKernelGGL(ball_query_grid_kernel, dim3(B), dim3(BQG_THREADS), lds, mpx_s(stream), new_xyz, new_stride, xyz,
-                         stride, N, npoint, r2, inv_h, nsample, idx, cnt, pad);
+      if (set) {
+        MPX_LDS_LIMIT_ONCE(ball_query_grid_kernel<true>, 158 * 1024, "mpx_ball_query_set");
+        hipLaunchKernelGGL(ball_query_grid_kernel<true>, dim3(B), dim3(BQG_THREADS), lds, mpx_s(stream), new_xyz, new_stride,
+                           xyz, stride, N, npoint, r2, inv_h, nsample, idx, cnt, 0);
+        MPX_LAUNCH_CHECK("mpx_ball_query_set");
+      }
+      MPX_LDS_LIMIT_ONCE(ball_query_grid_kernel<false>, 158 * 1024, "mpx_ball_query");
+      hipLaunchKernelGGL(ball_query_grid_kernel<false>, dim3(B), dim3(BQG_THREADS), lds, mpx_s(stream), new_xyz, new_stride,
+                         xyz, stride, N, npoint, r2, inv_h, nsample, idx, cnt, pad);
       MPX_LAUNCH_CHECK("mpx_ball_query");
     }
   }
@@ -1245,7 +1274,7 @@ static int ball_query_impl(const float *new_xyz, int new_stride, const float *xy
 MPX_EXPORT int mpx_ball_query(const float *new_xyz, int new_stride, const float *xyz, int stride, int B, int N,
                               int npoint, float radius, int nsample, int32_t *idx, int32_t *cnt,
                               mpx_stream_t stream) {
-  return ball_query_impl(new_xyz, new_stride, xyz, stride, B, N, npoint, radius, nsample, idx, cnt, 1, stream);
+  return ball_query_impl(new_xyz, new_stride, xyz, stride, B, N, npoint, radius, nsample, idx, cnt, 1, false, stream);
 }
 // the hit slots only: idx[b, j, 0 .. max(cnt, 1)) are written, the padding slots are LEFT UNTOUCHED -- for consumers that
 // take the hit count and never look past it (the fused grouped-MLP kernels with `cnt`): the first module's rows are 12 %
@@ -1257,7 +1286,20 @@ MPX_EXPORT int mpx_ball_query_hits(const float *new_xyz, int new_stride, const f
   // (the grouped-MLP kernels honour `cnt` up to 256 slots per neighbourhood; above that mpx_sa_mlp walks every slot, and
   // would read the slots this entry point leaves unwritten)
   MPX_REQUIRE(nsample <= 256, "mpx_ball_query_hits: nsample = %d > 256 (use mpx_ball_query: full rows)", nsample);
-  return ball_query_impl(new_xyz, new_stride, xyz, stride, B, N, npoint, radius, nsample, idx, cnt, 0, stream);
+  return ball_query_impl(new_xyz, new_stride, xyz, stride, B, N, npoint, radius, nsample, idx, cnt, 0, false, stream);
+}
+// the hit slots as a SET: the counts of mpx_ball_query, and in idx[b, j, 0 .. max(cnt, 1)) exactly the indices
+// mpx_ball_query_hits writes there, in UNSPECIFIED order (an empty row gets its slot 0 = 0; the other slots are left
+// untouched) -- for consumers that pool over the listed neighbours with a max and so consume no order (the fused
+// grouped-MLP kernels with `cnt`: see ball_query_grid_kernel).  The bucketed search then skips its per-row sort; the
+// small-cloud and brute-force kernels emit their hits in index order by construction and serve this entry point as they
+// are.  cnt is required; nsample <= 256 as for mpx_ball_query_hits.
+MPX_EXPORT int mpx_ball_query_set(const float *new_xyz, int new_stride, const float *xyz, int stride, int B, int N,
+                                  int npoint, float radius, int nsample, int32_t *idx, int32_t *cnt,
+                                  mpx_stream_t stream) {
+  MPX_REQUIRE(cnt != nullptr, "mpx_ball_query_set: the hit counts are required (they say which slots were written)");
+  MPX_REQUIRE(nsample <= 256, "mpx_ball_query_set: nsample = %d > 256 (use mpx_ball_query: full rows)", nsample);
+  return ball_query_impl(new_xyz, new_stride, xyz, stride, B, N, npoint, radius, nsample, idx, cnt, 0, true, stream);
 }
 
 // ---- QueryAndGroup, materialised (API parity with the reference's unfused path) ---------------------

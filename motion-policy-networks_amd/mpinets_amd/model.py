@@ -87,6 +87,9 @@ class MPiNetsPointNet(nn.Module):
         # +5.5 % time -- every launch has a tail); larger ones (the whole 65 536-environment configuration) in slabs of <= 8192.
         # Slabs stay above 1024 environments for chunk >= 2048, i.e. inside the dense layers' large-batch launch shape.
         self.workspace_chunk = 8192
+        # tests only: True keeps the index-ordered hit rows (mpx_ball_query_hits) where the engine's call takes the hit
+        # SETS (mpx_ball_query_set) -- the two must give the same output bits (tests/test_gpu_ball_query_sets.py)
+        self.ordered_ball_query = False
         self._derived = SplitWeights()  # (its pairs entries are named by their layer)
 
     def _lin(self, x, layer, act=ACT_NONE, out=None, weight=None):
@@ -355,10 +358,13 @@ class MPiNetsPointNet(nn.Module):
         cnt2 = torch.empty((B, sa2.npoint), dtype=torch.int32, device=dev)
 
         # the fused grouped-MLP kernels take the hit counts and never look past them: the ball queries then write the hit
-        # slots only (most of a 128-slot row is padding).  With `aux` (callers that want the reference's full index rows)
-        # or with padding elision off, the rows are padded like pointnet2_ops pads them.
-        bq1 = "mpx_ball_query_hits" if (aux is None and sa1.elide_padding) else "mpx_ball_query"
-        bq2 = "mpx_ball_query_hits" if (aux is None and sa2.elide_padding) else "mpx_ball_query"
+        # slots only (most of a 128-slot row is padding) -- and as a SET, in no particular order: those kernels max-pool over
+        # the listed neighbours, which consumes no order, so the first module's bucketed search skips its per-row sort.
+        # With `aux` (callers that want the reference's full index rows) or with padding elision off, the rows are ordered
+        # and padded like pointnet2_ops pads them.
+        hits = "mpx_ball_query_hits" if self.ordered_ball_query else "mpx_ball_query_set"
+        bq1 = hits if (aux is None and sa1.elide_padding) else "mpx_ball_query"
+        bq2 = hits if (aux is None and sa2.elide_padding) else "mpx_ball_query"
         want_rows = use_factored(sa2, C1o, c2)
 
         def sample_sa2():  # needs only xyz1
