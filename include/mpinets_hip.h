@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: an addition, no caller of an earlier 340 library needs rebuilding): mpx_ball_query_set;
+int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_franka_cloud_collision,
+                          MPX_VARIANT_CLOUD_CULL; 340 (unchanged, likewise): mpx_ball_query_set;
                           340 (unchanged, likewise): mpx_franka_ik, struct mpx_ik_options, mpx_franka_plan, struct mpx_plan_options;
                           340: mpx_pool_wgrad / mpx_pool_wgrad_scratch / mpx_pool_dgrad, mpx_linear_segmax / mpx_linear_segmax_bf16x3, mpx_pack_rows_ld / mpx_pack_rows_grad_ld (additions only);
                           330: mpx_sa3_front_bf16x3 / _pack / _pack_size / _w3_pairs (additions), the measurement hooks mpx_sa3_chain_probe / mpx_sa2_bf16x3_set_probe /
@@ -103,6 +104,34 @@ int mpx_franka_collision(const float *q, int B, int T, float finger, const float
                          const float *cyl_frames, const float *cyl_radii,
                          const float *cyl_heights, int M2, int32_t *flags, float *min_sdf,
                          mpx_stream_t stream);
+
+/* Swept-sphere check of q [B,T,7] against one POINT CLOUD per environment -- the scene as the policy sees it (a depth
+ * cloud, a captured cloud, the scene rows of the xyz slab), no primitives needed.  Point i of environment b is the three
+ * floats at cloud + b*cloud_batch_stride + i*cloud_point_stride (strides in floats, point stride >= 3: `xyz[:, 2048:6144,
+ * :3]` of a [B,6272,4] slab is read in place); counts (optional int32 [B]) = how many of the N rows of environment b
+ * exist, clamped to [0, N] on the device (NULL: all N).
+ *   c      = centre of sphere s at waypoint (b,t): the arithmetic of mpx_franka_spheres, bit for bit
+ *   d2     = fma(dz,dz, fma(dx,dx, dy*dy)) with dx = c.x - p.x, dy, dz likewise, in float32 (the library's one squared
+ *            distance; MPX_SQDIST_XFIRST builds do not change this file)
+ *   R      = (sph_radii[s] + point_radius) + clearance in float32 (the caller keeps it >= 0: the test squares it)
+ *   hit    : d2 <= R*R;  flags[b] |= 1 if any (waypoint, sphere, existing point) of environment b hits.  flags int32 [B]
+ *            is OR-ed into (caller zeroes it, as for mpx_franka_collision)
+ *   best   = +inf, then `if (d2 < best) best = d2, nearest = i` over i ascending: the LOWEST index wins a tie; a point
+ *            with a NaN or infinite coordinate never hits and is never nearest; an environment without points gives no
+ *            hit, min_dist = +inf, nearest = -1
+ *   min_dist [B,T,S] (optional) = sqrtf(best) - point_radius;  nearest int32 [B,T,S] (optional) = the index behind best
+ * This is sphere-CENTRE to POINT distance: a surface sampled at spacing h can pass between the points of its cloud, and
+ * point_radius is the caller's way to close that gap (about h / 2 for a gap-free cover of a flat patch).
+ * With min_dist and nearest both NULL ("flags only") a workgroup may skip points outside the box of its spheres and
+ * stop at the first hit (MPX_VARIANT_CLOUD_CULL); the flags are the same bit for bit.  S <= 64, point_radius >= 0.
+ * A workgroup takes MPX_CLOUD_TC waypoints of one environment and walks the cloud in tiles of MPX_CLOUD_TILE points. */
+#define MPX_CLOUD_TC 64
+#define MPX_CLOUD_TILE 256
+int mpx_franka_cloud_collision(const float *q, int B, int T, float finger, const float *sph_centers,
+                               const float *sph_radii, const int32_t *sph_link, int S, const float *cloud,
+                               int64_t cloud_batch_stride, int cloud_point_stride, int N, const int32_t *counts,
+                               float point_radius, float clearance, int32_t *flags, float *min_dist,
+                               int32_t *nearest, mpx_stream_t stream);
 
 /* rollout joint update, model.py:171-173 + utils.py:207-209:
  *   q_norm_out = clamp(q_norm + dq, -1, 1);  q_out = (q_norm_out + 1) * (hi - lo) / 2 + lo
@@ -481,7 +510,10 @@ int mpx_fps(const float *xyz, int B, int N, int stride, int npoint, int32_t *idx
  * (device, stream) handles per process).  0: handles not seen before get none, as if all 256 were taken -- the fp32
  * launchers then run one unit per wave without a queue (same results), mpx_sa_mlp_bf16x3_factored fails with a message. */
 #define MPX_VARIANT_UNIT_QUEUE 2
-#define MPX_VARIANT_COUNT_ 3
+/* 1 (default): the flags-only form of mpx_franka_cloud_collision discards points outside the box of its workgroup's
+ * spheres and stops at an environment's first hit.  0: it visits every point.  Same flags bit for bit either way.  */
+#define MPX_VARIANT_CLOUD_CULL 3
+#define MPX_VARIANT_COUNT_ 4
 int mpx_set_variant(int what, int value);
 int mpx_get_variant(int what); /* -1: unknown selector */
 

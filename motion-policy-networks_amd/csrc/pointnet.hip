@@ -643,7 +643,7 @@ static int opt_n_threads_log2(int n) {
 // query), variant 0 = the plain kernels they are proven against (fps_kernel, ball_query_kernel).  Both produce the same
 // indices bit for bit; the switch exists so that a test can run BOTH in one process on the same clouds
 // (tests/test_gpu_soak.py).  Process-wide, read at every launch.
-static std::atomic<int> g_variant[MPX_VARIANT_COUNT_] = {{1}, {1}, {1}};
+static std::atomic<int> g_variant[MPX_VARIANT_COUNT_] = {{1}, {1}, {1}, {1}};
 MPX_EXPORT int mpx_set_variant(int what, int value) {
   MPX_REQUIRE(what >= 0 && what < MPX_VARIANT_COUNT_, "mpx_set_variant: unknown selector %d", what);
   MPX_REQUIRE(value == 0 || value == 1, "mpx_set_variant: value must be 0 (plain kernels) or 1 (default)");

@@ -71,7 +71,9 @@ class BatchedEvaluator:
     @torch.no_grad()
     def evaluate_trajectories(self, trajectories: torch.Tensor, target_poses: torch.Tensor,
                               lengths: Optional[torch.Tensor] = None, cuboids=None, cylinders=None,
-                              target_volume=None, negative_volumes=None, dt: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                              target_volume=None, negative_volumes=None, dt: Optional[float] = None,
+                              scene_cloud: Optional[torch.Tensor] = None, scene_cloud_counts: Optional[torch.Tensor] = None,
+                              cloud_point_radius: float = 0.0) -> Dict[str, torch.Tensor]:
         """:param trajectories: [B,T,7] joint angles (rows past ``lengths[b]`` are ignored; they must still be
             valid configurations, e.g. the final one repeated, for the collision sweep)
         :param target_poses: [B,4,4] ``right_gripper`` targets
@@ -82,6 +84,11 @@ class BatchedEvaluator:
             negative volume. This is obviously a bad negative volume", metrics.py:507-512)
         :param dt: time between waypoints; when given (and T >= 2) the result also carries ``config_smoothness`` and
             ``eff_smoothness`` (SPARC, metrics.py:387-409, 495-497; the reference evaluates at dt = 0.12 s)
+        :param scene_cloud: optional [B,N,3] / [B,N,4] float32 point cloud per environment (``scene_cloud_counts``: how
+            many of its rows exist), for scenes that have no primitives -- a depth or a captured cloud.  When given,
+            ``collision`` is the primitive check OR ``FrankaCollisionSampler.check_cloud`` at ``cloud_point_radius``
+            (sphere centre to point distance: see there for what the radius is for), and the result also carries
+            ``cloud_collision``.  Without it the result is what it always was.
         """
         _lib.require_cuda(trajectories, target_poses)
         B, T, _ = trajectories.shape
@@ -97,6 +104,11 @@ class BatchedEvaluator:
             t_idx = torch.minimum(torch.arange(T, device=dev)[None, :], (ln.long() - 1).clamp(min=0)[:, None])
             tr = torch.gather(tr, 1, t_idx[:, :, None].expand(-1, -1, 7)).contiguous()
         collision = self.collision_sampler.check(tr, cuboids, cylinders)
+        cloud_collision = None
+        if scene_cloud is not None:
+            cloud_collision = self.collision_sampler.check_cloud(tr, scene_cloud, scene_cloud_counts,
+                                                                 point_radius=cloud_point_radius)
+            collision = collision | cloud_collision
         region = torch.ones(B, dtype=torch.bool, device=dev)
         if target_volume is not None or negative_volumes is not None:
             last = (ln.long() - 1).clamp(min=0) if ln is not None else torch.full((B,), T - 1, device=dev)
@@ -117,6 +129,8 @@ class BatchedEvaluator:
                "collision": collision, "physical_violations": violation, "correct_final_region": region,
                "success": (pos < 1) & (ori < 15) & region & ~violation,
                "num_steps": ln if ln is not None else torch.full((B,), T, dtype=torch.int32, device=dev)}
+        if cloud_collision is not None:
+            res["cloud_collision"] = cloud_collision
         if dt is not None and T >= 2:
             res["config_smoothness"], res["eff_smoothness"] = self.smoothness(tr, ln, dt)
         return res

@@ -435,3 +435,46 @@ class FrankaCollisionSampler:
                   _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2, _lib.ptr(flags), _lib.ptr(msdf))
         has = flags != 0
         return (has, msdf) if return_sdf else has
+
+    def check_cloud(self, q: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                    point_radius: float = 0.0, clearance: float = 0.0, return_distance: bool = False,
+                    return_nearest: bool = False):
+        """Swept-sphere check of trajectories against one POINT CLOUD per environment (csrc/cloud_collision.hip): the
+        scene as the policy sees it -- a depth cloud, a captured cloud, the scene rows of the xyz slab -- with no
+        primitives behind it.
+
+        :param q: [B,T,7] (or [B,7]) joint angles
+        :param cloud: [B,N,3] or [B,N,4] float32 on the GPU; any view whose last stride is 1 is read in place
+            (``xyz[:, 2048:6144, :3]`` of the slab), rows with a NaN or infinite coordinate are ignored
+        :param counts: optional int [B]: only the first ``counts[b]`` rows of environment b exist (clamped to [0, N])
+        :param point_radius: radius given to every point, >= 0.  The test is sphere-CENTRE to POINT distance
+            ``<= (r_s + point_radius) + clearance``: a surface sampled at spacing h can pass between its points, and this
+            is the caller's way to close that gap.  No default is right for every cloud; 0 is the bare points.
+        :returns: ``has_collision`` bool [B]; then ``min_dist`` [B,T,S] (distance of every sphere centre to the surface
+            of its nearest point's ball, +inf without points) when ``return_distance`` and ``nearest`` int32 [B,T,S]
+            (that point's row, lowest on a tie, -1 without points) when ``return_nearest``
+        """
+        if q.ndim == 2:
+            q = q.unsqueeze(1)
+        _lib.require_cuda(q, cloud, counts)
+        B, T, _ = q.shape
+        if cloud.ndim != 3 or cloud.size(0) != B or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32:
+            raise _lib.MpxError(f"check_cloud: cloud must be float32 [B={B},N,3] or [B,N,4], got {cloud.dtype} {tuple(cloud.shape)}")
+        N = cloud.size(1)
+        if N > 0 and B > 0 and cloud.stride(2) != 1:
+            raise _lib.MpxError("check_cloud: the cloud's last dimension must have stride 1")
+        ps = cloud.stride(1) if N > 1 else max(cloud.stride(1), 3)  # (a one-row view may carry any row stride)
+        qc = _lib.f32c(q)
+        cn = None
+        if counts is not None:
+            assert counts.shape == (B,)
+            cn = _lib.i32c(counts)
+        flags = torch.zeros(B, dtype=torch.int32, device=q.device)
+        S = self.num_spheres
+        dist = torch.empty((B, T, S), dtype=torch.float32, device=q.device) if return_distance else None
+        near = torch.empty((B, T, S), dtype=torch.int32, device=q.device) if return_nearest else None
+        _lib.call("mpx_franka_cloud_collision", _lib.ptr(qc), B, T, self.finger, _lib.ptr(self.centers),
+                  _lib.ptr(self.radii), _lib.ptr(self.links), S, _lib.ptr(cloud), cloud.stride(0), ps, N,
+                  _lib.ptr(cn), float(point_radius), float(clearance), _lib.ptr(flags), _lib.ptr(dist), _lib.ptr(near))
+        out = (flags != 0,) + ((dist,) if return_distance else ()) + ((near,) if return_nearest else ())
+        return out if len(out) > 1 else out[0]

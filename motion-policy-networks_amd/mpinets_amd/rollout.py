@@ -203,6 +203,14 @@ class RolloutEngine:
     def has_collision(self) -> torch.Tensor:
         return self.flags != 0
 
+    def cloud_collision(self, trajectory: torch.Tensor, point_radius: float = 0.0) -> torch.Tensor:
+        """``FrankaCollisionSampler.check_cloud`` of a [B,L,7] trajectory (e.g. ``rollout``'s) against the engine's OWN
+        scene rows of the slab, read in place: what the policy saw, whether or not primitives stand behind it.
+        -> bool [B]."""
+        n_robot = int(self.subset.numel())
+        scene = self.xyz[:, n_robot:self.xyz.size(1) - 128, :3]  # [robot | scene | 128 target rows]
+        return self.collision.check_cloud(trajectory, scene, point_radius=point_radius)
+
     def rollout_until_success(self, max_steps: int = 150, check_every: int = 1, native: bool = False):
         """Batched ``rollout_until_success`` (run_inference.py:137-191): step until every environment is
         within 1 cm / 15 deg of its target or ``max_steps`` is reached.  The host looks at the done
