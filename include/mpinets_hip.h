@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_franka_cloud_collision,
+int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_cloud_clean,
+                          mpx_cloud_clean_scratch; 340 (unchanged, likewise): mpx_franka_cloud_collision,
                           MPX_VARIANT_CLOUD_CULL; 340 (unchanged, likewise): mpx_ball_query_set;
                           340 (unchanged, likewise): mpx_franka_ik, struct mpx_ik_options, mpx_franka_plan, struct mpx_plan_options;
                           340: mpx_pool_wgrad / mpx_pool_wgrad_scratch / mpx_pool_dgrad, mpx_linear_segmax / mpx_linear_segmax_bf16x3, mpx_pack_rows_ld / mpx_pack_rows_grad_ld (additions only);
@@ -470,6 +471,47 @@ int mpx_depth_render(const float *cam_poses, float fx, float fy, float cx, float
 int mpx_depth_select(const float *depth, const float *cam_poses, float fx, float fy, float cx, float cy,
                      int W, int H, int B, int n_out, uint64_t seed, int64_t env_offset, float *out,
                      int64_t out_batch_stride, int out_point_stride, int32_t *count, mpx_stream_t stream);
+
+/* Cleaning of CAPTURED clouds, the step the reference's real-robot planner leaves to its caller
+ * (interactive_demo/mpinets_ros/nodes/planning_node.py:78-151 asserts a [4096,3] cloud; its clean_point_cloud, :187-228,
+ * crops to two boxes and draws on the host): crop, robot removal, outlier removal and the draw, for a batch.
+ * Row i of environment b is the three floats at cloud + b*cloud_batch_stride + i*cloud_point_stride (strides in floats,
+ * point stride >= 3, read in place as for mpx_franka_cloud_collision); the rows i < n_b exist, n_b = counts[b] clamped to
+ * [0, N], or N when counts is NULL.  Every row gets a reason, the FIRST stage it fails, or 0:
+ *   1  non-existent or non-finite: i >= n_b, or a coordinate is NaN or infinite
+ *   2  outside the workspace (skipped when n_boxes == 0): no box j of boxes [n_boxes,6] (lo xyz, hi xyz; one set for the
+ *      batch) has lo_j < p < hi_j STRICTLY on all three axes, float32 comparisons.  n_boxes <= MPX_CLEAN_MAX_BOXES
+ *   3  robot (skipped when S == 0): some sphere s has d2 <= R_s*R_s with d2 = fma(dz,dz, fma(dx,dx, dy*dy)), dx = p.x - c.x
+ *      (dy, dz likewise) in float32 -- the library's one squared distance -- and R_s = sph_radii[s] + robot_margin in
+ *      float32.  sph_centers [B,S,3] are mpx_franka_spheres' output.  S <= MPX_CLEAN_MAX_SPHERES, robot_margin >= 0
+ *   4  outlier (skipped when min_neighbors == 0): with alive1 = the rows that passed 1-3, row i is kept iff at least
+ *      min_neighbors rows j != i (by index) of alive1 have d2(p_i - p_j) <= r*r, r = outlier_radius > 0, r*r in float32.
+ *      A row with the same coordinates is a neighbour.  ONE pass: neighbours are counted among alive1, not among the
+ *      final survivors.
+ * count [B] = rows with reason 0.  reason uint8 [B,N] (optional) is written for all N rows.
+ * Draw (n_out == 0: filter only; else n_out <= 4096): an environment with count[b] < n_out is left untouched in out and
+ * src_index (the caller raises like numpy, as for mpx_depth_select).  Otherwise row i gets word i & 3 of
+ * Philox4x32-10(counter = (i >> 2, env_offset + b, 15, 0), key = (seed lo, seed hi)) as its key, the n_out smallest
+ * (key, i) pairs win and, in ascending order k, src_index[b,k] = i_k (int32 [B,n_out], optional) and out[b,k,0:3] =
+ * cloud[b,i_k,0:3] bit for bit, at out + b*out_batch_stride + k*out_point_stride; nothing else of an output row is
+ * touched (a slab row keeps its label column).
+ * The result depends on the inputs alone: not on the grid below, nor on the order in which atomics land.
+ * Stage 4 bins alive1 into a uniform grid per environment (over the bounding box of the crop boxes, else over alive1's
+ * own box; cell edge >= 1.01 r, at most MPX_CLEAN_MAX_CELLS cells -- a far-away row without a crop box only makes the
+ * cells coarse) and counts within the 27 cells around a row, stopping at min_neighbors.
+ * scratch: device memory, 16-byte aligned, at least mpx_cloud_clean_scratch(B, N) bytes, owned by the caller and free
+ * again when the call's work on the stream has finished.  Bad arguments are refused before any launch; B == 0
+ * launches nothing. */
+#define MPX_CLEAN_MAX_BOXES 8
+#define MPX_CLEAN_MAX_SPHERES 64
+#define MPX_CLEAN_MAX_CELLS 262144
+int64_t mpx_cloud_clean_scratch(int B, int N);
+int mpx_cloud_clean(const float *cloud, int64_t cloud_batch_stride, int cloud_point_stride, int N,
+                    const int32_t *counts, int B, const float *boxes, int n_boxes, const float *sph_centers,
+                    const float *sph_radii, int S, float robot_margin, float outlier_radius, int min_neighbors,
+                    int n_out, uint64_t seed, int64_t env_offset, float *out, int64_t out_batch_stride,
+                    int out_point_stride, int32_t *src_index, uint8_t *reason, int32_t *count, void *scratch,
+                    int64_t scratch_bytes, mpx_stream_t stream);
 
 /* ---- scene point clouds: mpinets/geometry.py:571-608 (construct_mixed_point_cloud), batched ----- */
 

@@ -57,6 +57,8 @@ PROTOTYPES = {
     "mpx_gather_rows": [P, P, I, I, P, P],
     "mpx_depth_render": [P, F, F, F, F, I, I, I, P, P, I, P, P, P, I, P, P, I, F, P, P],
     "mpx_depth_select": [P, P, F, F, F, F, I, I, I, I, ctypes.c_uint64, L, P, L, I, P, P],
+    "mpx_cloud_clean_scratch": [I, I],
+    "mpx_cloud_clean": [P, L, I, I, P, I, P, I, P, P, I, F, F, I, I, ctypes.c_uint64, L, P, L, I, P, P, P, P, L, P],
     "mpx_scene_cloud": [P, P, P, I, P, P, P, P, I, I, I, ctypes.c_uint64, L, P, P, P, P, L, I, I, P],
     "mpx_set_variant": [I, I],
     "mpx_get_variant": [I],
@@ -113,7 +115,7 @@ PROTOTYPES = {
     "mpx_rollout_step": [P, P, P, I, P, P, I, P, P, P, L, P],
     "mpx_rollout": [P, P, P, P, I, P, P, I, P, P, P, L, P],
 }
-RESTYPES = {"mpx_last_error": c_char_p, "mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
+RESTYPES = {"mpx_last_error": c_char_p, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
             "mpx_linear_wgrad_scratch": c_int64, "mpx_pool_wgrad_scratch": c_int64, "mpx_linear_workspace": c_int64, "mpx_policy_workspace": c_int64, "mpx_rollout_workspace": c_int64}
 
 

@@ -1,0 +1,166 @@
+"""Cleaning of captured point clouds on the device: crop, robot removal, outlier removal, draw (csrc/cloud_clean.hip).
+
+The reference's real-robot planner (``interactive_demo/mpinets_ros/nodes/planning_node.py:78-151``) asserts that the
+obstacle cloud it is given is already ``[4096, 3]``: "You must downsample obstacle PC before passing to planner. While
+you're at it, filter the outliers out as well".  Its own ``clean_point_cloud`` (``:187-228``) crops the capture to two
+workspace boxes and draws 4096 rows with ``np.random.choice`` on the host; removing the robot's own points and the
+outliers is left to the reader.  ``clean_point_clouds`` does all four for a batch of captures with one call of
+``mpx_cloud_clean``; ``clean_point_cloud`` keeps the reference's signature.
+
+Every row gets a ``reason``: 0 kept, 1 non-existent / non-finite, 2 outside the workspace, 3 robot, 4 outlier -- the
+first stage it fails (include/mpinets_hip.h has the arithmetic of each).
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .robot import FrankaCollisionSampler
+
+# planning_node.py:201-221: the task table and the mount table, rows of (lo x, lo y, lo z, hi x, hi y, hi z); a point is
+# inside when it is STRICTLY inside one of them
+REFERENCE_WORKSPACE = np.array([[0.25, -0.3, -0.05, 1.35, 1.6, 0.35],
+                                [-0.35, -0.5, -0.05, 0.30, 0.5, 0.05]], dtype=np.float32)
+REASONS = ("kept", "non-existent or non-finite", "outside the workspace", "robot", "outlier")
+MAX_POINTS = 4096  # SEL_MAX_OUT: what one workgroup's select can draw
+
+_scratch: Dict[int, torch.Tensor] = {}
+_samplers: Dict[int, FrankaCollisionSampler] = {}
+_boxes: Dict[Tuple[int, bytes], torch.Tensor] = {}
+
+
+def _scratch_for(device: torch.device, nbytes: int) -> torch.Tensor:
+    """One growing device buffer per GPU (the call's work is ordered on the stream, like every workspace here)."""
+    buf = _scratch.get(device.index)
+    if buf is None or buf.numel() < nbytes:
+        buf = _scratch[device.index] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    return buf
+
+
+def _boxes_on(device: torch.device, boxes) -> Tuple[Optional[torch.Tensor], int]:
+    if boxes is None:
+        return None, 0
+    if isinstance(boxes, torch.Tensor):
+        t = _lib.f32c(boxes.to(device))
+    else:
+        a = np.ascontiguousarray(boxes, dtype=np.float32)
+        key = (device.index, a.tobytes())
+        t = _boxes.get(key)
+        if t is None:
+            if len(_boxes) > 64:
+                _boxes.clear()
+            t = _boxes[key] = torch.from_numpy(a.copy()).to(device)
+    if t.ndim != 2 or t.size(1) != 6:
+        raise _lib.MpxError(f"clean_point_clouds: boxes must be [n, 6] (lo xyz, hi xyz), got {tuple(t.shape)}")
+    return (t, t.size(0)) if t.size(0) else (None, 0)
+
+
+@torch.no_grad()
+def clean_point_clouds(cloud: torch.Tensor, num_points: int = 4096, *, counts: Optional[torch.Tensor] = None,
+                       boxes=REFERENCE_WORKSPACE, q: Optional[torch.Tensor] = None,
+                       collision_sampler: Optional[FrankaCollisionSampler] = None, robot_margin: float = 0.0,
+                       outlier_radius: float = 0.0, min_neighbors: int = 0, seed: int = 0, env_offset: int = 0,
+                       out: Optional[torch.Tensor] = None, return_index: bool = False, return_reason: bool = False):
+    """Crop, remove the robot, remove outliers and draw ``num_points`` rows of every captured cloud.
+
+    :param cloud: float32 [B,N,3] or [B,N,4] on the GPU; any view whose last stride is 1 is read in place
+    :param counts: optional int [B]: only the first ``counts[b]`` rows of environment b exist (clamped to [0, N])
+    :param boxes: [n,6] (lo xyz, hi xyz), n <= 8, shared by the batch: a row is kept when it is strictly inside one of them.
+        ``None``: no crop.  Default: the reference's two workspace boxes
+    :param q: [B,7] joint angles at capture time: rows within ``radius + robot_margin`` of a collision sphere's centre
+        are removed.  ``collision_sampler`` defaults to ``FrankaCollisionSampler(device, with_base_link=True)`` -- a
+        capture shows the base.  A ``robot_margin`` above ``point_radius + clearance`` of a later ``check_cloud`` with the
+        same sampler makes the cleaned cloud free of hits at ``q`` by construction
+    :param outlier_radius, min_neighbors: a row is kept when at least ``min_neighbors`` OTHER rows that passed the crop
+        and the robot stage lie within ``outlier_radius`` of it (one pass).  ``min_neighbors=0``: off
+    :param seed, env_offset: row b draws as global environment ``env_offset + b`` (sharded batches)
+    :param out: where to write, e.g. the slab's scene rows ``xyz[:, 2048:6144]``: only columns 0-2 of its first
+        ``num_points`` rows are written
+    :returns: ``[B,num_points,3]``, a uniform subset of the kept rows in uniform order; then ``src_index`` int32
+        ``[B,num_points]`` (the rows' indices in ``cloud``) when ``return_index`` and ``reason`` uint8 ``[B,N]`` when
+        ``return_reason``.  ``num_points=0`` filters only and returns ``(reason, counts)``.  The kept rows per environment
+        stay in ``clean_point_clouds.last_counts``.
+    :raises ValueError: like ``np.random.choice`` when an environment keeps fewer than ``num_points`` rows
+    """
+    _lib.require_cuda(cloud, counts, q, out)
+    if cloud.ndim != 3 or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32:
+        raise _lib.MpxError(f"clean_point_clouds: cloud must be float32 [B,N,3] or [B,N,4], got {cloud.dtype} {tuple(cloud.shape)}")
+    B, N = cloud.size(0), cloud.size(1)
+    dev = cloud.device
+    if N > 0 and B > 0 and cloud.stride(2) != 1:
+        raise _lib.MpxError("clean_point_clouds: the cloud's last dimension must have stride 1")
+    ps = cloud.stride(1) if N > 1 else max(cloud.stride(1), 3)  # (a one-row view may carry any row stride)
+    num_points = int(num_points)
+    if not 0 <= num_points <= MAX_POINTS:
+        raise _lib.MpxError(f"clean_point_clouds: num_points must be in [0, {MAX_POINTS}], got {num_points}")
+    cn = None
+    if counts is not None:
+        assert counts.shape == (B,)
+        cn = _lib.i32c(counts)
+    bx, n_boxes = _boxes_on(dev, boxes)
+    sc = sr = None
+    S = 0
+    if q is not None:
+        cs = collision_sampler
+        if cs is None:
+            cs = _samplers.get(dev.index)
+            if cs is None:
+                cs = _samplers[dev.index] = FrankaCollisionSampler(dev, with_base_link=True)
+        assert q.shape == (B, 7)
+        sc, sr, S = cs.sphere_centers(q), cs.radii, cs.num_spheres
+    obs = ops = 0
+    if num_points > 0:
+        if out is None:
+            out = torch.empty((B, num_points, 3), dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and out.size(0) == B and out.size(1) >= num_points and out.size(2) >= 3
+        assert out.stride(2) == 1
+        obs, ops = out.stride(0), out.stride(1) if out.size(1) > 1 else max(out.stride(1), 3)
+    want_reason = return_reason or num_points == 0
+    reason = torch.empty((B, N), dtype=torch.uint8, device=dev) if want_reason else None
+    index = torch.empty((B, num_points), dtype=torch.int32, device=dev) if return_index and num_points > 0 else None
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = int(_lib.load().mpx_cloud_clean_scratch(B, N))
+    scratch = _scratch_for(dev, nbytes)
+    _lib.call("mpx_cloud_clean", _lib.ptr(cloud), cloud.stride(0), ps, N, _lib.ptr(cn), B, _lib.ptr(bx), n_boxes,
+              _lib.ptr(sc), _lib.ptr(sr), S, float(robot_margin), float(outlier_radius), int(min_neighbors), num_points,
+              int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(out) if num_points else None, obs, ops, _lib.ptr(index),
+              _lib.ptr(reason), _lib.ptr(count), _lib.ptr(scratch), nbytes)
+    clean_point_clouds.last_counts = count
+    if num_points == 0:
+        return reason, count
+    if B > 0:
+        host = count.cpu()
+        b = int(host.argmin().item())
+        if int(host[b].item()) < num_points:
+            raise ValueError("Cannot take a larger sample than population when 'replace=False' "
+                             f"(environment {b} keeps {int(host[b].item())} of its rows, {num_points} requested)")
+    res = (out[:, :num_points, :3],) + ((index,) if return_index else ()) + ((reason,) if return_reason else ())
+    return res if len(res) > 1 else res[0]
+
+
+clean_point_clouds.last_counts = None
+
+
+def clean_point_cloud(xyz: np.ndarray, rgba: np.ndarray, **kw) -> Tuple[np.ndarray, np.ndarray]:
+    """The reference's ``clean_point_cloud(xyz, rgba)`` (planning_node.py:187-228): NumPy ``[N,3]`` and ``[N,4]`` ->
+    ``(xyz [num_points,3], rgba [num_points,4])``.  With its defaults it is the reference's crop to the two workspace
+    boxes and the draw of 4096 rows without replacement; every keyword of ``clean_point_clouds`` is passed on (``q`` as
+    ``[7]`` or ``[1,7]``).  The subset is drawn on the device from ``seed`` (the reference uses NumPy's global state)."""
+    if not torch.cuda.is_available():
+        raise _lib.MpxError("clean_point_cloud needs a GPU (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pts = np.ascontiguousarray(xyz, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3 or len(rgba) != len(pts):
+        raise ValueError(f"clean_point_cloud: xyz must be [N,3] and rgba [N,...], got {pts.shape} and {np.shape(rgba)}")
+    for bad in ("out", "return_index", "return_reason", "counts"):
+        if bad in kw:
+            raise TypeError(f"clean_point_cloud() takes no {bad!r}: use clean_point_clouds")
+    if kw.get("q") is not None:
+        kw["q"] = torch.as_tensor(np.asarray(kw["q"], dtype=np.float32).reshape(1, 7)).to(dev)
+    cloud = torch.from_numpy(pts).to(dev).unsqueeze(0)
+    got, index = clean_point_clouds(cloud, kw.pop("num_points", 4096), return_index=True, **kw)
+    index = index[0].cpu().numpy()
+    return got[0].cpu().numpy(), np.asarray(rgba)[index]
