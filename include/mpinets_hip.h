@@ -29,7 +29,9 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_cloud_clean,
+int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_cloud_field_build,
+                          mpx_cloud_field_sample, mpx_franka_plan_cloud, mpx_franka_plan_cloud_scratch, struct mpx_field_grid;
+                          340 (unchanged, likewise): mpx_cloud_clean,
                           mpx_cloud_clean_scratch; 340 (unchanged, likewise): mpx_franka_cloud_collision,
                           MPX_VARIANT_CLOUD_CULL; 340 (unchanged, likewise): mpx_ball_query_set;
                           340 (unchanged, likewise): mpx_franka_ik, struct mpx_ik_options, mpx_franka_plan, struct mpx_plan_options;
@@ -270,6 +272,83 @@ int mpx_franka_plan(const float *q_start, const float *q_goal, int B, int T, flo
                     const float *cyl_radii, const float *cyl_heights, int M2, const mpx_plan_options *options,
                     uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *choice, float *all_traj,
                     int32_t *all_status, mpx_stream_t stream);
+
+/* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
+ * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at
+ *   (fma((float)i, h, lo[0]), fma((float)j, h, lo[1]), fma((float)k, h, lo[2]))  in float32.
+ * lo and trunc finite, h finite and > 0, trunc > 0, 2 <= nx, ny, nz <= MPX_FIELD_MAX_SIDE, nx*ny*nz <= MPX_FIELD_MAX_NODES;
+ * anything else is refused before a launch.                                                                            */
+#define MPX_FIELD_MAX_SIDE 1024
+#define MPX_FIELD_MAX_NODES (1 << 24)
+typedef struct mpx_field_grid {
+  float lo[3];    /* world position of node (0,0,0) */
+  float h;        /* node spacing [m], > 0 */
+  int nx, ny, nz; /* nodes per axis */
+  float trunc;    /* > 0: the field saturates here */
+} mpx_field_grid;
+
+/* field [B,nz,ny,nx] float32 (x fastest) = the distance of every node to the nearest point of environment b's cloud, cut
+ * at grid->trunc.  The cloud is addressed exactly as for mpx_franka_cloud_collision (strides in floats, point stride >= 3,
+ * `xyz[:, 2048:6144, :3]` of the slab read in place; counts optional int32 [B], clamped to [0, N] on the device, NULL: N).
+ *   best  = +inf; over the existing rows whose three coordinates are finite:
+ *           best = min(best, d2),  d2 = fma(dz,dz, fma(dx,dx, dy*dy)) with dx = node.x - p.x, dy, dz likewise (float32: the
+ *           library's one squared distance, the argument order of mpx_franka_cloud_collision with the node as the centre)
+ *   field = fminf(sqrtf(best), trunc)          (an environment without a usable row: trunc everywhere)
+ * A minimum does not depend on the order of its operands and nothing is accumulated, so the result depends on the inputs
+ * alone: not on the launch shape, not on the order in which points are staged.  A workgroup owns a brick of
+ * MPX_FIELD_BRICK^3 nodes and drops the points outside the brick's box inflated by more than trunc: a dropped point is
+ * farther than trunc from every node of the brick, so it could only have produced a value that the fminf replaces by
+ * trunc.  No allocation, no atomics on global memory, no scratch; B == 0 launches nothing.                              */
+#define MPX_FIELD_BRICK 8
+int mpx_cloud_field_build(const float *cloud, int64_t cloud_batch_stride, int cloud_point_stride, int N,
+                          const int32_t *counts, int B, const mpx_field_grid *grid, float *field, mpx_stream_t stream);
+
+/* Trilinear interpolant of the node values and its analytic derivative at points [B,P] (point p of environment b = the
+ * three floats at points + b*points_batch_stride + p*points_point_stride, strides in floats, point stride >= 3).
+ * dist [B,P]; grad [B,P,3] optional (NULL: not computed).  All in float32:
+ *   inv_h = 1.0f / h (once, on the host);  u = (x - lo[0]) * inv_h, v and w likewise for y and z
+ *   INSIDE: 0 <= u <= nx-1 and 0 <= v <= ny-1 and 0 <= w <= nz-1 (a NaN or infinite coordinate fails).  Not inside:
+ *   dist = trunc, grad = 0 -- the caller sizes the grid to the workspace.
+ *   i0 = min((int)floorf(u), nx-2), fx = u - (float)i0 (fx = 1 only on the last node of an axis); j0, fy, k0, fz likewise.
+ *   Corners c[z][y][x] = field[b, k0+z, j0+y, i0+x]; every lerp is lerp(f, a, b) = fma(f, b - a, a), so f = 0 returns a
+ *   bit for bit: a sample whose u, v, w are exact node indices below the last returns the node's value.
+ *   along x: a[z][y] = lerp(fx, c[z][y][0], c[z][y][1]);  along y: e[z] = lerp(fy, a[z][0], a[z][1]);
+ *   dist = lerp(fz, e[0], e[1])
+ *   grad.x = inv_h * lerp(fz, lerp(fy, X[0][0], X[0][1]), lerp(fy, X[1][0], X[1][1])),  X[z][y] = c[z][y][1] - c[z][y][0]
+ *   grad.y = inv_h * lerp(fz, a[0][1] - a[0][0], a[1][1] - a[1][0])
+ *   grad.z = inv_h * (e[1] - e[0])
+ * A SURFACE field: unsigned, no inside; the gradient is that of the interpolant (discontinuous across cell faces, not of
+ * unit length).  The result depends on the inputs alone.                                                               */
+int mpx_cloud_field_sample(const float *field, const mpx_field_grid *grid, int B, const float *points,
+                           int64_t points_batch_stride, int points_point_stride, int P, float *dist, float *grad,
+                           mpx_stream_t stream);
+
+/* mpx_franka_plan against a POINT CLOUD: the same planner -- candidates (Philox stream 14), L, M, the clamp, endpoints
+ * bit-equal, iterations = 0, the jerk bit, the self bit, the lowest valid candidate, choice, NaN rows on status != 0,
+ * options with the same defaults and the same refusals -- with these differences:
+ *   Environment term of one iteration.  D, n = mpx_cloud_field_sample's dist and grad of `field` [B,nz,ny,nx] (built by
+ *   mpx_cloud_field_build on `grid`) at the sphere centre x_s;  d_s = ((D - point_radius) - r_s) - clearance;  a sphere
+ *   with D >= trunc is saturated and contributes nothing (so does a centre outside the grid);  c'(d) as for
+ *   mpx_franka_plan;  n_s = n as sampled, not normalised.  field == NULL: no environment term.
+ *   Environment validity (bit 0 of all_status).  Candidate k is invalid exactly when mpx_franka_cloud_collision flags its
+ *   refined configurations [B,R,7], R = (T-1) substeps + 1 (r = t substeps + i, the same fma), against environment b's
+ *   cloud (cloud, strides, N, counts: as there) with this point_radius and clearance = options->clearance +
+ *   options->check_margin summed in float32: that entry itself is called, once per candidate, flags only.  The field
+ *   steers the optimiser and never judges.  cloud == NULL or N == 0 or S == 0: no environment test.
+ *   status 2: mpx_franka_plan's rule (an endpoint not finite, outside the limits, self hit with check_self), the
+ *   environment test being that call on the two endpoints [B,2,7].
+ * scratch: device memory, 16-byte aligned, at least mpx_franka_plan_cloud_scratch(B, T, candidates, substeps) bytes (-1 for
+ * sizes the planner refuses), owned by the caller, free when the stream has passed the call.  No allocation; every step
+ * is enqueued on `stream` (a memset of the flags, the optimise kernel, candidates + 1 flag calls, a select kernel).
+ * S <= 64, point_radius >= 0; B == 0 launches nothing.                                                                 */
+int64_t mpx_franka_plan_cloud_scratch(int B, int T, int candidates, int substeps);
+int mpx_franka_plan_cloud(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                          const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                          const float *field, const mpx_field_grid *grid, const float *cloud, int64_t cloud_batch_stride,
+                          int cloud_point_stride, int N, const int32_t *counts, float point_radius,
+                          const mpx_plan_options *options, uint64_t seed, int64_t env_offset, float *traj, int32_t *status,
+                          int32_t *choice, float *all_traj, int32_t *all_status, void *scratch, int64_t scratch_bytes,
+                          mpx_stream_t stream);
 
 /* ---- split-bf16 ("bf16x3") dense layers: the opt-in fast mode of mpx_linear / mpx_linear_rowmax ------
  * Every fp32 product is evaluated as x_hi*w_hi + x_hi*w_lo + x_lo*w_hi on the bf16 matrix cores (fp32

@@ -13,17 +13,7 @@
 // The validity sweep reuses the mapping with lane = refined configuration, in passes of 64.
 #include "common.h"
 #include "sdf_grad_device.h"
-#include "philox.h"
-
-enum { STREAM_PLAN = 14 };
-enum { PLAN_BIT_ENV = 1, PLAN_BIT_SELF = 2, PLAN_BIT_JERK = 4 };
-
-// the centre of a table sphere on a frame held in registers: rigid_apply's operations in rigid_apply's order
-__device__ __forceinline__ void plan_apply(const Rigid &g, float x, float y, float z, float &ox, float &oy, float &oz) {
-  ox = mpx_fma(g.r[2], z, mpx_fma(g.r[1], y, g.r[0] * x)) + g.t[0];
-  oy = mpx_fma(g.r[5], z, mpx_fma(g.r[4], y, g.r[3] * x)) + g.t[1];
-  oz = mpx_fma(g.r[8], z, mpx_fma(g.r[7], y, g.r[6] * x)) + g.t[2];
-}
+#include "plan_device.h"  // what the planner shares with cloud_field.hip: candidates, M g, the jerk and self tests
 
 // min over the live primitives (LDS rows [R | Rt (3 x 4 floats) | sizes]; cuboids from row 0, cylinders from row 64) and
 // the row that attains it: the first minimum, cuboids before cylinders (-1: no live primitive)
@@ -64,13 +54,7 @@ __device__ __forceinline__ int plan_config_bits(const float *q, float finger, co
       }
     }
     if constexpr (id == 7 || id == 9 || id == 12 || id == 13) {  // trajectory_metrics_kernel's self model
-      if (test_self) {
-        const float radius = id == 7 ? 0.1f : 0.01f;
-        const float zc = fminf(fmaxf(g.t[2], -0.3f), 0.333f);
-        const float dz = g.t[2] - zc;
-        const float d = sqrtf(mpx_fma(dz, dz, mpx_fma(g.t[1], g.t[1], g.t[0] * g.t[0])));
-        if (d < 0.15f + radius + self_margin) bits |= PLAN_BIT_SELF;
-      }
+      if (test_self && plan_self_hit<id>(g, self_margin)) bits |= PLAN_BIT_SELF;
     }
   });
   return bits;
@@ -141,12 +125,7 @@ __global__ void __launch_bounds__(64 * MAXK)
     for (int i = 0; i < 12; ++i) dst[i] = yf[16 * lane + i];
     dst[12] = r0, dst[13] = h0;
   }
-  // M[t,u] = min(t,u) (n + 1 - max(t,u)) / (n + 1): an exact integer product, one division
-  for (int i = threadIdx.x; i < T * T; i += blockDim.x) {
-    const int a = i / T, c = i - a * T;
-    const int mn = a < c ? a : c, mx = a < c ? c : a;
-    Mtab[i] = (float)(mn * (n + 1 - mx)) / (float)(n + 1);
-  }
+  plan_fill_metric(Mtab, T, n);
   __syncthreads();
 
   const bool test_env = S > 0 && n_cub + n_cyl > 0, test_self = opt.check_self != 0;
@@ -177,22 +156,7 @@ __global__ void __launch_bounds__(64 * MAXK)
 
   // ---- this lane's waypoint of candidate k ---------------------------------------------------------------------------------
   float L[7], q[7];
-  {
-    const float s = (float)t / (float)(T - 1);
-    float bump, unused;
-    mpx_sincos(3.14159265358979323846f * s, bump, unused);
-    const Philox p0 = philox4x32(2u * (uint32_t)k, env0 + (uint32_t)b, STREAM_PLAN, 0u, seed_lo, seed_hi);
-    const Philox p1 = philox4x32(2u * (uint32_t)k + 1u, env0 + (uint32_t)b, STREAM_PLAN, 0u, seed_lo, seed_hi);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float line = mpx_fma(s, qg[j] - qs[j], qs[j]);
-      L[j] = t == 0 ? qs[j] : t == T - 1 ? qg[j] : line;
-      const float u = u01(j < 4 ? p0.c[j] : p1.c[j - 4]);
-      const float delta = (opt.spread * mpx_fma(2.0f, u, -1.0f)) * ((hi[j] - lo[j]) * 0.5f);
-      const float moved = fminf(fmaxf(mpx_fma(bump, delta, L[j]), lo[j]), hi[j]);
-      q[j] = (k == 0 || t == 0 || t == T - 1) ? L[j] : moved;
-    }
-  }
+  plan_candidate(k, t, T, env0 + (uint32_t)b, seed_lo, seed_hi, opt.spread, qs, qg, lo, hi, L, q);
   const bool interior = lane >= 1 && lane <= n;
 
   // ---- covariant gradient descent ------------------------------------------------------------------------------------------
@@ -227,14 +191,7 @@ __global__ void __launch_bounds__(64 * MAXK)
                 cylinder_sdf_grad_local(px, py, pz, row[12], row[13], l0, l1, l2);
               sdf_grad_to_world(row, l0, l1, l2, nx, ny, nz);
               nx *= cp, ny *= cp, nz *= cp;
-#pragma unroll
-              for (int j = 0; j < nj; ++j) {
-                const float rx = x - o[j][0], ry = y - o[j][1], rz = zz - o[j][2];
-                const float cx = mpx_fma(z[j][1], rz, -(z[j][2] * ry));
-                const float cy = mpx_fma(z[j][2], rx, -(z[j][0] * rz));
-                const float cz = mpx_fma(z[j][0], ry, -(z[j][1] * rx));
-                g[j] += mpx_fma(nz, cz, mpx_fma(ny, cy, nx * cx));
-              }
+              plan_joint_terms<nj>(o, z, x, y, zz, nx, ny, nz, g);
             }
           }
         }
@@ -247,20 +204,8 @@ __global__ void __launch_bounds__(64 * MAXK)
     // two barriers per ~20 k instructions of an iteration.  The looser form is unmeasured.)
     __syncthreads();
     float acc[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (test_env) {
-      for (int u = 1; u <= n; ++u) {
-        const float m = Mtab[u * T + t];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) acc[j] = mpx_fma(m, buf[u * 7 + j], acc[j]);
-      }
-    }
-    if (interior) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const float dir = mpx_fma(opt.smooth_weight, q[j] - L[j], acc[j]);
-        q[j] = fminf(fmaxf(mpx_fma(-opt.step, dir, q[j]), lo[j]), hi[j]);
-      }
-    }
+    if (test_env) plan_metric_product(Mtab, buf, T, n, t, acc);
+    if (interior) plan_update(opt.step, opt.smooth_weight, acc, L, lo, hi, q);
     __syncthreads();  // (the next iteration overwrites buf)
   }
 
@@ -268,33 +213,14 @@ __global__ void __launch_bounds__(64 * MAXK)
 #pragma unroll
   for (int j = 0; j < 7; ++j) buf[lane * 7 + j] = q[j];
   __syncthreads();
-  int bits = 0;
-  if (lane + 3 < T) {
-    const float lim = opt.max_jerk * MPX_PLAN_JERK_SHARE;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float q0 = buf[lane * 7 + j], q1 = buf[(lane + 1) * 7 + j], q2 = buf[(lane + 2) * 7 + j],
-                  q3 = buf[(lane + 3) * 7 + j];
-      const float v0 = q1 - q0, v1 = q2 - q1, v2 = q3 - q2;
-      const float jerk = (v2 - v1) - (v1 - v0);
-      if (!(__builtin_fabsf(jerk) <= lim)) bits |= PLAN_BIT_JERK;
-    }
-  }
+  int bits = plan_jerk_bits(buf, lane, T, opt.max_jerk);
   if (test_env || test_self) {
     const int R = (T - 1) * opt.substeps + 1;
     for (int r0_ = 0; r0_ < R; r0_ += 64) {
       const int r = r0_ + lane;
       if (r < R) {
-        const int seg = r / opt.substeps, i = r - seg * opt.substeps;
         float qq[7];
-        if (i == 0) {
-#pragma unroll
-          for (int j = 0; j < 7; ++j) qq[j] = buf[seg * 7 + j];
-        } else {
-          const float f = (float)i / (float)opt.substeps;
-#pragma unroll
-          for (int j = 0; j < 7; ++j) qq[j] = mpx_fma(f, buf[(seg + 1) * 7 + j] - buf[seg * 7 + j], buf[seg * 7 + j]);
-        }
+        plan_refined(buf, r, opt.substeps, qq);
         bits |= plan_config_bits(qq, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin);
       }
     }

@@ -38,6 +38,10 @@ PROTOTYPES = {
     "mpx_trajectory_metrics": [P, P, P, P, I, I, F, P, P, P, P, P, P, P],
     "mpx_franka_ik": [P, I, F, P, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P],
     "mpx_franka_plan": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P],
+    "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
+    "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
+    "mpx_franka_plan_cloud_scratch": [I, I, I, I],
+    "mpx_franka_plan_cloud": [P, P, I, I, F, P, P, P, P, I, P, P, P, L, I, I, P, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, L, P],
     "mpx_collision_hinge": [P, L, I, I, I, P, P, I, P, P, P, I, F, P, P, L, I, P],
     "mpx_point_match": [P, P, I, I, F, F, P, P, P],
     "mpx_franka_cloud_grad": [P, I, F, P, P, P, I, P, L, I, P, P],
@@ -115,7 +119,7 @@ PROTOTYPES = {
     "mpx_rollout_step": [P, P, P, I, P, P, I, P, P, P, L, P],
     "mpx_rollout": [P, P, P, P, I, P, P, I, P, P, P, L, P],
 }
-RESTYPES = {"mpx_last_error": c_char_p, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
+RESTYPES = {"mpx_last_error": c_char_p, "mpx_franka_plan_cloud_scratch": c_int64, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
             "mpx_linear_wgrad_scratch": c_int64, "mpx_pool_wgrad_scratch": c_int64, "mpx_linear_workspace": c_int64, "mpx_policy_workspace": c_int64, "mpx_rollout_workspace": c_int64}
 
 
@@ -130,6 +134,11 @@ class PlanOptions(ctypes.Structure):
     _fields_ = [("candidates", c_int), ("iterations", c_int), ("step", c_float), ("smooth_weight", c_float),
                 ("epsilon", c_float), ("spread", c_float), ("substeps", c_int), ("check_margin", c_float),
                 ("clearance", c_float), ("max_jerk", c_float), ("check_self", c_int)]
+
+
+class FieldGrid(ctypes.Structure):
+    """``mpx_field_grid`` (include/mpinets_hip.h): one grid of distance-field nodes for a whole batch."""
+    _fields_ = [("lo", c_float * 3), ("h", c_float), ("nx", c_int), ("ny", c_int), ("nz", c_int), ("trunc", c_float)]
 
 
 _lib: Optional[ctypes.CDLL] = None

@@ -238,6 +238,92 @@ def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylin
     return (traj, status, choice, all_traj, all_status) if return_all else (traj, status)
 
 
+PLAN_CLOUD_SCRATCH_BYTES = 256 << 20  # ``franka_plan_cloud`` runs a large batch in slabs of problems whose scratch stays below this
+_plan_cloud_scratch: dict = {}
+
+
+def plan_cloud_truncation(point_radius: float = 0.0, clearance: float = 0.0, epsilon: float = PLAN_DEFAULTS["epsilon"],
+                          voxel: float = 0.03, with_base_link: bool = False) -> float:
+    """The truncation ``franka_plan_cloud`` builds its field with: the largest sphere radius + ``point_radius`` +
+    ``clearance`` + ``epsilon`` is the farthest a sphere centre can be from a point and still be repelled; two more cells
+    keep every corner of a cell inside that band below saturation."""
+    rmax = float(ft.collision_sphere_table(with_base_link)[1].max())
+    return rmax + float(point_radius) + max(float(clearance), 0.0) + float(epsilon) + 2.0 * float(voxel)
+
+
+def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                      field=None, point_radius: float = 0.0, T: int = 50, seed: int = 0, env_offset: int = 0,
+                      return_all: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                      finger: float = ft.FINGER_OPENING, **options):
+    """``franka_plan`` against one POINT CLOUD per environment instead of primitives (csrc/cloud_field.hip): the same
+    candidates, metric, jerk and self tests and lowest-valid-candidate rule.  The obstacle term of an iteration reads a
+    truncated distance field of the cloud (``field.CloudField``, built here when ``field`` is None); whether a candidate is
+    free is decided by ``FrankaCollisionSampler.check_cloud``'s kernel on its refined configurations, with this
+    ``point_radius`` and ``clearance + check_margin`` -- the field steers, the exact test judges.
+
+    :param cloud: [B,N,3] or [B,N,4] float32 on the GPU, any view whose last stride is 1 (``xyz[:, 2048:6144, :3]`` of the
+        slab is read in place); ``counts`` optional int [B] as for ``check_cloud``
+    :param field: a ``CloudField`` of this cloud (batch B), or None: one is built on the default grid with
+        ``plan_cloud_truncation(point_radius, clearance, epsilon, voxel)``
+    :param point_radius: radius given to every point (>= 0), in the cost and in the validity test
+    :returns: what ``franka_plan`` returns.  A batch whose scratch would exceed ``PLAN_CLOUD_SCRATCH_BYTES`` runs in slabs
+        of problems (the draws are keyed by the global row: the result does not depend on the slabbing)."""
+    from .field import DEFAULT_VOXEL, CloudField, cloud_operand
+
+    _lib.require_cuda(q_start, q_goal, cloud, counts)
+    assert q_start.ndim == 2 and q_start.size(1) == 7 and q_goal.shape == q_start.shape
+    B, dev = q_start.size(0), q_start.device
+    qs, qg = _lib.f32c(q_start), _lib.f32c(q_goal)
+    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
+    assert lim.shape == (7, 2)
+    unknown = set(options) - set(PLAN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"franka_plan_cloud: unknown option(s) {sorted(unknown)}")
+    o = dict(PLAN_DEFAULTS, **options)
+    copt = _lib.PlanOptions(int(o["candidates"]), int(o["iterations"]), float(o["step"]), float(o["smooth_weight"]),
+                            float(o["epsilon"]), float(o["spread"]), int(o["substeps"]), float(o["check_margin"]),
+                            float(o["clearance"]), float(o["max_jerk"]), int(bool(o["check_self"])))
+    N, cbs, cps = cloud_operand("franka_plan_cloud", cloud, B)
+    cn = None
+    if counts is not None:
+        assert counts.shape == (B,)
+        cn = _lib.i32c(counts)
+    if field is None:
+        field = CloudField.build(cloud, cn, truncation=plan_cloud_truncation(point_radius, o["clearance"], o["epsilon"],
+                                                                            DEFAULT_VOXEL, with_base_link))
+    _lib.require_cuda(field.values)
+    if field.values.size(0) != B or not field.values.is_contiguous():
+        raise _lib.MpxError(f"franka_plan_cloud: the field holds {field.values.size(0)} environments, the batch {B}")
+    sc, sr, sl = _ik_sphere_table(dev, with_base_link)
+    S = int(sc.size(0))
+    K = max(int(o["candidates"]), 0)
+    traj = torch.empty((B, T, 7), dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    choice = torch.empty(B, dtype=torch.int32, device=dev) if return_all else None
+    all_traj = torch.empty((B, K, T, 7), dtype=torch.float32, device=dev) if return_all else None
+    all_status = torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None
+    lib = _lib.load()
+    per = int(lib.mpx_franka_plan_cloud_scratch(1, int(T), K, int(o["substeps"])))
+    slab = max(B, 1) if per <= 0 else max(1, min(max(B, 1), PLAN_CLOUD_SCRATCH_BYTES // per))  # (per <= 0: the call refuses)
+    nodes = field.values[0].numel() if B else 0
+    for b0 in range(0, max(B, 1), slab):
+        n = min(slab, B - b0)
+        nbytes = max(int(lib.mpx_franka_plan_cloud_scratch(n, int(T), K, int(o["substeps"]))), 0)
+        buf = _plan_cloud_scratch.get(dev.index)
+        if buf is None or buf.numel() < nbytes:
+            buf = _plan_cloud_scratch[dev.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+
+        def at(t, row):  # pointer to row b0 of a [B, ...] operand
+            return None if t is None else t.data_ptr() + b0 * row * t.element_size()
+
+        _lib.call("mpx_franka_plan_cloud", at(qs, 7), at(qg, 7), n, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
+                  _lib.ptr(sr), _lib.ptr(sl), S, at(field.values, nodes), ctypes.byref(field.grid), at(cloud, cbs), cbs, cps, N,
+                  at(cn, 1), float(point_radius), ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset) + b0,
+                  at(traj, T * 7), at(status, 1), at(choice, 1), at(all_traj, K * T * 7), at(all_status, K), _lib.ptr(buf),
+                  nbytes)
+    return (traj, status, choice, all_traj, all_status) if return_all else (traj, status)
+
+
 def frames_to_matrix(frames: torch.Tensor) -> torch.Tensor:
     """[...,12] -> [...,4,4]."""
     m = torch.zeros(frames.shape[:-1] + (4, 4), dtype=frames.dtype, device=frames.device)

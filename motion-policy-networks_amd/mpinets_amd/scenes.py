@@ -287,6 +287,20 @@ def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
     return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
 
 
+EXPERT_CLOUD_POINT_RADIUS = 0.02  # [m] about half the spacing of 4096 points on a scene's surfaces
+
+
+def _expert_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
+                               seed: int, env_offset: int, point_radius: float) -> Dict[str, torch.Tensor]:
+    """``expert_from="cloud"``: the demonstration is planned against the batch's own scene cloud (a view of the slab),
+    with ``robot.franka_plan_cloud``; valid means free by ``FrankaCollisionSampler.check_cloud`` at ``point_radius``."""
+    from .robot import franka_plan_cloud
+
+    traj, status = franka_plan_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH, seed=seed,
+                                     env_offset=env_offset)
+    return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
+
+
 _DATASET_KEYS = {"cuboid_dims": "cuboid_dims", "cuboid_centers": "cuboid_centers", "cuboid_quats": "cuboid_quaternions",
                  "cylinder_radii": "cylinder_radii", "cylinder_heights": "cylinder_heights",
                  "cylinder_centers": "cylinder_centers", "cylinder_quats": "cylinder_quaternions"}
@@ -307,7 +321,8 @@ def problems_to_dataset(prob: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
 def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop",), M1: int = 16, M2: int = 16,
                        scene_pool: Optional[int] = None, device_clouds: bool = False, env_offset: int = 0,
                        total_envs: Optional[int] = None, collision_free: bool = False,
-                       max_redraws: int = 4, expert: bool = False) -> Dict[str, torch.Tensor]:
+                       max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
+                       expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS) -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -328,10 +343,15 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     ``expert`` (with ``collision_free``): also plans a demonstration from ``q`` to ``q_goal`` with ``robot.franka_plan``
     (a local optimiser standing in for the reference's AIT* + Geometric Fabrics; valid by this engine's sphere model):
     ``global_solutions`` [B,50,7] and ``expert_valid`` = ``valid`` & planned (bool [B]); the other rows are NaN.  The
-    candidate draws are keyed by the global row, so shards agree."""
+    candidate draws are keyed by the global row, so shards agree.  ``expert_from="cloud"`` plans against the batch's own
+    scene cloud (the scene rows of ``xyz``) with ``robot.franka_plan_cloud`` at ``expert_point_radius`` instead of against
+    the primitives: what a depth or captured cloud, which has no primitives, allows.  Valid then means free by
+    ``FrankaCollisionSampler.check_cloud`` at that radius, which is not the primitive test."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
+    if expert_from not in ("primitives", "cloud"):
+        raise ValueError(f"expert_from must be 'primitives' or 'cloud', got {expert_from!r}")
 
     dev = torch.device(device)
     total = env_offset + B if total_envs is None else int(total_envs)
@@ -348,7 +368,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if collision_free:
         q, q_target, q_goal, valid = _collision_free_problems(out, q, q_target, seed, env_offset, max_redraws)
         out.update(q_goal=q_goal, valid=valid)
-        if expert:
+        if expert and expert_from == "primitives":
             out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset))
     state = np.random.get_state()
     np.random.seed(seed)
@@ -364,6 +384,9 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                             env_offset=env_offset)
     else:
         xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3] = torch.from_numpy(cloud[sid]).to(dev)
+    if expert and expert_from == "cloud":
+        scene_cloud = xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3]
+        out.update(_expert_trajectories_cloud(scene_cloud, q, q_goal, valid, seed, env_offset, expert_point_radius))
     target_pose = frames_to_matrix(franka_fk(q_target)[:, ft.LINK_ID["right_gripper"]])
     xyz[:, NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS:, :3] = sampler.sample_end_effector(target_pose, NUM_TARGET_POINTS)
     np.random.set_state(state)

@@ -1,0 +1,198 @@
+"""CPU: the restatement of the distance field (tests/float64_cloud_field.py) stands on its own -- the cases of the GPU
+test cover what they claim, the banded rule holds for a correctly rounded evaluation of the float64 minimum, the
+sampler's gradient is the derivative of its value, the bars of the GPU sample test are derived here -- and
+``mpx_cloud_field_build`` / ``mpx_cloud_field_sample`` refuse bad arguments on the host, before any launch."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import float64_cloud_field as fcf  # noqa: E402
+
+
+def test_cases_cover_what_the_issue_lists():
+    cases = fcf.BUILD_CASES
+    assert {c[0] for c in cases} == {1, 3}
+    assert {c[1] for c in cases} == {0, 1, fcf.TILE - 1, fcf.TILE, fcf.TILE + 1, 2 * fcf.TILE + 3}
+    assert {c[2] for c in cases} == set(range(len(fcf.GRIDS))) and fcf.GRIDS == [(2, 2, 2), (9, 8, 5), (17, 3, 2), (33, 9, 6)]
+    assert {c[3] for c in cases} == {"small", "large"}
+    assert {e for c in cases for e in c[4]} == {"counts", "bad", "empty", "slab", "far"}
+    assert len({fcf.case_id(c) for c in cases}) == len(cases)
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mpinets_hip.h")).read()
+    assert int(re.search(r"#define MPX_CLOUD_TILE\s+(\d+)", text).group(1)) == fcf.TILE
+    assert int(re.search(r"#define MPX_FIELD_BRICK\s+(\d+)", text).group(1)) == fcf.BRICK
+
+
+@pytest.mark.parametrize("case", fcf.BUILD_CASES, ids=fcf.case_id)
+def test_restatement_passes_its_own_banded_rule(case):
+    """float32(sqrt(d2min)) cut at trunc -- what a device with an exact d2 returns -- is inside the bands; the cases have
+    nodes on both sides of trunc where they claim to, and an unusable environment is trunc everywhere."""
+    cloud, counts, grid = fcf.make_build_case(case)
+    B, N, g, tr, extras = case
+    d2 = fcf.build_restate(cloud, counts, grid)
+    assert d2.shape == (B, grid["nz"], grid["ny"], grid["nx"])
+    field = fcf.field_from_d2(d2, grid["trunc"])
+    below, above, mid = fcf.check_field(field, d2, grid["trunc"])
+    x, y, z = fcf.node_coordinates(grid)
+    diag = np.linalg.norm([float(x[-1] - x[0]), float(y[-1] - y[0]), float(z[-1] - z[0])])
+    assert (float(grid["trunc"]) < diag) == (tr == "small")
+    if N == 0 or "empty" in extras:
+        assert np.isinf(d2[0]).all() and (field[0] == grid["trunc"]).all()
+    if N >= fcf.TILE - 1 and tr == "small" and "empty" not in extras:
+        assert below > 0
+    if "bad" in extras:
+        assert (~np.isfinite(cloud)).any()
+    if "far" in extras:
+        assert (np.abs(cloud[np.isfinite(cloud)]) > 20).any()
+
+
+def test_exact_cases():
+    """Rows placed on node coordinates give 0 there; a single point at a 3-4-5 offset scaled by a power of two gives the
+    exact distance (every product and sum is exact in float32)."""
+    grid = fcf.make_grid((9, 8, 5), trunc=10.0)
+    x, y, z = fcf.node_coordinates(grid)
+    cloud = np.array([[[x[3], y[7], z[4]], [x[8], y[0], z[0]]]], np.float32)
+    d2 = fcf.build_restate(cloud, None, grid)
+    assert d2[0, 4, 7, 3] == 0.0 and d2[0, 0, 0, 8] == 0.0 and (d2 > 0).sum() == d2.size - 2
+    s = np.float32(2.0 ** -5)
+    p = np.array([[[x[2] + 3 * s, y[3] - 4 * s, z[1]]]], np.float32)
+    d2 = fcf.build_restate(p, None, grid)
+    assert d2[0, 1, 3, 2] == float(25 * s * s) and np.sqrt(d2[0, 1, 3, 2]) == float(5 * s)
+
+
+def test_fast_build_agrees_with_the_restatement():
+    cloud, counts, grid = fcf.make_build_case(fcf.BUILD_CASES[6])
+    exact = fcf.field_from_d2(fcf.build_restate(cloud, counts, grid), grid["trunc"])
+    assert np.abs(fcf.build_fast(cloud, counts, grid).astype(np.float64) - exact).max() < 1e-6
+
+
+def _host_sample_case():
+    grid, cloud, pts = fcf.make_sample_case()
+    field = fcf.field_from_d2(fcf.build_restate(cloud, None, grid), grid["trunc"])
+    return grid, field, pts
+
+
+def test_sampler_on_nodes_outside_and_at_the_last_node():
+    """In float32 with emulated fmas: a sample on a node (fractions 0) returns the node's value bit for bit; u == n - 1 is
+    inside; outside the grid, NaN and infinite coordinates give trunc and a zero gradient."""
+    grid, field, pts = _host_sample_case()
+    x, y, z = fcf.node_coordinates(grid)
+    Z, Y, X = np.meshgrid(z[:-1], y[:-1], x[:-1], indexing="ij")
+    nodes = np.broadcast_to(np.stack([X, Y, Z], -1).reshape(1, -1, 3), (field.shape[0], X.size, 3)).astype(np.float32)
+    d, g, inside = fcf.sample(field, grid, nodes, torch.float32)
+    assert bool(inside.all()) and np.array_equal(d.numpy().reshape(field.shape[0], *X.shape), field[:, :-1, :-1, :-1])
+    d, g, inside = fcf.sample(field, grid, pts, torch.float32)
+    trunc = float(grid["trunc"])
+    for row in (0, 1, 4):
+        assert not bool(inside[:, row].any()) and bool((d[:, row] == trunc).all()) and bool((g[:, row] == 0).all())
+    assert bool(inside[:, 2].all()) and bool(inside[:, 3].all())
+    assert np.allclose(d[:, 2].numpy(), field[:, -1, -1, -1], rtol=0, atol=1e-7)
+    assert np.allclose(d[:, 3].numpy(), field[:, 0, 0, -1], rtol=0, atol=1e-7)
+    share_outside = 1 - float(inside.float().mean())
+    assert 0.2 < share_outside < 0.6
+
+
+def test_sampler_gradient_is_the_derivative_of_its_value():
+    """Central differences of the float64 interpolant inside one cell: the interpolant is trilinear, so a difference that
+    stays inside the cell is exact to rounding."""
+    grid, field, pts = _host_sample_case()
+    d, g, inside, near = fcf.sample(field, grid, pts, torch.float64, want_face=True)
+    h = 1e-4 * float(grid["h"])
+    u = (pts.astype(np.float64) - grid["lo"].astype(np.float64)) / float(grid["h"])
+    with np.errstate(invalid="ignore"):
+        keep = inside.numpy() & (np.abs(u - np.round(u)) > 1e-3).all(-1)
+    assert keep.mean() > 0.3
+    p64 = torch.from_numpy(pts.astype(np.float64))
+    import float64_cloud_plan as fcp
+    for a in range(3):
+        e = torch.zeros(3, dtype=torch.float64)
+        e[a] = h
+        dp = fcp._sample_any(field, grid, p64 + e, torch.float64)[0]
+        dm = fcp._sample_any(field, grid, p64 - e, torch.float64)[0]
+        num = ((dp - dm) / (2 * h)).numpy()
+        assert np.abs(num - g[..., a].numpy())[keep].max() < 1e-7
+
+
+# what the bars of tests/test_gpu_cloud_field.py's interior-sample test are 4x of (recorded on the CPU)
+SAMPLE_DIST_REFERENCE = 5.9e-8  # [m]
+SAMPLE_GRAD_REFERENCE = 1.2e-6  # [1] (a value difference of 7e-8 m over a 6.25 cm cell)
+
+
+def sample_reference_difference():
+    grid, field, pts = _host_sample_case()
+    d64, g64, inside, near = fcf.sample(field, grid, pts, torch.float64, want_face=True)
+    d32, g32, inside32 = fcf.sample(field, grid, pts, torch.float32)
+    both = inside & inside32
+    dd = float((d64 - d32.double()).abs()[both].max())
+    dg = float((g64 - g32.double()).abs().amax(-1)[both & ~near].max())
+    return dd, dg, float(near.float().mean()), float(both.float().mean())
+
+
+def test_sample_bars_can_be_derived_again():
+    """Reference against reference on the inputs of the GPU sample test: the float32 run of the restated sampler against
+    the float64 run from the same float32 field and points.  The GPU bars are 4x the recorded figures; here the
+    measurement is repeated and must land within a factor 2 of them.  The share of samples within 1e-5 cells of a face
+    stays under the cap.  Measured: dist 5.93e-8 m, grad 1.17e-6, 0.05 % of the samples near a face, 58 % inside."""
+    dd, dg, near, both = sample_reference_difference()
+    print(f"sampler, float32 vs float64 restatement: dist {dd:.3e} m, grad {dg:.3e}, near a face {near:.5f}, inside {both:.3f}")
+    assert near <= fcf.FACE_CAP
+    assert SAMPLE_DIST_REFERENCE / 2 <= dd <= SAMPLE_DIST_REFERENCE * 2
+    assert SAMPLE_GRAD_REFERENCE / 2 <= dg <= SAMPLE_GRAD_REFERENCE * 2
+
+
+def _grid(**kw):
+    from mpinets_amd import _lib
+
+    g = dict(lo=(0.0, 0.0, 0.0), h=0.1, nx=4, ny=4, nz=4, trunc=0.2)
+    g.update(kw)
+    return _lib.FieldGrid((ctypes.c_float * 3)(*g["lo"]), g["h"], g["nx"], g["ny"], g["nz"], g["trunc"])
+
+
+def test_bad_arguments_are_refused_on_the_host():
+    from mpinets_amd import _lib
+
+    lib = _lib.load()
+    assert lib.mpx_version() == 340
+    one = ctypes.c_void_p(256)  # any non-NULL "device pointer": validation fails before it is touched
+
+    def build(grid=None, B=2, N=8, stride=3, cloud=one, field=one):
+        g = _grid() if grid is None else grid
+        return lib.mpx_cloud_field_build(cloud, 24, stride, N, None, B, ctypes.byref(g) if g is not False else None, field, None)
+
+    def sample(grid=None, B=2, P=8, stride=3, dist=one):
+        g = _grid() if grid is None else grid
+        return lib.mpx_cloud_field_sample(one, ctypes.byref(g), B, one, 24, stride, P, dist, None, None)
+
+    for call in (build, sample):
+        for bad, word in ((dict(h=0.0), b"spacing"), (dict(h=float("nan")), b"spacing"), (dict(trunc=0.0), b"trunc"),
+                          (dict(trunc=float("inf")), b"trunc"), (dict(nx=1), b"nodes"), (dict(nz=1025), b"nodes"),
+                          (dict(nx=1024, ny=1024, nz=17), b"in all"), (dict(lo=(0.0, float("nan"), 0.0)), b"lo")):
+            assert call(grid=_grid(**bad)) != 0 and word in lib.mpx_last_error(), bad
+        assert call(stride=2) != 0 and b"stride" in lib.mpx_last_error()
+        assert call(B=-1) != 0 and b"negative" in lib.mpx_last_error()
+    assert build(grid=False) != 0 and b"NULL grid" in lib.mpx_last_error()
+    assert build(field=None) != 0 and b"NULL operand" in lib.mpx_last_error()
+    assert build(cloud=None) != 0 and b"NULL operand" in lib.mpx_last_error()
+    assert sample(dist=None) != 0 and b"NULL operand" in lib.mpx_last_error()
+    assert build(B=0, field=None, cloud=None) == 0 and sample(B=0, dist=None) == 0  # nothing to do, nothing touched
+    assert build(grid=_grid(nx=1024, ny=1024, nz=16), B=0) == 0  # exactly MPX_FIELD_MAX_NODES is allowed
+
+
+def test_python_entry_points_refuse_cpu_tensors():
+    from mpinets_amd import _lib
+    from mpinets_amd.field import CloudField, make_grid
+
+    with pytest.raises(_lib.MpxError):
+        CloudField.build(torch.zeros(1, 8, 3))
+    g = make_grid((-0.9, -0.9, -0.3), (0.9, 0.9, 1.2), 0.03, 0.2)
+    assert (g.nx, g.ny, g.nz) == (61, 61, 51)
+    with pytest.raises(_lib.MpxError):
+        CloudField(torch.zeros(1, 51, 61, 61), g).sample(torch.zeros(1, 4, 3))
+    import float64_cloud_plan as fcp
+    ref = fcp.default_grid(0.2)
+    assert (ref["nx"], ref["ny"], ref["nz"]) == (g.nx, g.ny, g.nz) and float(ref["h"]) == g.h
