@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_cloud_field_build,
+int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_franka_cloud_collision_each,
+                          mpx_franka_ik_cloud, mpx_franka_ik_cloud_scratch; 340 (unchanged, likewise): mpx_cloud_field_build,
                           mpx_cloud_field_sample, mpx_franka_plan_cloud, mpx_franka_plan_cloud_scratch, struct mpx_field_grid;
                           340 (unchanged, likewise): mpx_cloud_clean,
                           mpx_cloud_clean_scratch; 340 (unchanged, likewise): mpx_franka_cloud_collision,
@@ -136,6 +137,24 @@ int mpx_franka_cloud_collision(const float *q, int B, int T, float finger, const
                                float point_radius, float clearance, int32_t *flags, float *min_dist,
                                int32_t *nearest, mpx_stream_t stream);
 
+/* The same check with ONE VERDICT PER WAYPOINT: hit int32 [B,T] is WRITTEN (not OR-ed), every entry exactly once, 1 or 0.
+ * hit[b,t] = 1 exactly when mpx_franka_cloud_collision, called on the single configuration q[b,t] (B = 1, T = 1) against
+ * environment b's cloud with the same strides, counts[b], point_radius and clearance, would set its flag: the same
+ * centres, the same d2, the same R = (sph_radii[s] + point_radius) + clearance and d2 <= R*R, non-finite points never hit.
+ *   active int32 [B,T] (optional; NULL: every waypoint is tested): a waypoint with active[b,t] == 0 is not tested -- its q
+ *   is not even read -- and gets hit = 0.
+ *   N == 0, counts[b] <= 0 or S == 0 writes zeros; B == 0 or T == 0 launches nothing.  Refused: what
+ *   mpx_franka_cloud_collision refuses, and hit == NULL.  No allocation, no global atomics.
+ * The same kernel template: a workgroup takes MPX_CLOUD_TC waypoints of one environment; with MPX_VARIANT_CLOUD_CULL the
+ * box is that of the ACTIVE waypoints' spheres and the workgroup stops after a tile once every active waypoint of its
+ * chunk has a hit (not at the first hit).  The verdicts depend on the inputs alone: not on the launch shape, the variant
+ * or the order in which points are staged.                                                                            */
+int mpx_franka_cloud_collision_each(const float *q, int B, int T, float finger, const float *sph_centers,
+                                    const float *sph_radii, const int32_t *sph_link, int S, const float *cloud,
+                                    int64_t cloud_batch_stride, int cloud_point_stride, int N, const int32_t *counts,
+                                    float point_radius, float clearance, const int32_t *active, int32_t *hit,
+                                    mpx_stream_t stream);
+
 /* rollout joint update, model.py:171-173 + utils.py:207-209:
  *   q_norm_out = clamp(q_norm + dq, -1, 1);  q_out = (q_norm_out + 1) * (hi - lo) / 2 + lo
  * limits [7,2] device; either output may alias q_norm; environments with frozen[b] != 0
@@ -207,6 +226,31 @@ int mpx_franka_ik(const float *target_poses, int B, float finger, const float *l
                   const float *cyl_radii, const float *cyl_heights, int M2, const mpx_ik_options *options,
                   uint64_t seed, int64_t env_offset, float *q_out, int32_t *status, float *all_q,
                   int32_t *all_status, mpx_stream_t stream);
+
+/* mpx_franka_ik against one POINT CLOUD per environment: the lowest start that converges and is free of the cloud (and,
+ * with check_self, of the robot itself).  The starts, the iterations, the acceptance test and the self bit are
+ * mpx_franka_ik's -- its kernel runs, without primitives -- so for the same targets, limits, q_init, options, seed and
+ * env_offset every start's final q and its bits 0 and 2 are bit-equal to what mpx_franka_ik returns in all_q / all_status.
+ *   Bit 1 of a converged start is mpx_franka_cloud_collision_each's verdict on that start's q against environment b's
+ *   cloud (addressed, trimmed by counts and inflated by point_radius exactly as there), with clearance =
+ *   options->clearance; it is 0 on every start that did not converge (those are not tested: `active` = converged).  The
+ *   result is the LOWEST start whose bits equal 1.
+ *   q_out, status, NaN rows, all_q and all_status: as for mpx_franka_ik.  Every converged start is tested whether or not
+ *   all_status is passed (the cloud kernel's own stop -- every active start of a chunk has hit -- is the only one), so
+ *   q_out and status cannot depend on it.
+ *   cloud == NULL or N == 0: no environment test (S may then be 0).  Refused: N > 0 with S == 0, point_radius < 0, a point
+ *   stride below 3, a scratch that is NULL (B > 0), smaller than mpx_franka_ik_cloud_scratch(B) or not 16-byte aligned,
+ *   and what mpx_franka_ik and mpx_franka_cloud_collision_each refuse.  No allocation; everything is enqueued on `stream`;
+ *   B == 0 launches nothing.
+ *   scratch: mpx_franka_ik_cloud_scratch(B) = B * 64 * (7 + 3) * 4 bytes (every start's q, bits, active flag, verdict);
+ *   -1 for B < 0.                                                                                                    */
+int64_t mpx_franka_ik_cloud_scratch(int B);
+int mpx_franka_ik_cloud(const float *target_poses, int B, float finger, const float *limits, const float *q_init,
+                        const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                        const float *cloud, int64_t cloud_batch_stride, int cloud_point_stride, int N, const int32_t *counts,
+                        float point_radius, const mpx_ik_options *options, uint64_t seed, int64_t env_offset,
+                        float *q_out, int32_t *status, float *all_q, int32_t *all_status,
+                        void *scratch, int64_t scratch_bytes, mpx_stream_t stream);
 
 /* Batched collision-free trajectory planning between two configurations (what the reference's data generator asks of OMPL
  * AIT* + Geometric Fabrics and then filters with verify_trajectory, data_pipeline/gen_data.py:106-153, 396-430).  This is a

@@ -18,6 +18,11 @@
 // is a hit: with clearance 0 exactly mpx_franka_collision's test), then the body-cylinder self test of
 // trajectory_metrics_kernel (franka.hip).  The first candidate without a hit is the result: "the lowest seed that
 // converges and is free".
+//
+// Against a point cloud (mpx_franka_ik_cloud, at the end of this file): the same kernel without primitives, every start's
+// q and bits kept; the per-waypoint cloud check of cloud_collision.hip on the [B,64,7] starts with `active` = converged
+// (a self-hit start is tested too: with all_status every converged start carries both bits); then a select kernel, one wave per problem, that folds the verdicts into bit 1 and picks the lowest start
+// whose bits equal 1.
 #include "common.h"
 #include "sdf_device.h"
 #include "philox.h"
@@ -311,4 +316,83 @@ MPX_EXPORT int mpx_franka_ik(const float *target_poses, int B, float finger, con
                      cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, q_out, status,
                      all_q, all_status);
   MPX_LAUNCH_CHECK("mpx_franka_ik");
+}
+
+// ---- against a point cloud ------------------------------------------------------------------------------------------------------
+// scratch: all_q [B,64,7] float, all_status [B,64], active [B,64], hit [B,64] int32 (the first two unused when the caller
+// passes its own)
+constexpr int64_t IK_CLOUD_WORDS_PER_PROBLEM = MPX_IK_SEEDS * (7 + 3);
+
+__global__ void __launch_bounds__(256)
+    franka_ik_cloud_active_kernel(const int32_t *__restrict__ all_status, int64_t n, int32_t *__restrict__ active) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) active[i] = all_status[i] & 1;  // converged: the starts that carry a cloud verdict
+}
+
+// one wave per problem, lane = start: bit 1 from the cloud verdicts, the lowest start with bits == 1, NaN row otherwise
+__global__ void __launch_bounds__(256)
+    franka_ik_cloud_select_kernel(int B, const float *__restrict__ all_q, const int32_t *__restrict__ bits_in,
+                                  const int32_t *__restrict__ hit, float *__restrict__ q_out, int32_t *__restrict__ status,
+                                  int32_t *__restrict__ all_status) {
+  const int b = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+  if (b >= B) return;  // (wave-uniform)
+  const size_t i = (size_t)b * 64 + lane;
+  int bits = bits_in[i];
+  if (hit && (bits & 1) && hit[i] != 0) bits |= 2;
+  if (all_status) all_status[i] = bits;
+  const unsigned long long free = __builtin_amdgcn_ballot_w64(bits == 1), conv = __builtin_amdgcn_ballot_w64((bits & 1) != 0);
+  const int winner = free ? (int)__builtin_ctzll(free) : -1;
+  if (lane < 7) q_out[(size_t)b * 7 + lane] = winner >= 0 ? all_q[((size_t)b * 64 + winner) * 7 + lane] : __builtin_nanf("");
+  if (lane == 0) status[b] = winner >= 0 ? 0 : conv ? 1 : 2;
+}
+
+MPX_EXPORT int64_t mpx_franka_ik_cloud_scratch(int B) {
+  if (B < 0) return -1;
+  return (int64_t)B * IK_CLOUD_WORDS_PER_PROBLEM * 4;  // (2560 B: a multiple of 16)
+}
+
+MPX_EXPORT int mpx_franka_ik_cloud(const float *target_poses, int B, float finger, const float *limits, const float *q_init,
+                                   const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                                   const float *cloud, int64_t cloud_batch_stride, int cloud_point_stride, int N,
+                                   const int32_t *counts, float point_radius, const mpx_ik_options *options, uint64_t seed,
+                                   int64_t env_offset, float *q_out, int32_t *status, float *all_q, int32_t *all_status,
+                                   void *scratch, int64_t scratch_bytes, mpx_stream_t stream) {
+  const float clearance = options ? options->clearance : 0.0f;
+  // what the cloud check would refuse, before anything is launched
+  MPX_REQUIRE(B >= 0 && S >= 0 && N >= 0, "mpx_franka_ik_cloud: negative size");
+  MPX_REQUIRE(S <= MPX_IK_SEEDS, "mpx_franka_ik_cloud: S = %d collision spheres, at most %d", S, MPX_IK_SEEDS);
+  MPX_REQUIRE(point_radius >= 0.0f, "mpx_franka_ik_cloud: point_radius must be >= 0");
+  MPX_REQUIRE(clearance == clearance, "mpx_franka_ik_cloud: clearance is NaN");
+  MPX_REQUIRE(cloud_point_stride >= 3, "mpx_franka_ik_cloud: cloud_point_stride < 3");
+  MPX_REQUIRE((int64_t)B * MPX_IK_SEEDS < (int64_t)1 << 31, "mpx_franka_ik_cloud: B * 64 overflows int32");
+  const bool test_env = cloud != nullptr && N > 0;
+  MPX_REQUIRE(N == 0 || S > 0, "mpx_franka_ik_cloud: a cloud without collision spheres to test it with");
+  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_ik_cloud: S > 0 without the sphere table");
+  const int64_t need = mpx_franka_ik_cloud_scratch(B);
+  MPX_REQUIRE(scratch_bytes >= need, "mpx_franka_ik_cloud: scratch of %lld bytes, mpx_franka_ik_cloud_scratch(%d) = %lld",
+              (long long)scratch_bytes, B, (long long)need);
+  MPX_REQUIRE(B == 0 || (scratch && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0),
+              "mpx_franka_ik_cloud: scratch is NULL or not 16-byte aligned");
+  float *w_q = all_q ? all_q : static_cast<float *>(scratch);
+  int32_t *wi = static_cast<int32_t *>(scratch) + (size_t)B * MPX_IK_SEEDS * 7;
+  int32_t *w_bits = wi, *w_active = wi + (size_t)B * MPX_IK_SEEDS, *w_hit = wi + (size_t)2 * B * MPX_IK_SEEDS;
+  // the solver, no primitives: every start's q, bit 0 and (check_self) bit 2.  (Its q_out / status are written again below.)
+  if (mpx_franka_ik(target_poses, B, finger, limits, q_init, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                    nullptr, nullptr, 0, options, seed, env_offset, q_out, status, w_q, w_bits, stream))
+    return 1;
+  if (B == 0) return 0;
+  const int64_t n = (int64_t)B * MPX_IK_SEEDS;
+  hipStream_t st = mpx_s(stream);
+  if (test_env) {
+    hipLaunchKernelGGL(franka_ik_cloud_active_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, w_bits, n, w_active);
+    hipError_t e = hipGetLastError();
+    MPX_REQUIRE(e == hipSuccess, "mpx_franka_ik_cloud: launch failed: %s", hipGetErrorString(e));
+    if (mpx_franka_cloud_collision_each(w_q, B, MPX_IK_SEEDS, finger, sph_centers, sph_radii, sph_link, S, cloud,
+                                        cloud_batch_stride, cloud_point_stride, N, counts, point_radius, clearance, w_active,
+                                        w_hit, stream))
+      return 1;
+  }
+  hipLaunchKernelGGL(franka_ik_cloud_select_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, B, w_q, w_bits,
+                     test_env ? w_hit : nullptr, q_out, status, all_status);
+  MPX_LAUNCH_CHECK("mpx_franka_ik_cloud");
 }

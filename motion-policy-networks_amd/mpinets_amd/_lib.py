@@ -32,11 +32,14 @@ PROTOTYPES = {
     "mpx_franka_spheres": [P, I, F, P, P, I, P, P],
     "mpx_franka_collision": [P, I, I, F, P, P, P, I, P, P, I, P, P, P, I, P, P, P],
     "mpx_franka_cloud_collision": [P, I, I, F, P, P, P, I, P, L, I, I, P, F, F, P, P, P, P],
+    "mpx_franka_cloud_collision_each": [P, I, I, F, P, P, P, I, P, L, I, I, P, F, F, P, P, P],
     "mpx_draw_subset": [I, I, ctypes.c_uint64, I, P, P],
     "mpx_joint_step": [P, P, P, I, P, P, P, P],
     "mpx_franka_success": [P, P, I, F, F, F, P, P, P, P, P],
     "mpx_trajectory_metrics": [P, P, P, P, I, I, F, P, P, P, P, P, P, P],
     "mpx_franka_ik": [P, I, F, P, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P],
+    "mpx_franka_ik_cloud_scratch": [I],
+    "mpx_franka_ik_cloud": [P, I, F, P, P, P, P, P, I, P, L, I, I, P, F, P, ctypes.c_uint64, L, P, P, P, P, P, L, P],
     "mpx_franka_plan": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
@@ -119,7 +122,7 @@ PROTOTYPES = {
     "mpx_rollout_step": [P, P, P, I, P, P, I, P, P, P, L, P],
     "mpx_rollout": [P, P, P, P, I, P, P, I, P, P, P, L, P],
 }
-RESTYPES = {"mpx_last_error": c_char_p, "mpx_franka_plan_cloud_scratch": c_int64, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
+RESTYPES = {"mpx_last_error": c_char_p, "mpx_franka_ik_cloud_scratch": c_int64, "mpx_franka_plan_cloud_scratch": c_int64, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
             "mpx_linear_wgrad_scratch": c_int64, "mpx_pool_wgrad_scratch": c_int64, "mpx_linear_workspace": c_int64, "mpx_policy_workspace": c_int64, "mpx_rollout_workspace": c_int64}
 
 

@@ -164,3 +164,30 @@ def clean_point_cloud(xyz: np.ndarray, rgba: np.ndarray, **kw) -> Tuple[np.ndarr
     got, index = clean_point_clouds(cloud, kw.pop("num_points", 4096), return_index=True, **kw)
     index = index[0].cpu().numpy()
     return got[0].cpu().numpy(), np.asarray(rgba)[index]
+
+
+@torch.no_grad()
+def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torch.Tensor, *,
+                  counts: Optional[torch.Tensor] = None, point_radius: float = 0.0, T: int = 50, seed: int = 0,
+                  env_offset: int = 0, field=None, ik_options: Optional[dict] = None,
+                  plan_options: Optional[dict] = None) -> dict:
+    """From a cloud and a target pose to a checked trajectory: ``robot.franka_ik_cloud`` for the goal configuration, then
+    ``robot.franka_plan_cloud`` from ``q_start`` to it, both against the same ``cloud`` (``counts``, ``point_radius``).  The
+    optimiser-based counterpart of the reference demo's ``Planner.plan(q0, target_pose, obstacle_pc)``
+    (``interactive_demo/mpinets_ros/nodes/planning_node.py``), for a batch.
+
+    :param cloud: [B,N,3] or [B,N,4] float32 on the GPU (e.g. what ``clean_point_clouds`` returns, or the slab's scene rows)
+    :param q_start: [B,7];  :param target_poses: [B,4,4] right_gripper poses
+    :param field: a ``CloudField`` of the cloud for the planner, or None (built there)
+    :param ik_options, plan_options: keyword options of the two calls (``franka_ik_cloud`` / ``franka_plan_cloud``)
+    :returns: dict of ``q_goal`` [B,7] (NaN rows where ``ik_status`` != 0), ``ik_status`` int32 [B], ``trajectory``
+        [B,T,7] (NaN rows where ``plan_status`` != 0), ``plan_status`` int32 [B] -- 2 for every row without a goal: the
+        planner refuses a NaN endpoint -- and ``valid`` bool [B]: both statuses 0."""
+    from .robot import franka_ik_cloud, franka_plan_cloud
+
+    q_goal, ik_status = franka_ik_cloud(target_poses, cloud, counts, point_radius, seed=seed, env_offset=env_offset,
+                                        **(ik_options or {}))
+    traj, plan_status = franka_plan_cloud(q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T,
+                                          seed=seed, env_offset=env_offset, **(plan_options or {}))
+    return {"q_goal": q_goal, "ik_status": ik_status, "trajectory": traj, "plan_status": plan_status,
+            "valid": (ik_status == 0) & (plan_status == 0)}

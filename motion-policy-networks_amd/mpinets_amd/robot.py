@@ -68,15 +68,32 @@ class FrankaRobot:
 
     @classmethod
     def collision_free_ik(cls, pose, cuboids=None, cylinders=None, q_init=None, seed: int = 0,
-                          device: Union[str, torch.device] = "cuda:0", **options):
+                          device: Union[str, torch.device] = "cuda:0", cloud=None, counts=None, point_radius: float = 0.0,
+                          **options):
         """robofin's ``collision_free_ik(sim, arm, selfcc, pose, retries)`` for one pose: the lowest of 64 starts that
         reaches ``pose`` and is free of ``cuboids`` / ``cylinders`` (``geometry.TorchCuboids`` / ``TorchCylinders`` with a
         batch of one, standing in for the PyBullet ``sim`` / ``arm``) and of the self-collision model (``selfcc``:
         ``check_self=True`` here whether or not primitives are passed; ``check_self=False`` turns it off).  The result
-        satisfies ``cls.within_limits``.  Returns a numpy ``[7]`` or ``None``."""
+        satisfies ``cls.within_limits``.  Returns a numpy ``[7]`` or ``None``.
+
+        ``cloud`` (``[N,3]``, ``[N,4]`` or ``[1,N,.]``, numpy or tensor; ``counts`` and ``point_radius`` as for
+        ``franka_ik_cloud``) asks the same of a point cloud instead; a cloud together with primitives is a ``ValueError``."""
+        if cloud is not None and (cuboids is not None or cylinders is not None):
+            raise ValueError("collision_free_ik: pass primitives or a cloud, not both")
         m = np.asarray(getattr(pose, "matrix", pose), dtype=np.float32).reshape(1, 4, 4)
         dev = torch.device(device)
         qi = None if q_init is None else torch.as_tensor(np.asarray(q_init, dtype=np.float32)).reshape(1, 7).to(dev)
+        if cloud is not None:
+            pc = cloud if torch.is_tensor(cloud) else torch.from_numpy(np.ascontiguousarray(cloud, dtype=np.float32))
+            pc = pc.to(dev, dtype=torch.float32)
+            if pc.ndim == 2:
+                pc = pc.unsqueeze(0)
+            if pc.ndim != 3 or pc.size(0) != 1 or pc.size(2) not in (3, 4):
+                raise ValueError(f"collision_free_ik: cloud must be [N,3], [N,4] or [1,N,.], got {tuple(pc.shape)}")
+            cn = None if counts is None else torch.as_tensor(counts, dtype=torch.int32).reshape(1).to(dev)
+            q, status = franka_ik_cloud(torch.from_numpy(m).to(dev), pc, cn, point_radius, q_init=qi, limits=cls.JOINT_LIMITS,
+                                        seed=seed, **{"check_self": True, **options})
+            return q[0].cpu().numpy().astype(np.float64) if int(status[0]) == 0 else None
         q, status = franka_ik(torch.from_numpy(m).to(dev), cuboids, cylinders, q_init=qi, limits=cls.JOINT_LIMITS,
                               seed=seed, **{"check_self": True, **options})
         return q[0].cpu().numpy().astype(np.float64) if int(status[0]) == 0 else None
@@ -170,6 +187,66 @@ def franka_ik(target_poses: torch.Tensor, cuboids=None, cylinders=None, q_init: 
               _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
               ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(q), _lib.ptr(status),
               _lib.ptr(all_q), _lib.ptr(all_status))
+    return (q, status, all_q, all_status) if return_all else (q, status)
+
+
+_ik_cloud_scratch: dict = {}
+
+
+def franka_ik_cloud(target_poses: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                    point_radius: float = 0.0, q_init: Optional[torch.Tensor] = None, limits=ft.JOINT_LIMITS_REAL,
+                    seed: int = 0, env_offset: int = 0, with_base_link: bool = False, return_all: bool = False,
+                    finger: float = ft.FINGER_OPENING, **options):
+    """``franka_ik`` against one POINT CLOUD per environment instead of primitives (``mpx_franka_ik_cloud``): the same 64
+    starts and iterations, and the result is the lowest start that converges, is free of the cloud by
+    ``FrankaCollisionSampler.check_cloud``'s test (``point_radius``, ``clearance`` from the options) and, with
+    ``check_self`` (default: on), of the robot itself.
+
+    :param cloud: [B,N,3] or [B,N,4] float32 on the GPU, any view whose last stride is 1 (``xyz[:, 2048:6144, :3]`` of the
+        slab is read in place); ``counts`` optional int [B] as for ``check_cloud``
+    :param point_radius: radius given to every point (>= 0)
+    :returns: what ``franka_ik`` returns; bit 1 of ``all_status`` is the cloud verdict of a converged start (0 on the
+        others, which are not tested)."""
+    from .field import cloud_operand
+
+    opts = dict(IK_DEFAULTS, check_self=True)
+    if "lambda" in options:
+        options["damping"] = options.pop("lambda")
+    unknown = set(options) - set(opts)
+    if unknown:
+        raise TypeError(f"franka_ik_cloud: unknown option(s) {sorted(unknown)}")
+    opts.update(options)
+    _lib.require_cuda(target_poses, q_init, cloud, counts)
+    assert target_poses.ndim == 3 and target_poses.shape[1:] == (4, 4)
+    B, dev = target_poses.size(0), target_poses.device
+    tp = _lib.f32c(target_poses)
+    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
+    assert lim.shape == (7, 2)
+    qi = None
+    if q_init is not None:
+        assert q_init.shape == (B, 7)
+        qi = _lib.f32c(q_init)
+    copt = _lib.IkOptions(int(opts["iterations"]), float(opts["damping"]), float(opts["step_clip"]), float(opts["pos_tol"]),
+                          float(opts["rot_tol"]), float(opts["clearance"]), int(bool(opts["check_self"])))
+    N, cbs, cps = cloud_operand("franka_ik_cloud", cloud, B)
+    cn = None
+    if counts is not None:
+        assert counts.shape == (B,)
+        cn = _lib.i32c(counts)
+    sc, sr, sl = _ik_sphere_table(dev, with_base_link)
+    S = int(sc.size(0))
+    q = torch.empty((B, 7), dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    all_q = torch.empty((B, IK_SEEDS, 7), dtype=torch.float32, device=dev) if return_all else None
+    all_status = torch.empty((B, IK_SEEDS), dtype=torch.int32, device=dev) if return_all else None
+    nbytes = int(_lib.load().mpx_franka_ik_cloud_scratch(B))
+    buf = _ik_cloud_scratch.get(dev.index)  # one growing buffer per GPU: the call's work is ordered on the stream
+    if buf is None or buf.numel() < nbytes:
+        buf = _ik_cloud_scratch[dev.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _lib.call("mpx_franka_ik_cloud", _lib.ptr(tp), B, float(finger), _lib.ptr(lim), _lib.ptr(qi), _lib.ptr(sc), _lib.ptr(sr),
+              _lib.ptr(sl), S, _lib.ptr(cloud) if N else None, cbs, cps, N, _lib.ptr(cn), float(point_radius),
+              ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(q), _lib.ptr(status), _lib.ptr(all_q),
+              _lib.ptr(all_status), _lib.ptr(buf), nbytes)
     return (q, status, all_q, all_status) if return_all else (q, status)
 
 
@@ -564,3 +641,39 @@ class FrankaCollisionSampler:
                   _lib.ptr(cn), float(point_radius), float(clearance), _lib.ptr(flags), _lib.ptr(dist), _lib.ptr(near))
         out = (flags != 0,) + ((dist,) if return_distance else ()) + ((near,) if return_nearest else ())
         return out if len(out) > 1 else out[0]
+
+    def check_cloud_each(self, q: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                         point_radius: float = 0.0, clearance: float = 0.0, active: Optional[torch.Tensor] = None):
+        """``check_cloud`` with one verdict per WAYPOINT (``mpx_franka_cloud_collision_each``): the same cloud and stride
+        rules, the same test.
+
+        :param q: [B,T,7] (or [B,7]) joint angles
+        :param active: optional bool / int [B,T]: waypoints with a zero are not tested (their q is not read) and come back
+            False
+        :returns: ``hit`` bool [B,T]: ``hit[b,t]`` is what ``check_cloud`` answers for the single configuration ``q[b,t]``
+            against environment b's cloud; ``hit.any(1)`` is ``check_cloud(q, cloud)``
+        """
+        if q.ndim == 2:
+            q = q.unsqueeze(1)
+        _lib.require_cuda(q, cloud, counts, active)
+        B, T, _ = q.shape
+        if cloud.ndim != 3 or cloud.size(0) != B or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32:
+            raise _lib.MpxError(f"check_cloud_each: cloud must be float32 [B={B},N,3] or [B,N,4], got {cloud.dtype} {tuple(cloud.shape)}")
+        N = cloud.size(1)
+        if N > 0 and B > 0 and cloud.stride(2) != 1:
+            raise _lib.MpxError("check_cloud_each: the cloud's last dimension must have stride 1")
+        ps = cloud.stride(1) if N > 1 else max(cloud.stride(1), 3)  # (a one-row view may carry any row stride)
+        qc = _lib.f32c(q)
+        cn = None
+        if counts is not None:
+            assert counts.shape == (B,)
+            cn = _lib.i32c(counts)
+        ac = None
+        if active is not None:
+            assert active.shape == (B, T)
+            ac = _lib.i32c(active)
+        hit = torch.empty((B, T), dtype=torch.int32, device=q.device)
+        _lib.call("mpx_franka_cloud_collision_each", _lib.ptr(qc), B, T, self.finger, _lib.ptr(self.centers),
+                  _lib.ptr(self.radii), _lib.ptr(self.links), self.num_spheres, _lib.ptr(cloud), cloud.stride(0), ps, N,
+                  _lib.ptr(cn), float(point_radius), float(clearance), _lib.ptr(ac), _lib.ptr(hit))
+        return hit != 0
