@@ -36,6 +36,7 @@
 // most 0.9902 + 4e-4 < 1 apart in that coordinate and their cells differ by at most one.  Clamping into [0, n - 1] is
 // monotone and keeps that; it is also what keeps every index in range whatever the coordinates are.
 #include "common.h"
+#include "franka_host.h"
 #include "philox.h"
 #include "select_device.h"
 
@@ -339,10 +340,9 @@ MPX_EXPORT int mpx_cloud_clean(const float *cloud, int64_t cloud_batch_stride, i
   MPX_REQUIRE(min_neighbors == 0 || outlier_radius > 0.0f, "mpx_cloud_clean: outlier_radius must be > 0 when min_neighbors > 0");
   MPX_REQUIRE(cloud_point_stride >= 3, "mpx_cloud_clean: cloud_point_stride < 3");
   MPX_REQUIRE(n_out == 0 || out_point_stride >= 3, "mpx_cloud_clean: out_point_stride < 3");
-  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "mpx_cloud_clean: env_offset + B exceeds 2^32");
+  if (franka_env_offset_check("mpx_cloud_clean", env_offset, B)) return 1;
   const CleanLayout L = clean_layout(B, N);
-  MPX_REQUIRE(scratch_bytes >= (int64_t)L.total, "mpx_cloud_clean: scratch of %lld bytes, mpx_cloud_clean_scratch(%d, %d) = %lld",
-              (long long)scratch_bytes, B, N, (long long)L.total);
+  if (franka_scratch_size_check("mpx_cloud_clean", scratch_bytes, (int64_t)L.total, {B, N})) return 1;
   if (B == 0) return 0;
   MPX_REQUIRE(count && scratch && (cloud || N == 0) && (boxes || n_boxes == 0) && ((sph_centers && sph_radii) || S == 0) &&
                   (out || n_out == 0),

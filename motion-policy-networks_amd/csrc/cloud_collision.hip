@@ -40,6 +40,7 @@
 // function the shared body compiled the flag kernels differently (__restrict__ on its parameters is not __restrict__ on a
 // kernel's), and their instruction streams are pinned (tools/isa_diff.py, profiles/ik_cloud_timing.md).
 #include "common.h"
+#include "franka_host.h"
 
 constexpr int FRAME_FLOATS = MPX_NUM_FRAMES * 12;  // 180
 constexpr int CC_TC = MPX_CLOUD_TC;                // waypoints per workgroup
@@ -79,47 +80,29 @@ MPX_EXPORT int mpx_franka_cloud_collision(const float *q, int B, int T, float fi
                                           int64_t cloud_batch_stride, int cloud_point_stride, int N, const int32_t *counts,
                                           float point_radius, float clearance, int32_t *flags, float *min_dist,
                                           int32_t *nearest, mpx_stream_t stream) {
-  MPX_REQUIRE(B >= 0 && T >= 0 && S >= 0 && N >= 0, "mpx_franka_cloud_collision: negative size");
-  MPX_REQUIRE(S <= 64, "mpx_franka_cloud_collision: S = %d spheres, at most 64", S);
-  MPX_REQUIRE(point_radius >= 0.0f, "mpx_franka_cloud_collision: point_radius must be >= 0");
-  MPX_REQUIRE(clearance == clearance, "mpx_franka_cloud_collision: clearance is NaN");
-  MPX_REQUIRE(cloud_point_stride >= 3, "mpx_franka_cloud_collision: cloud_point_stride < 3");
-  MPX_REQUIRE((int64_t)B * T < (int64_t)1 << 31, "mpx_franka_cloud_collision: B*T overflows int32");
+  const char *who = "mpx_franka_cloud_collision";
+  if (franka_cloud_operand_check(who, B, S, N, point_radius, clearance, cloud_point_stride) || franka_rows_check(who, B, T, "B*T") ||
+      franka_counts_check(who, S))
+    return 1;
   if (B == 0 || T == 0 || S == 0) return 0;
   const bool full = min_dist != nullptr || nearest != nullptr;
   if (N == 0 && !full) return 0;  // no point, no hit
-  MPX_REQUIRE(q && sph_centers && sph_radii && sph_link && flags && (cloud || N == 0), "mpx_franka_cloud_collision: NULL operand");
+  MPX_REQUIRE(q && sph_centers && sph_radii && sph_link && flags && (cloud || N == 0), "%s: NULL operand", who);
   const int chunks = cdiv(T, CC_TC);
-  MPX_REQUIRE((int64_t)B * chunks < (int64_t)1 << 31, "mpx_franka_cloud_collision: too many workgroups");
+  MPX_REQUIRE((int64_t)B * chunks < (int64_t)1 << 31, "%s: too many workgroups", who);
   const bool cull = !full && mpx_get_variant(MPX_VARIANT_CLOUD_CULL) != 0;
   const int nt = min(T, CC_TC);
   const size_t lds_bytes = sizeof(float) * (size_t)max(nt * FRAME_FLOATS, 2 * CC_TILE * 4);
-#define CLOUD_LAUNCH(BLOCK, PPT, FULL, CULL)                                                                            \
-  hipLaunchKernelGGL((franka_cloud_collision_kernel<BLOCK, PPT, FULL, CULL>), dim3((unsigned)(B * chunks)), dim3(BLOCK), \
-                     lds_bytes, mpx_s(stream), q, T, chunks, finger, sph_centers, sph_radii, sph_link, S, cloud,        \
-                     cloud_batch_stride, cloud_point_stride, N, counts, point_radius, clearance, flags, min_dist, nearest)
-#define CLOUD_FORM(BLOCK, PPT)                       \
-  do {                                               \
-    if (full) CLOUD_LAUNCH(BLOCK, PPT, true, false); \
-    else if (cull) CLOUD_LAUNCH(BLOCK, PPT, false, true); \
-    else CLOUD_LAUNCH(BLOCK, PPT, false, false);     \
-  } while (0)
-  if (nt * S <= 64) CLOUD_FORM(64, 1);  // one waypoint (a configuration, the rollout step): one wave, one pair per lane
-  else {
-    switch ((nt * S + 511) / 512) {  // pairs per thread of a full chunk over 256 threads, rounded up to even
-      case 1: CLOUD_FORM(256, 2); break;
-      case 2: CLOUD_FORM(256, 4); break;
-      case 3: CLOUD_FORM(256, 6); break;
-      case 4: CLOUD_FORM(256, 8); break;
-      case 5: CLOUD_FORM(256, 10); break;
-      case 6: CLOUD_FORM(256, 12); break;
-      case 7: CLOUD_FORM(256, 14); break;
-      default: CLOUD_FORM(256, 16); break;
-    }
-  }
-#undef CLOUD_FORM
-#undef CLOUD_LAUNCH
-  MPX_LAUNCH_CHECK("mpx_franka_cloud_collision");
+  franka_cloud_launch_form(nt * S, [&](auto BLOCK, auto PPT) {
+    constexpr int block = decltype(BLOCK)::value, ppt = decltype(PPT)::value;
+    auto kernel = full   ? franka_cloud_collision_kernel<block, ppt, true, false>
+                  : cull ? franka_cloud_collision_kernel<block, ppt, false, true>
+                         : franka_cloud_collision_kernel<block, ppt, false, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(B * chunks)), dim3(block), lds_bytes, mpx_s(stream), q, T, chunks, finger,
+                       sph_centers, sph_radii, sph_link, S, cloud, cloud_batch_stride, cloud_point_stride, N, counts,
+                       point_radius, clearance, flags, min_dist, nearest);
+  });
+  MPX_LAUNCH_CHECK(who);
 }
 
 __global__ void __launch_bounds__(256) cloud_each_zero_kernel(int32_t *__restrict__ hit, int64_t n) {
@@ -132,48 +115,29 @@ MPX_EXPORT int mpx_franka_cloud_collision_each(const float *q, int B, int T, flo
                                                int64_t cloud_batch_stride, int cloud_point_stride, int N,
                                                const int32_t *counts, float point_radius, float clearance,
                                                const int32_t *active, int32_t *hit, mpx_stream_t stream) {
-  MPX_REQUIRE(B >= 0 && T >= 0 && S >= 0 && N >= 0, "mpx_franka_cloud_collision_each: negative size");
-  MPX_REQUIRE(S <= 64, "mpx_franka_cloud_collision_each: S = %d spheres, at most 64", S);
-  MPX_REQUIRE(point_radius >= 0.0f, "mpx_franka_cloud_collision_each: point_radius must be >= 0");
-  MPX_REQUIRE(clearance == clearance, "mpx_franka_cloud_collision_each: clearance is NaN");
-  MPX_REQUIRE(cloud_point_stride >= 3, "mpx_franka_cloud_collision_each: cloud_point_stride < 3");
-  MPX_REQUIRE((int64_t)B * T < (int64_t)1 << 31, "mpx_franka_cloud_collision_each: B*T overflows int32");
+  const char *who = "mpx_franka_cloud_collision_each";
+  if (franka_cloud_operand_check(who, B, S, N, point_radius, clearance, cloud_point_stride) || franka_rows_check(who, B, T, "B*T") ||
+      franka_counts_check(who, S))
+    return 1;
   if (B == 0 || T == 0) return 0;
-  MPX_REQUIRE(hit, "mpx_franka_cloud_collision_each: NULL output (hit)");
+  MPX_REQUIRE(hit, "%s: NULL output (hit)", who);
   if (S == 0 || N == 0) {  // no sphere or no point: no hit, but every verdict is still written
     const int64_t n = (int64_t)B * T;
     hipLaunchKernelGGL(cloud_each_zero_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, mpx_s(stream), hit, n);
-    MPX_LAUNCH_CHECK("mpx_franka_cloud_collision_each");
+    MPX_LAUNCH_CHECK(who);
   }
-  MPX_REQUIRE(q && sph_centers && sph_radii && sph_link && cloud, "mpx_franka_cloud_collision_each: NULL operand");
+  MPX_REQUIRE(q && sph_centers && sph_radii && sph_link && cloud, "%s: NULL operand", who);
   const int chunks = cdiv(T, CC_TC);
-  MPX_REQUIRE((int64_t)B * chunks < (int64_t)1 << 31, "mpx_franka_cloud_collision_each: too many workgroups");
+  MPX_REQUIRE((int64_t)B * chunks < (int64_t)1 << 31, "%s: too many workgroups", who);
   const bool cull = mpx_get_variant(MPX_VARIANT_CLOUD_CULL) != 0;
   const int nt = min(T, CC_TC);
   const size_t lds_bytes = sizeof(float) * (size_t)max(nt * FRAME_FLOATS, 2 * CC_TILE * 4);
-#define CLOUD_LAUNCH(BLOCK, PPT, CULL)                                                                                   \
-  hipLaunchKernelGGL((franka_cloud_collision_each_kernel<BLOCK, PPT, CULL>), dim3((unsigned)(B * chunks)), dim3(BLOCK),  \
-                     lds_bytes, mpx_s(stream), q, T, chunks, finger, sph_centers, sph_radii, sph_link, S, cloud,         \
-                     cloud_batch_stride, cloud_point_stride, N, counts, point_radius, clearance, active, hit)
-#define CLOUD_FORM(BLOCK, PPT)                   \
-  do {                                           \
-    if (cull) CLOUD_LAUNCH(BLOCK, PPT, true);    \
-    else CLOUD_LAUNCH(BLOCK, PPT, false);        \
-  } while (0)
-  if (nt * S <= 64) CLOUD_FORM(64, 1);
-  else {
-    switch ((nt * S + 511) / 512) {  // (the instantiations of mpx_franka_cloud_collision)
-      case 1: CLOUD_FORM(256, 2); break;
-      case 2: CLOUD_FORM(256, 4); break;
-      case 3: CLOUD_FORM(256, 6); break;
-      case 4: CLOUD_FORM(256, 8); break;
-      case 5: CLOUD_FORM(256, 10); break;
-      case 6: CLOUD_FORM(256, 12); break;
-      case 7: CLOUD_FORM(256, 14); break;
-      default: CLOUD_FORM(256, 16); break;
-    }
-  }
-#undef CLOUD_FORM
-#undef CLOUD_LAUNCH
-  MPX_LAUNCH_CHECK("mpx_franka_cloud_collision_each");
+  franka_cloud_launch_form(nt * S, [&](auto BLOCK, auto PPT) {
+    constexpr int block = decltype(BLOCK)::value, ppt = decltype(PPT)::value;
+    auto kernel = cull ? franka_cloud_collision_each_kernel<block, ppt, true> : franka_cloud_collision_each_kernel<block, ppt, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(B * chunks)), dim3(block), lds_bytes, mpx_s(stream), q, T, chunks, finger,
+                       sph_centers, sph_radii, sph_link, S, cloud, cloud_batch_stride, cloud_point_stride, N, counts,
+                       point_radius, clearance, active, hit);
+  });
+  MPX_LAUNCH_CHECK(who);
 }

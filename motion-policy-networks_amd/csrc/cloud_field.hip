@@ -19,6 +19,7 @@
 // mpx_franka_cloud_collision once per candidate (flags only: its bounding-box cull applies) and once for the endpoints,
 // and a select kernel forms status, choice and traj.
 #include "common.h"
+#include "franka_host.h"
 #include "plan_device.h"
 
 constexpr int FB = MPX_FIELD_BRICK;
@@ -416,12 +417,8 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-static bool plan_cloud_sizes_ok(int B, int T, int K, int substeps) {
-  return B >= 0 && T >= 2 && T <= MPX_PLAN_MAX_T && K >= 1 && K <= MPX_PLAN_MAX_CANDIDATES && substeps >= 1 && substeps <= 64;
-}
-
 MPX_EXPORT int64_t mpx_franka_plan_cloud_scratch(int B, int T, int candidates, int substeps) {
-  if (!plan_cloud_sizes_ok(B, T, candidates, substeps)) return -1;
+  if (B < 0 || !franka_plan_T_ok(T) || !franka_plan_candidates_ok(candidates) || !franka_plan_substeps_ok(substeps)) return -1;
   return (int64_t)plan_cloud_layout(B, T, candidates, substeps).total_bytes;
 }
 
@@ -432,53 +429,34 @@ MPX_EXPORT int mpx_franka_plan_cloud(const float *q_start, const float *q_goal, 
                                      float point_radius, const mpx_plan_options *options, uint64_t seed, int64_t env_offset,
                                      float *traj, int32_t *status, int32_t *choice, float *all_traj, int32_t *all_status,
                                      void *scratch, int64_t scratch_bytes, mpx_stream_t stream) {
-  mpx_plan_options opt = {MPX_PLAN_DEFAULT_CANDIDATES,   MPX_PLAN_DEFAULT_ITERATIONS, MPX_PLAN_DEFAULT_STEP,
-                          MPX_PLAN_DEFAULT_SMOOTH_WEIGHT, MPX_PLAN_DEFAULT_EPSILON,    MPX_PLAN_DEFAULT_SPREAD,
-                          MPX_PLAN_DEFAULT_SUBSTEPS,      MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f,
-                          MPX_PLAN_DEFAULT_MAX_JERK,      1};
-  if (options) opt = *options;
-  MPX_REQUIRE(B >= 0 && S >= 0 && N >= 0, "mpx_franka_plan_cloud: negative size");
-  MPX_REQUIRE(T >= 2 && T <= MPX_PLAN_MAX_T, "mpx_franka_plan_cloud: T = %d waypoints, need 2 .. %d (one lane each)", T,
-              MPX_PLAN_MAX_T);
-  MPX_REQUIRE(opt.candidates >= 1 && opt.candidates <= MPX_PLAN_MAX_CANDIDATES,
-              "mpx_franka_plan_cloud: candidates = %d, need 1 .. %d (one wave each)", opt.candidates, MPX_PLAN_MAX_CANDIDATES);
-  MPX_REQUIRE(S <= 64, "mpx_franka_plan_cloud: S = %d collision spheres, at most 64", S);
-  MPX_REQUIRE(opt.iterations >= 0, "mpx_franka_plan_cloud: iterations = %d, need >= 0", opt.iterations);
-  MPX_REQUIRE(opt.step > 0.0f, "mpx_franka_plan_cloud: step must be > 0");
-  MPX_REQUIRE(opt.epsilon > 0.0f, "mpx_franka_plan_cloud: epsilon must be > 0");
-  MPX_REQUIRE(opt.smooth_weight >= 0.0f, "mpx_franka_plan_cloud: smooth_weight must be >= 0");
-  MPX_REQUIRE(opt.substeps >= 1 && opt.substeps <= 64, "mpx_franka_plan_cloud: substeps = %d, need 1 .. 64", opt.substeps);
-  MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "mpx_franka_plan_cloud: negative check_margin or max_jerk");
-  MPX_REQUIRE(opt.clearance == opt.clearance && opt.spread == opt.spread, "mpx_franka_plan_cloud: clearance or spread is NaN");
-  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "mpx_franka_plan_cloud: env_offset + B exceeds 2^32");
-  MPX_REQUIRE(point_radius >= 0.0f, "mpx_franka_plan_cloud: point_radius must be >= 0");
-  MPX_REQUIRE(cloud_point_stride >= 3 || N == 0 || !cloud, "mpx_franka_plan_cloud: cloud_point_stride < 3");
+  const char *who = "mpx_franka_plan_cloud";
+  const mpx_plan_options opt = options ? *options : franka_plan_defaults();
+  if (franka_plan_options_check(who, T, opt) || franka_counts_check(who, S) || franka_env_offset_check(who, env_offset, B) ||
+      franka_cloud_operand_check(who, B, S, N, point_radius, opt.clearance, cloud_point_stride, cloud && N > 0))
+    return 1;  // (a short stride is tolerated when no point is read)
   FieldGrid G = {};
-  if (field && field_grid_check("mpx_franka_plan_cloud", grid, G)) return 1;
+  if (field && field_grid_check(who, grid, G)) return 1;
   const int K = opt.candidates, R = (T - 1) * opt.substeps + 1;
-  MPX_REQUIRE((int64_t)B * R < (int64_t)1 << 31, "mpx_franka_plan_cloud: B x refined configurations overflows int32");
+  if (franka_rows_check(who, B, R, "B x refined configurations")) return 1;
   const PlanCloudScratch L = plan_cloud_layout(B, T, K, opt.substeps);
-  MPX_REQUIRE(scratch_bytes >= (int64_t)L.total_bytes,
-              "mpx_franka_plan_cloud: scratch of %lld bytes, mpx_franka_plan_cloud_scratch(%d, %d, %d, %d) = %lld",
-              (long long)scratch_bytes, B, T, K, opt.substeps, (long long)L.total_bytes);
+  if (franka_scratch_size_check(who, scratch_bytes, (int64_t)L.total_bytes, {B, T, K, opt.substeps})) return 1;
   if (B == 0) return 0;
-  MPX_REQUIRE(traj && status, "mpx_franka_plan_cloud: NULL output (traj, status)");
-  MPX_REQUIRE(q_start && q_goal && limits, "mpx_franka_plan_cloud: NULL operand (q_start, q_goal, limits)");
-  MPX_REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "mpx_franka_plan_cloud: scratch is NULL or not 16-byte aligned");
-  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_plan_cloud: S > 0 without the sphere table");
-  MPX_REQUIRE((!field && (!cloud || N == 0)) || S > 0, "mpx_franka_plan_cloud: a field or a cloud without collision spheres to test them with");
+  MPX_REQUIRE(traj && status, "%s: NULL output (traj, status)", who);
+  MPX_REQUIRE(q_start && q_goal && limits, "%s: NULL operand (q_start, q_goal, limits)", who);
+  if (franka_scratch_pointer_check(who, scratch) || franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link)) return 1;
+  MPX_REQUIRE((!field && (!cloud || N == 0)) || S > 0, "%s: a field or a cloud without collision spheres to test them with", who);
   float *w = static_cast<float *>(scratch);
   int32_t *wi = static_cast<int32_t *>(scratch);
   hipStream_t st = mpx_s(stream);
   hipError_t e = hipMemsetAsync(wi + L.cand_flags, 0, sizeof(int32_t) * ((size_t)K + 1) * B, st);
-  MPX_REQUIRE(e == hipSuccess, "mpx_franka_plan_cloud: memset failed: %s", hipGetErrorString(e));
+  MPX_REQUIRE(e == hipSuccess, "%s: memset failed: %s", who, hipGetErrorString(e));
   const size_t lds = sizeof(float) * ((size_t)T * T + (size_t)K * 64 * 7);  // <= 45 056 B
   auto kernel = K <= 8 ? franka_plan_cloud_kernel<8> : franka_plan_cloud_kernel<MPX_PLAN_MAX_CANDIDATES>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64 * K), lds, st, q_start, q_goal, B, T, finger, limits, sph_centers,
                      sph_radii, sph_link, S, field, G, point_radius, opt, (uint32_t)seed, (uint32_t)(seed >> 32),
                      (uint32_t)env_offset, w + L.refined, w + L.ctraj, w + L.ends, wi + L.cand_bits, wi + L.bad_end);
   e = hipGetLastError();
-  MPX_REQUIRE(e == hipSuccess, "mpx_franka_plan_cloud: launch failed: %s", hipGetErrorString(e));
+  MPX_REQUIRE(e == hipSuccess, "%s: launch failed: %s", who, hipGetErrorString(e));
   if (cloud && N > 0 && S > 0) {
     const float reach = opt.clearance + opt.check_margin;  // (float32, as the contract says)
     for (int k = 0; k < K; ++k)
@@ -494,5 +472,5 @@ MPX_EXPORT int mpx_franka_plan_cloud(const float *q_start, const float *q_goal, 
   hipLaunchKernelGGL(franka_plan_cloud_select_kernel, dim3((unsigned)B), dim3(256), 0, st, B, T, K, w + L.ctraj,
                      wi + L.cand_bits, wi + L.cand_flags, wi + L.end_flags, wi + L.bad_end, traj, status, choice, all_traj,
                      all_status);
-  MPX_LAUNCH_CHECK("mpx_franka_plan_cloud");
+  MPX_LAUNCH_CHECK(who);
 }

@@ -1,0 +1,121 @@
+// franka_host.h -- host-only (no __device__ code): the argument checks and the cloud launch table that the Franka geometry
+// entries share (ik.hip, plan.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for env_offset and scratch size); a
+// new entry takes its checks from here.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
+// returns 0 or 1 (field_grid_check's idiom).  Sizes and values are checked before an entry's "nothing to do" return, pointers after.
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <initializer_list>
+#include <type_traits>
+
+#include "common.h"
+
+// options: the defaults (MPX_*_DEFAULT_*, include/mpinets_hip.h) and what a kernel can run with
+static inline mpx_ik_options franka_ik_defaults() {
+  return {MPX_IK_DEFAULT_ITERATIONS, MPX_IK_DEFAULT_LAMBDA, MPX_IK_DEFAULT_STEP_CLIP, MPX_IK_DEFAULT_POS_TOL,
+          MPX_IK_DEFAULT_ROT_TOL, 0.0f, 0};
+}
+static inline mpx_plan_options franka_plan_defaults() {
+  return {MPX_PLAN_DEFAULT_CANDIDATES, MPX_PLAN_DEFAULT_ITERATIONS, MPX_PLAN_DEFAULT_STEP, MPX_PLAN_DEFAULT_SMOOTH_WEIGHT,
+          MPX_PLAN_DEFAULT_EPSILON, MPX_PLAN_DEFAULT_SPREAD, MPX_PLAN_DEFAULT_SUBSTEPS, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f,
+          MPX_PLAN_DEFAULT_MAX_JERK, 1};
+}
+static inline int franka_ik_options_check(const char *who, const mpx_ik_options &opt) {
+  MPX_REQUIRE(opt.iterations >= 1, "%s: iterations = %d, need >= 1", who, opt.iterations);
+  MPX_REQUIRE(opt.lambda > 0.0f, "%s: lambda must be > 0 (the 6x6 solve has no pivoting)", who);
+  MPX_REQUIRE(opt.step_clip > 0.0f, "%s: step_clip must be > 0", who);
+  MPX_REQUIRE(opt.pos_tol >= 0.0f && opt.rot_tol >= 0.0f, "%s: negative tolerance", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
+  return 0;
+}
+// (the three sizes a planner's LDS and scratch layouts are computed from: mpx_franka_plan_cloud_scratch asks them too)
+static inline bool franka_plan_T_ok(int T) { return T >= 2 && T <= MPX_PLAN_MAX_T; }
+static inline bool franka_plan_candidates_ok(int K) { return K >= 1 && K <= MPX_PLAN_MAX_CANDIDATES; }
+static inline bool franka_plan_substeps_ok(int substeps) { return substeps >= 1 && substeps <= 64; }
+static inline int franka_plan_options_check(const char *who, int T, const mpx_plan_options &opt) {
+  MPX_REQUIRE(franka_plan_T_ok(T), "%s: T = %d waypoints, need 2 .. %d (one lane each)", who, T, MPX_PLAN_MAX_T);
+  MPX_REQUIRE(franka_plan_candidates_ok(opt.candidates), "%s: candidates = %d, need 1 .. %d (one wave each)", who,
+              opt.candidates, MPX_PLAN_MAX_CANDIDATES);
+  MPX_REQUIRE(opt.iterations >= 0, "%s: iterations = %d, need >= 0", who, opt.iterations);
+  MPX_REQUIRE(opt.step > 0.0f, "%s: step must be > 0", who);
+  MPX_REQUIRE(opt.epsilon > 0.0f, "%s: epsilon must be > 0", who);
+  MPX_REQUIRE(opt.smooth_weight >= 0.0f, "%s: smooth_weight must be >= 0", who);
+  MPX_REQUIRE(franka_plan_substeps_ok(opt.substeps), "%s: substeps = %d, need 1 .. 64", who, opt.substeps);
+  MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "%s: negative check_margin or max_jerk", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance && opt.spread == opt.spread, "%s: clearance or spread is NaN", who);
+  return 0;
+}
+
+// (a negative S, M1 or M2 is the entry's own "negative size")
+static inline int franka_counts_check(const char *who, int S, int M1 = 0, int M2 = 0) {
+  MPX_REQUIRE(S <= MPX_IK_SEEDS, "%s: S = %d collision spheres, at most %d", who, S, MPX_IK_SEEDS);
+  MPX_REQUIRE(M1 <= 64 && M2 <= 64, "%s: at most 64 cuboids and 64 cylinders per problem (%d, %d)", who, M1, M2);
+  return 0;
+}
+static inline int franka_sphere_table_check(const char *who, int S, const float *sph_centers, const float *sph_radii,
+                                            const int32_t *sph_link) {
+  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "%s: S > 0 without the sphere table", who);
+  return 0;
+}
+static inline int franka_primitive_arrays_check(const char *who, int S, const float *cub_inv_frames, const float *cub_dims,
+                                                int M1, const float *cyl_inv_frames, const float *cyl_radii,
+                                                const float *cyl_heights, int M2) {
+  MPX_REQUIRE(M1 == 0 || (cub_inv_frames && cub_dims), "%s: M1 > 0 without cuboid arrays", who);
+  MPX_REQUIRE(M2 == 0 || (cyl_inv_frames && cyl_radii && cyl_heights), "%s: M2 > 0 without cylinder arrays", who);
+  MPX_REQUIRE(M1 + M2 == 0 || S > 0, "%s: primitives without collision spheres to test them with", who);
+  return 0;
+}
+static inline int franka_env_offset_check(const char *who, int64_t env_offset, int B) {
+  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "%s: env_offset + B exceeds 2^32", who);
+  return 0;
+}
+
+// `cloud_is_read` = false: the entry reads no point (no cloud, or N == 0) and says a short stride is then tolerated
+// (mpx_franka_plan_cloud; the cloud-collision entries and mpx_franka_ik_cloud refuse it whatever N is).
+static inline int franka_cloud_operand_check(const char *who, int B, int S, int N, float point_radius, float clearance,
+                                             int cloud_point_stride, bool cloud_is_read = true) {
+  MPX_REQUIRE(B >= 0 && S >= 0 && N >= 0, "%s: negative size", who);
+  MPX_REQUIRE(point_radius >= 0.0f, "%s: point_radius must be >= 0", who);
+  MPX_REQUIRE(clearance == clearance, "%s: clearance is NaN", who);
+  MPX_REQUIRE(cloud_point_stride >= 3 || !cloud_is_read, "%s: cloud_point_stride < 3", who);
+  return 0;
+}
+// the B x T rows (waypoints, starts, refined configurations) an entry indexes in int32; `product` is its name for them
+static inline int franka_rows_check(const char *who, int B, int T, const char *product) {
+  MPX_REQUIRE(T >= 0, "%s: negative size", who);
+  MPX_REQUIRE((int64_t)B * T < (int64_t)1 << 31, "%s: %s overflows int32", who, product);
+  return 0;
+}
+
+// `need` is what the entry's own <who>_scratch(dims...) answers
+static inline int franka_scratch_size_check(const char *who, int64_t scratch_bytes, int64_t need, std::initializer_list<int> dims) {
+  char args[64] = "";  // (at most four ints of up to 11 characters and their separators)
+  int at = 0;
+  if (scratch_bytes < need)
+    for (int d : dims) at += snprintf(args + at, sizeof(args) - (size_t)at, at ? ", %d" : "%d", d);
+  MPX_REQUIRE(scratch_bytes >= need, "%s: scratch of %lld bytes, %s_scratch(%s) = %lld", who, (long long)scratch_bytes, who,
+              args, (long long)need);
+  return 0;
+}
+static inline int franka_scratch_pointer_check(const char *who, const void *scratch) {
+  MPX_REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "%s: scratch is NULL or not 16-byte aligned", who);
+  return 0;
+}
+
+// pairs = (waypoint, sphere) pairs of a full chunk -> launch(BLOCK, PPT) as std::integral_constants.  Up to 64 pairs (one
+// waypoint: a configuration, the rollout step): one wave, one pair per lane; above, the pairs per thread of 256, rounded to even.
+template <class Launch>
+static inline void franka_cloud_launch_form(int pairs, Launch &&launch) {
+  using B256 = std::integral_constant<int, 256>;
+  if (pairs <= 64) return launch(std::integral_constant<int, 64>(), std::integral_constant<int, 1>());
+  switch ((pairs + 511) / 512) {
+    case 1: return launch(B256(), std::integral_constant<int, 2>());
+    case 2: return launch(B256(), std::integral_constant<int, 4>());
+    case 3: return launch(B256(), std::integral_constant<int, 6>());
+    case 4: return launch(B256(), std::integral_constant<int, 8>());
+    case 5: return launch(B256(), std::integral_constant<int, 10>());
+    case 6: return launch(B256(), std::integral_constant<int, 12>());
+    case 7: return launch(B256(), std::integral_constant<int, 14>());
+    default: return launch(B256(), std::integral_constant<int, 16>());
+  }
+}

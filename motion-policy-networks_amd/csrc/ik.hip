@@ -24,6 +24,7 @@
 // (a self-hit start is tested too: with all_status every converged start carries both bits); then a select kernel, one wave per problem, that folds the verdicts into bit 1 and picks the lowest start
 // whose bits equal 1.
 #include "common.h"
+#include "franka_host.h"
 #include "sdf_device.h"
 #include "philox.h"
 
@@ -292,30 +293,22 @@ MPX_EXPORT int mpx_franka_ik(const float *target_poses, int B, float finger, con
                              const float *cyl_radii, const float *cyl_heights, int M2, const mpx_ik_options *options,
                              uint64_t seed, int64_t env_offset, float *q_out, int32_t *status, float *all_q,
                              int32_t *all_status, mpx_stream_t stream) {
-  mpx_ik_options opt = {MPX_IK_DEFAULT_ITERATIONS, MPX_IK_DEFAULT_LAMBDA, MPX_IK_DEFAULT_STEP_CLIP, MPX_IK_DEFAULT_POS_TOL,
-                        MPX_IK_DEFAULT_ROT_TOL, 0.0f, 0};
-  if (options) opt = *options;
-  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "mpx_franka_ik: negative size");
-  MPX_REQUIRE(S <= MPX_IK_SEEDS, "mpx_franka_ik: S = %d collision spheres, at most %d (one lane each)", S, MPX_IK_SEEDS);
-  MPX_REQUIRE(M1 <= 64 && M2 <= 64, "mpx_franka_ik: at most 64 cuboids and 64 cylinders per problem (%d, %d)", M1, M2);
-  MPX_REQUIRE(opt.iterations >= 1, "mpx_franka_ik: iterations = %d, need >= 1", opt.iterations);
-  MPX_REQUIRE(opt.lambda > 0.0f, "mpx_franka_ik: lambda must be > 0 (the 6x6 solve has no pivoting)");
-  MPX_REQUIRE(opt.step_clip > 0.0f, "mpx_franka_ik: step_clip must be > 0");
-  MPX_REQUIRE(opt.pos_tol >= 0.0f && opt.rot_tol >= 0.0f, "mpx_franka_ik: negative tolerance");
-  MPX_REQUIRE(opt.clearance == opt.clearance, "mpx_franka_ik: clearance is NaN");
-  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "mpx_franka_ik: env_offset + B exceeds 2^32");
+  const char *who = "mpx_franka_ik";
+  const mpx_ik_options opt = options ? *options : franka_ik_defaults();
+  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "%s: negative size", who);
+  if (franka_counts_check(who, S, M1, M2) || franka_ik_options_check(who, opt) || franka_env_offset_check(who, env_offset, B))
+    return 1;
   if (B == 0) return 0;
-  MPX_REQUIRE(q_out && status, "mpx_franka_ik: NULL output (q_out, status)");
-  MPX_REQUIRE(target_poses && limits, "mpx_franka_ik: NULL operand (target_poses, limits)");
-  MPX_REQUIRE(M1 == 0 || (cub_inv_frames && cub_dims), "mpx_franka_ik: M1 > 0 without cuboid arrays");
-  MPX_REQUIRE(M2 == 0 || (cyl_inv_frames && cyl_radii && cyl_heights), "mpx_franka_ik: M2 > 0 without cylinder arrays");
-  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_ik: S > 0 without the sphere table");
-  MPX_REQUIRE(M1 + M2 == 0 || S > 0, "mpx_franka_ik: primitives without collision spheres to test them with");
+  MPX_REQUIRE(q_out && status, "%s: NULL output (q_out, status)", who);
+  MPX_REQUIRE(target_poses && limits, "%s: NULL operand (target_poses, limits)", who);
+  if (franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link) ||
+      franka_primitive_arrays_check(who, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii, cyl_heights, M2))
+    return 1;
   hipLaunchKernelGGL(franka_ik_kernel, dim3((unsigned)B), dim3(64), 0, mpx_s(stream), target_poses, finger, limits, q_init,
                      sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii,
                      cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, q_out, status,
                      all_q, all_status);
-  MPX_LAUNCH_CHECK("mpx_franka_ik");
+  MPX_LAUNCH_CHECK(who);
 }
 
 // ---- against a point cloud ------------------------------------------------------------------------------------------------------
@@ -357,22 +350,18 @@ MPX_EXPORT int mpx_franka_ik_cloud(const float *target_poses, int B, float finge
                                    const int32_t *counts, float point_radius, const mpx_ik_options *options, uint64_t seed,
                                    int64_t env_offset, float *q_out, int32_t *status, float *all_q, int32_t *all_status,
                                    void *scratch, int64_t scratch_bytes, mpx_stream_t stream) {
-  const float clearance = options ? options->clearance : 0.0f;
-  // what the cloud check would refuse, before anything is launched
-  MPX_REQUIRE(B >= 0 && S >= 0 && N >= 0, "mpx_franka_ik_cloud: negative size");
-  MPX_REQUIRE(S <= MPX_IK_SEEDS, "mpx_franka_ik_cloud: S = %d collision spheres, at most %d", S, MPX_IK_SEEDS);
-  MPX_REQUIRE(point_radius >= 0.0f, "mpx_franka_ik_cloud: point_radius must be >= 0");
-  MPX_REQUIRE(clearance == clearance, "mpx_franka_ik_cloud: clearance is NaN");
-  MPX_REQUIRE(cloud_point_stride >= 3, "mpx_franka_ik_cloud: cloud_point_stride < 3");
-  MPX_REQUIRE((int64_t)B * MPX_IK_SEEDS < (int64_t)1 << 31, "mpx_franka_ik_cloud: B * 64 overflows int32");
+  const char *who = "mpx_franka_ik_cloud";
+  const float clearance = options ? options->clearance : franka_ik_defaults().clearance;
+  // what the cloud check would refuse, before anything is launched (the 64 starts are its waypoints)
+  if (franka_cloud_operand_check(who, B, S, N, point_radius, clearance, cloud_point_stride) ||
+      franka_rows_check(who, B, MPX_IK_SEEDS, "B * 64"))
+    return 1;
   const bool test_env = cloud != nullptr && N > 0;
-  MPX_REQUIRE(N == 0 || S > 0, "mpx_franka_ik_cloud: a cloud without collision spheres to test it with");
-  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_ik_cloud: S > 0 without the sphere table");
-  const int64_t need = mpx_franka_ik_cloud_scratch(B);
-  MPX_REQUIRE(scratch_bytes >= need, "mpx_franka_ik_cloud: scratch of %lld bytes, mpx_franka_ik_cloud_scratch(%d) = %lld",
-              (long long)scratch_bytes, B, (long long)need);
-  MPX_REQUIRE(B == 0 || (scratch && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0),
-              "mpx_franka_ik_cloud: scratch is NULL or not 16-byte aligned");
+  MPX_REQUIRE(N == 0 || S > 0, "%s: a cloud without collision spheres to test it with", who);
+  if (franka_counts_check(who, S) || franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link) ||
+      franka_scratch_size_check(who, scratch_bytes, mpx_franka_ik_cloud_scratch(B), {B}) ||
+      (B > 0 && franka_scratch_pointer_check(who, scratch)))
+    return 1;
   float *w_q = all_q ? all_q : static_cast<float *>(scratch);
   int32_t *wi = static_cast<int32_t *>(scratch) + (size_t)B * MPX_IK_SEEDS * 7;
   int32_t *w_bits = wi, *w_active = wi + (size_t)B * MPX_IK_SEEDS, *w_hit = wi + (size_t)2 * B * MPX_IK_SEEDS;
@@ -386,7 +375,7 @@ MPX_EXPORT int mpx_franka_ik_cloud(const float *target_poses, int B, float finge
   if (test_env) {
     hipLaunchKernelGGL(franka_ik_cloud_active_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, w_bits, n, w_active);
     hipError_t e = hipGetLastError();
-    MPX_REQUIRE(e == hipSuccess, "mpx_franka_ik_cloud: launch failed: %s", hipGetErrorString(e));
+    MPX_REQUIRE(e == hipSuccess, "%s: launch failed: %s", who, hipGetErrorString(e));
     if (mpx_franka_cloud_collision_each(w_q, B, MPX_IK_SEEDS, finger, sph_centers, sph_radii, sph_link, S, cloud,
                                         cloud_batch_stride, cloud_point_stride, N, counts, point_radius, clearance, w_active,
                                         w_hit, stream))
@@ -394,5 +383,5 @@ MPX_EXPORT int mpx_franka_ik_cloud(const float *target_poses, int B, float finge
   }
   hipLaunchKernelGGL(franka_ik_cloud_select_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, B, w_q, w_bits,
                      test_env ? w_hit : nullptr, q_out, status, all_status);
-  MPX_LAUNCH_CHECK("mpx_franka_ik_cloud");
+  MPX_LAUNCH_CHECK(who);
 }

@@ -12,6 +12,7 @@
 // g goes to LDS once per iteration for the M g product (n x 7 FMAs per lane, M in LDS, broadcast reads of g).
 // The validity sweep reuses the mapping with lane = refined configuration, in passes of 64.
 #include "common.h"
+#include "franka_host.h"
 #include "sdf_grad_device.h"
 #include "plan_device.h"  // what the planner shares with cloud_field.hip: candidates, M g, the jerk and self tests
 
@@ -255,33 +256,17 @@ MPX_EXPORT int mpx_franka_plan(const float *q_start, const float *q_goal, int B,
                                const float *cyl_radii, const float *cyl_heights, int M2, const mpx_plan_options *options,
                                uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *choice,
                                float *all_traj, int32_t *all_status, mpx_stream_t stream) {
-  mpx_plan_options opt = {MPX_PLAN_DEFAULT_CANDIDATES,   MPX_PLAN_DEFAULT_ITERATIONS, MPX_PLAN_DEFAULT_STEP,
-                          MPX_PLAN_DEFAULT_SMOOTH_WEIGHT, MPX_PLAN_DEFAULT_EPSILON,    MPX_PLAN_DEFAULT_SPREAD,
-                          MPX_PLAN_DEFAULT_SUBSTEPS,      MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f,
-                          MPX_PLAN_DEFAULT_MAX_JERK,      1};
-  if (options) opt = *options;
-  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "mpx_franka_plan: negative size");
-  MPX_REQUIRE(T >= 2 && T <= MPX_PLAN_MAX_T, "mpx_franka_plan: T = %d waypoints, need 2 .. %d (one lane each)", T,
-              MPX_PLAN_MAX_T);
-  MPX_REQUIRE(opt.candidates >= 1 && opt.candidates <= MPX_PLAN_MAX_CANDIDATES,
-              "mpx_franka_plan: candidates = %d, need 1 .. %d (one wave each)", opt.candidates, MPX_PLAN_MAX_CANDIDATES);
-  MPX_REQUIRE(S <= 64, "mpx_franka_plan: S = %d collision spheres, at most 64", S);
-  MPX_REQUIRE(M1 <= 64 && M2 <= 64, "mpx_franka_plan: at most 64 cuboids and 64 cylinders per problem (%d, %d)", M1, M2);
-  MPX_REQUIRE(opt.iterations >= 0, "mpx_franka_plan: iterations = %d, need >= 0", opt.iterations);
-  MPX_REQUIRE(opt.step > 0.0f, "mpx_franka_plan: step must be > 0");
-  MPX_REQUIRE(opt.epsilon > 0.0f, "mpx_franka_plan: epsilon must be > 0");
-  MPX_REQUIRE(opt.smooth_weight >= 0.0f, "mpx_franka_plan: smooth_weight must be >= 0");
-  MPX_REQUIRE(opt.substeps >= 1 && opt.substeps <= 64, "mpx_franka_plan: substeps = %d, need 1 .. 64", opt.substeps);
-  MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "mpx_franka_plan: negative check_margin or max_jerk");
-  MPX_REQUIRE(opt.clearance == opt.clearance && opt.spread == opt.spread, "mpx_franka_plan: clearance or spread is NaN");
-  MPX_REQUIRE(env_offset >= 0 && env_offset + B <= 0xFFFFFFFFll, "mpx_franka_plan: env_offset + B exceeds 2^32");
+  const char *who = "mpx_franka_plan";
+  const mpx_plan_options opt = options ? *options : franka_plan_defaults();
+  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "%s: negative size", who);
+  if (franka_plan_options_check(who, T, opt) || franka_counts_check(who, S, M1, M2) || franka_env_offset_check(who, env_offset, B))
+    return 1;
   if (B == 0) return 0;
-  MPX_REQUIRE(traj && status, "mpx_franka_plan: NULL output (traj, status)");
-  MPX_REQUIRE(q_start && q_goal && limits, "mpx_franka_plan: NULL operand (q_start, q_goal, limits)");
-  MPX_REQUIRE(M1 == 0 || (cub_inv_frames && cub_dims), "mpx_franka_plan: M1 > 0 without cuboid arrays");
-  MPX_REQUIRE(M2 == 0 || (cyl_inv_frames && cyl_radii && cyl_heights), "mpx_franka_plan: M2 > 0 without cylinder arrays");
-  MPX_REQUIRE(S == 0 || (sph_centers && sph_radii && sph_link), "mpx_franka_plan: S > 0 without the sphere table");
-  MPX_REQUIRE(M1 + M2 == 0 || S > 0, "mpx_franka_plan: primitives without collision spheres to test them with");
+  MPX_REQUIRE(traj && status, "%s: NULL output (traj, status)", who);
+  MPX_REQUIRE(q_start && q_goal && limits, "%s: NULL operand (q_start, q_goal, limits)", who);
+  if (franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link) ||
+      franka_primitive_arrays_check(who, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii, cyl_heights, M2))
+    return 1;
   const int K = opt.candidates;
   const size_t lds = sizeof(float) * ((size_t)128 * 16 + (size_t)T * T + (size_t)K * 64 * 7) + sizeof(int) * K;  // <= 53 312 B
   auto kernel = K <= 8 ? franka_plan_kernel<8> : franka_plan_kernel<MPX_PLAN_MAX_CANDIDATES>;
@@ -289,5 +274,5 @@ MPX_EXPORT int mpx_franka_plan(const float *q_start, const float *q_goal, int B,
                      sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii,
                      cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, traj, status,
                      choice, all_traj, all_status);
-  MPX_LAUNCH_CHECK("mpx_franka_plan");
+  MPX_LAUNCH_CHECK(who);
 }

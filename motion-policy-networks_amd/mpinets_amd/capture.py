@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._operands import cloud_operand, counts_operand, scratch_for
 from .robot import FrankaCollisionSampler
 
 # planning_node.py:201-221: the task table and the mount table, rows of (lo x, lo y, lo z, hi x, hi y, hi z); a point is
@@ -27,17 +28,8 @@ REFERENCE_WORKSPACE = np.array([[0.25, -0.3, -0.05, 1.35, 1.6, 0.35],
 REASONS = ("kept", "non-existent or non-finite", "outside the workspace", "robot", "outlier")
 MAX_POINTS = 4096  # SEL_MAX_OUT: what one workgroup's select can draw
 
-_scratch: Dict[int, torch.Tensor] = {}
 _samplers: Dict[int, FrankaCollisionSampler] = {}
 _boxes: Dict[Tuple[int, bytes], torch.Tensor] = {}
-
-
-def _scratch_for(device: torch.device, nbytes: int) -> torch.Tensor:
-    """One growing device buffer per GPU (the call's work is ordered on the stream, like every workspace here)."""
-    buf = _scratch.get(device.index)
-    if buf is None or buf.numel() < nbytes:
-        buf = _scratch[device.index] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-    return buf
 
 
 def _boxes_on(device: torch.device, boxes) -> Tuple[Optional[torch.Tensor], int]:
@@ -86,20 +78,12 @@ def clean_point_clouds(cloud: torch.Tensor, num_points: int = 4096, *, counts: O
     :raises ValueError: like ``np.random.choice`` when an environment keeps fewer than ``num_points`` rows
     """
     _lib.require_cuda(cloud, counts, q, out)
-    if cloud.ndim != 3 or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32:
-        raise _lib.MpxError(f"clean_point_clouds: cloud must be float32 [B,N,3] or [B,N,4], got {cloud.dtype} {tuple(cloud.shape)}")
-    B, N = cloud.size(0), cloud.size(1)
-    dev = cloud.device
-    if N > 0 and B > 0 and cloud.stride(2) != 1:
-        raise _lib.MpxError("clean_point_clouds: the cloud's last dimension must have stride 1")
-    ps = cloud.stride(1) if N > 1 else max(cloud.stride(1), 3)  # (a one-row view may carry any row stride)
+    N, cbs, ps = cloud_operand("clean_point_clouds", cloud, empty_batch_any_stride=False)
+    B, dev = cloud.size(0), cloud.device
     num_points = int(num_points)
     if not 0 <= num_points <= MAX_POINTS:
         raise _lib.MpxError(f"clean_point_clouds: num_points must be in [0, {MAX_POINTS}], got {num_points}")
-    cn = None
-    if counts is not None:
-        assert counts.shape == (B,)
-        cn = _lib.i32c(counts)
+    cn = counts_operand(counts, B)
     bx, n_boxes = _boxes_on(dev, boxes)
     sc = sr = None
     S = 0
@@ -123,8 +107,8 @@ def clean_point_clouds(cloud: torch.Tensor, num_points: int = 4096, *, counts: O
     index = torch.empty((B, num_points), dtype=torch.int32, device=dev) if return_index and num_points > 0 else None
     count = torch.empty(B, dtype=torch.int32, device=dev)
     nbytes = int(_lib.load().mpx_cloud_clean_scratch(B, N))
-    scratch = _scratch_for(dev, nbytes)
-    _lib.call("mpx_cloud_clean", _lib.ptr(cloud), cloud.stride(0), ps, N, _lib.ptr(cn), B, _lib.ptr(bx), n_boxes,
+    scratch = scratch_for(dev, nbytes)
+    _lib.call("mpx_cloud_clean", _lib.ptr(cloud), cbs, ps, N, _lib.ptr(cn), B, _lib.ptr(bx), n_boxes,
               _lib.ptr(sc), _lib.ptr(sr), S, float(robot_margin), float(outlier_radius), int(min_neighbors), num_points,
               int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(out) if num_points else None, obs, ops, _lib.ptr(index),
               _lib.ptr(reason), _lib.ptr(count), _lib.ptr(scratch), nbytes)

@@ -15,25 +15,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._operands import cloud_operand, counts_operand  # (cloud_operand: also this module's public name)
 
 FIELD_MAX_SIDE = 1024  # MPX_FIELD_MAX_SIDE
 FIELD_MAX_NODES = 1 << 24  # MPX_FIELD_MAX_NODES
 # the reach box of the arm: what the cloud-collision tests crop to
 DEFAULT_LO, DEFAULT_HI, DEFAULT_VOXEL = (-0.9, -0.9, -0.3), (0.9, 0.9, 1.2), 0.03
-
-
-def cloud_operand(who: str, cloud: torch.Tensor, B: Optional[int] = None):
-    """A ``[B,N,3]`` / ``[B,N,4]`` float32 view whose last stride is 1 -> (N, batch stride, point stride) in floats, read
-    in place as ``FrankaCollisionSampler.check_cloud`` reads it."""
-    if cloud.ndim != 3 or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32 or (B is not None and cloud.size(0) != B):
-        raise _lib.MpxError(f"{who}: cloud must be float32 [B{'' if B is None else '=' + str(B)},N,3] or [B,N,4], "
-                            f"got {cloud.dtype} {tuple(cloud.shape)}")
-    N = cloud.size(1)
-    if N > 0 and cloud.size(0) > 0 and cloud.stride(2) != 1:
-        raise _lib.MpxError(f"{who}: the cloud's last dimension must have stride 1")
-    # (a one-row view, or an empty batch, may carry any row stride)
-    ps = cloud.stride(1) if N > 1 and cloud.size(0) > 0 else max(cloud.stride(1), 3)
-    return N, cloud.stride(0), ps
 
 
 def make_grid(lo: Sequence[float], hi: Sequence[float], voxel: float, truncation: float) -> _lib.FieldGrid:
@@ -84,10 +71,7 @@ class CloudField:
         N, bs, ps = cloud_operand("CloudField.build", cloud)
         B = cloud.size(0)
         g = grid if grid is not None else make_grid(lo, hi, voxel, truncation)
-        cn = None
-        if counts is not None:
-            assert counts.shape == (B,)
-            cn = _lib.i32c(counts)
+        cn = counts_operand(counts, B)
         shape = (B, max(g.nz, 0), max(g.ny, 0), max(g.nx, 0))
         if out is None:
             nodes = shape[1] * shape[2] * shape[3]

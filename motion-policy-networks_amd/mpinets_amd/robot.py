@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import franka_tables as ft
+from ._operands import cloud_operand, counts_operand, limits_operand, scratch_for
 
 
 class _SE3Lite:
@@ -129,6 +130,42 @@ def _ik_sphere_table(device: torch.device, with_base_link: bool):
     return _ik_tables[key]
 
 
+def _ik_options(who: str, options: dict, check_self: bool) -> _lib.IkOptions:
+    """Keyword options of an IK entry over ``IK_DEFAULTS`` and its ``check_self`` default; ``lambda`` is ``damping``'s C name."""
+    opts = IK_DEFAULTS
+    if options:  # (most calls pass none: nothing to merge)
+        opts = dict(IK_DEFAULTS, check_self=check_self)
+        if "lambda" in options:
+            options["damping"] = options.pop("lambda")
+        if not options.keys() <= opts.keys():
+            raise TypeError(f"{who}: unknown option(s) {sorted(options.keys() - opts.keys())}")
+        opts.update(options)
+        check_self = opts["check_self"]
+    return _lib.IkOptions(int(opts["iterations"]), float(opts["damping"]), float(opts["step_clip"]), float(opts["pos_tol"]),
+                          float(opts["rot_tol"]), float(opts["clearance"]), int(bool(check_self)))
+
+
+def _ik_outputs(B: int, dev: torch.device, return_all: bool):  # -> q, status, all_q, all_status (None without return_all)
+    return (torch.empty((B, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty((B, IK_SEEDS, 7), dtype=torch.float32, device=dev) if return_all else None,
+            torch.empty((B, IK_SEEDS), dtype=torch.int32, device=dev) if return_all else None)
+
+
+def _primitive_operands(cuboids, cylinders, B: Optional[int] = None):
+    """-> cub frames, dims, M1, cyl frames, radii, heights, M2; the caller holds the tensors (maybe copies) until its call returns."""
+    cf = cd = yf = yr = yh = None
+    M1 = M2 = 0
+    if cuboids is not None:
+        assert B is None or cuboids.centers.size(0) == B
+        M1 = cuboids.centers.size(1)
+        cf, cd = cuboids.inv_frames, _lib.f32c(cuboids.dims)
+    if cylinders is not None:
+        assert B is None or cylinders.centers.size(0) == B
+        M2 = cylinders.centers.size(1)
+        yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
+    return cf, cd, M1, yf, yr, yh, M2
+
+
 def franka_ik(target_poses: torch.Tensor, cuboids=None, cylinders=None, q_init: Optional[torch.Tensor] = None,
               limits=ft.JOINT_LIMITS_REAL, seed: int = 0, env_offset: int = 0, with_base_link: bool = False,
               return_all: bool = False, finger: float = ft.FINGER_OPENING, **options):
@@ -150,47 +187,19 @@ def franka_ik(target_poses: torch.Tensor, cuboids=None, cylinders=None, q_init: 
     assert target_poses.ndim == 3 and target_poses.shape[1:] == (4, 4)
     B, dev = target_poses.size(0), target_poses.device
     tp = _lib.f32c(target_poses)
-    # float32 limits rounded INWARD: a joint left on a limit by the kernel's clamp is inside the limits as passed
-    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
-    assert lim.shape == (7, 2)
-    qi = None
-    if q_init is not None:
-        assert q_init.shape == (B, 7)
-        qi = _lib.f32c(q_init)
-    opts = dict(IK_DEFAULTS, check_self=cuboids is not None or cylinders is not None)
-    if "lambda" in options:
-        options["damping"] = options.pop("lambda")
-    unknown = set(options) - set(opts)
-    if unknown:
-        raise TypeError(f"franka_ik: unknown option(s) {sorted(unknown)}")
-    opts.update(options)
-    copt = _lib.IkOptions(int(opts["iterations"]), float(opts["damping"]), float(opts["step_clip"]), float(opts["pos_tol"]),
-                          float(opts["rot_tol"]), float(opts["clearance"]), int(bool(opts["check_self"])))
-    cf = cd = yf = yr = yh = sc = sr = sl = None
-    M1 = M2 = S = 0
-    if cuboids is not None:
-        assert cuboids.centers.size(0) == B
-        M1 = cuboids.centers.size(1)
-        cf, cd = cuboids.inv_frames, _lib.f32c(cuboids.dims)
-    if cylinders is not None:
-        assert cylinders.centers.size(0) == B
-        M2 = cylinders.centers.size(1)
-        yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
-    if M1 + M2 > 0:
-        sc, sr, sl = _ik_sphere_table(dev, with_base_link)
-        S = int(sc.size(0))
-    q = torch.empty((B, 7), dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    all_q = torch.empty((B, IK_SEEDS, 7), dtype=torch.float32, device=dev) if return_all else None
-    all_status = torch.empty((B, IK_SEEDS), dtype=torch.int32, device=dev) if return_all else None
+    lim = limits_operand(limits, dev)
+    assert q_init is None or q_init.shape == (B, 7)
+    qi = None if q_init is None else _lib.f32c(q_init)
+    copt = _ik_options("franka_ik", options, check_self=cuboids is not None or cylinders is not None)
+    cf, cd, M1, yf, yr, yh, M2 = _primitive_operands(cuboids, cylinders, B)
+    sc, sr, sl = _ik_sphere_table(dev, with_base_link) if M1 + M2 > 0 else (None, None, None)
+    S = 0 if sc is None else int(sc.size(0))
+    q, status, all_q, all_status = _ik_outputs(B, dev, return_all)
     _lib.call("mpx_franka_ik", _lib.ptr(tp), B, float(finger), _lib.ptr(lim), _lib.ptr(qi), _lib.ptr(sc), _lib.ptr(sr),
               _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
               ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(q), _lib.ptr(status),
               _lib.ptr(all_q), _lib.ptr(all_status))
     return (q, status, all_q, all_status) if return_all else (q, status)
-
-
-_ik_cloud_scratch: dict = {}
 
 
 def franka_ik_cloud(target_poses: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
@@ -207,42 +216,21 @@ def franka_ik_cloud(target_poses: torch.Tensor, cloud: torch.Tensor, counts: Opt
     :param point_radius: radius given to every point (>= 0)
     :returns: what ``franka_ik`` returns; bit 1 of ``all_status`` is the cloud verdict of a converged start (0 on the
         others, which are not tested)."""
-    from .field import cloud_operand
-
-    opts = dict(IK_DEFAULTS, check_self=True)
-    if "lambda" in options:
-        options["damping"] = options.pop("lambda")
-    unknown = set(options) - set(opts)
-    if unknown:
-        raise TypeError(f"franka_ik_cloud: unknown option(s) {sorted(unknown)}")
-    opts.update(options)
+    copt = _ik_options("franka_ik_cloud", options, check_self=True)
     _lib.require_cuda(target_poses, q_init, cloud, counts)
     assert target_poses.ndim == 3 and target_poses.shape[1:] == (4, 4)
     B, dev = target_poses.size(0), target_poses.device
     tp = _lib.f32c(target_poses)
-    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
-    assert lim.shape == (7, 2)
-    qi = None
-    if q_init is not None:
-        assert q_init.shape == (B, 7)
-        qi = _lib.f32c(q_init)
-    copt = _lib.IkOptions(int(opts["iterations"]), float(opts["damping"]), float(opts["step_clip"]), float(opts["pos_tol"]),
-                          float(opts["rot_tol"]), float(opts["clearance"]), int(bool(opts["check_self"])))
+    lim = limits_operand(limits, dev)
+    assert q_init is None or q_init.shape == (B, 7)
+    qi = None if q_init is None else _lib.f32c(q_init)
     N, cbs, cps = cloud_operand("franka_ik_cloud", cloud, B)
-    cn = None
-    if counts is not None:
-        assert counts.shape == (B,)
-        cn = _lib.i32c(counts)
+    cn = counts_operand(counts, B)
     sc, sr, sl = _ik_sphere_table(dev, with_base_link)
     S = int(sc.size(0))
-    q = torch.empty((B, 7), dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    all_q = torch.empty((B, IK_SEEDS, 7), dtype=torch.float32, device=dev) if return_all else None
-    all_status = torch.empty((B, IK_SEEDS), dtype=torch.int32, device=dev) if return_all else None
+    q, status, all_q, all_status = _ik_outputs(B, dev, return_all)
     nbytes = int(_lib.load().mpx_franka_ik_cloud_scratch(B))
-    buf = _ik_cloud_scratch.get(dev.index)  # one growing buffer per GPU: the call's work is ordered on the stream
-    if buf is None or buf.numel() < nbytes:
-        buf = _ik_cloud_scratch[dev.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    buf = scratch_for(dev, nbytes)
     _lib.call("mpx_franka_ik_cloud", _lib.ptr(tp), B, float(finger), _lib.ptr(lim), _lib.ptr(qi), _lib.ptr(sc), _lib.ptr(sr),
               _lib.ptr(sl), S, _lib.ptr(cloud) if N else None, cbs, cps, N, _lib.ptr(cn), float(point_radius),
               ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(q), _lib.ptr(status), _lib.ptr(all_q),
@@ -255,6 +243,24 @@ PLAN_BIT_ENV_HIT, PLAN_BIT_SELF_HIT, PLAN_BIT_JERK = 1, 2, 4  # per-candidate bi
 # MPX_PLAN_DEFAULT_* (include/mpinets_hip.h; profiles/plan_timing.md holds the table behind iterations / step / smooth_weight)
 PLAN_DEFAULTS = dict(candidates=8, iterations=20, step=2e-4, smooth_weight=20.0, epsilon=0.05, spread=0.5, substeps=4,
                      check_margin=1e-4, clearance=0.0, max_jerk=0.15, check_self=True)
+
+
+def _plan_options(who: str, options: dict):
+    """The keyword options of a planning entry over ``PLAN_DEFAULTS`` (which holds the planners' ``check_self`` default) ->
+    the ``_lib.PlanOptions`` and the merged dict, read-only: its values as the caller gave them, not yet float32."""
+    if not options.keys() <= PLAN_DEFAULTS.keys():
+        raise TypeError(f"{who}: unknown option(s) {sorted(options.keys() - PLAN_DEFAULTS.keys())}")
+    o = dict(PLAN_DEFAULTS, **options) if options else PLAN_DEFAULTS  # (most calls pass none: nothing to merge)
+    return _lib.PlanOptions(int(o["candidates"]), int(o["iterations"]), float(o["step"]), float(o["smooth_weight"]),
+                            float(o["epsilon"]), float(o["spread"]), int(o["substeps"]), float(o["check_margin"]),
+                            float(o["clearance"]), float(o["max_jerk"]), int(bool(o["check_self"]))), o
+
+
+def _plan_outputs(B: int, K: int, T: int, dev: torch.device, return_all: bool):  # -> traj, status, choice, all_traj, all_status
+    return (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev) if return_all else None,
+            torch.empty((B, K, T, 7), dtype=torch.float32, device=dev) if return_all else None,
+            torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None)
 
 
 def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
@@ -280,34 +286,12 @@ def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylin
     assert q_start.ndim == 2 and q_start.size(1) == 7 and q_goal.shape == q_start.shape
     B, dev = q_start.size(0), q_start.device
     qs, qg = _lib.f32c(q_start), _lib.f32c(q_goal)
-    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
-    assert lim.shape == (7, 2)
-    unknown = set(options) - set(PLAN_DEFAULTS)
-    if unknown:
-        raise TypeError(f"franka_plan: unknown option(s) {sorted(unknown)}")
-    o = dict(PLAN_DEFAULTS, **options)
-    copt = _lib.PlanOptions(int(o["candidates"]), int(o["iterations"]), float(o["step"]), float(o["smooth_weight"]),
-                            float(o["epsilon"]), float(o["spread"]), int(o["substeps"]), float(o["check_margin"]),
-                            float(o["clearance"]), float(o["max_jerk"]), int(bool(o["check_self"])))
-    cf = cd = yf = yr = yh = sc = sr = sl = None
-    M1 = M2 = S = 0
-    if cuboids is not None:
-        assert cuboids.centers.size(0) == B
-        M1 = cuboids.centers.size(1)
-        cf, cd = cuboids.inv_frames, _lib.f32c(cuboids.dims)
-    if cylinders is not None:
-        assert cylinders.centers.size(0) == B
-        M2 = cylinders.centers.size(1)
-        yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
-    if M1 + M2 > 0:
-        sc, sr, sl = _ik_sphere_table(dev, with_base_link)
-        S = int(sc.size(0))
-    K = max(int(o["candidates"]), 0)
-    traj = torch.empty((B, T, 7), dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    choice = torch.empty(B, dtype=torch.int32, device=dev) if return_all else None
-    all_traj = torch.empty((B, K, T, 7), dtype=torch.float32, device=dev) if return_all else None
-    all_status = torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None
+    lim = limits_operand(limits, dev)
+    copt, o = _plan_options("franka_plan", options)
+    cf, cd, M1, yf, yr, yh, M2 = _primitive_operands(cuboids, cylinders, B)
+    sc, sr, sl = _ik_sphere_table(dev, with_base_link) if M1 + M2 > 0 else (None, None, None)
+    S = 0 if sc is None else int(sc.size(0))
+    traj, status, choice, all_traj, all_status = _plan_outputs(B, max(int(o["candidates"]), 0), T, dev, return_all)
     _lib.call("mpx_franka_plan", _lib.ptr(qs), _lib.ptr(qg), B, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
               _lib.ptr(sr), _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
               ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(traj), _lib.ptr(status),
@@ -316,7 +300,6 @@ def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylin
 
 
 PLAN_CLOUD_SCRATCH_BYTES = 256 << 20  # ``franka_plan_cloud`` runs a large batch in slabs of problems whose scratch stays below this
-_plan_cloud_scratch: dict = {}
 
 
 def plan_cloud_truncation(point_radius: float = 0.0, clearance: float = 0.0, epsilon: float = PLAN_DEFAULTS["epsilon"],
@@ -345,26 +328,16 @@ def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.
     :param point_radius: radius given to every point (>= 0), in the cost and in the validity test
     :returns: what ``franka_plan`` returns.  A batch whose scratch would exceed ``PLAN_CLOUD_SCRATCH_BYTES`` runs in slabs
         of problems (the draws are keyed by the global row: the result does not depend on the slabbing)."""
-    from .field import DEFAULT_VOXEL, CloudField, cloud_operand
+    from .field import DEFAULT_VOXEL, CloudField
 
     _lib.require_cuda(q_start, q_goal, cloud, counts)
     assert q_start.ndim == 2 and q_start.size(1) == 7 and q_goal.shape == q_start.shape
     B, dev = q_start.size(0), q_start.device
     qs, qg = _lib.f32c(q_start), _lib.f32c(q_goal)
-    lim = torch.from_numpy(ft.limits_float32_inward(limits.detach().cpu().numpy() if torch.is_tensor(limits) else limits)).to(dev)
-    assert lim.shape == (7, 2)
-    unknown = set(options) - set(PLAN_DEFAULTS)
-    if unknown:
-        raise TypeError(f"franka_plan_cloud: unknown option(s) {sorted(unknown)}")
-    o = dict(PLAN_DEFAULTS, **options)
-    copt = _lib.PlanOptions(int(o["candidates"]), int(o["iterations"]), float(o["step"]), float(o["smooth_weight"]),
-                            float(o["epsilon"]), float(o["spread"]), int(o["substeps"]), float(o["check_margin"]),
-                            float(o["clearance"]), float(o["max_jerk"]), int(bool(o["check_self"])))
+    lim = limits_operand(limits, dev)
+    copt, o = _plan_options("franka_plan_cloud", options)
     N, cbs, cps = cloud_operand("franka_plan_cloud", cloud, B)
-    cn = None
-    if counts is not None:
-        assert counts.shape == (B,)
-        cn = _lib.i32c(counts)
+    cn = counts_operand(counts, B)
     if field is None:
         field = CloudField.build(cloud, cn, truncation=plan_cloud_truncation(point_radius, o["clearance"], o["epsilon"],
                                                                             DEFAULT_VOXEL, with_base_link))
@@ -374,11 +347,7 @@ def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.
     sc, sr, sl = _ik_sphere_table(dev, with_base_link)
     S = int(sc.size(0))
     K = max(int(o["candidates"]), 0)
-    traj = torch.empty((B, T, 7), dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    choice = torch.empty(B, dtype=torch.int32, device=dev) if return_all else None
-    all_traj = torch.empty((B, K, T, 7), dtype=torch.float32, device=dev) if return_all else None
-    all_status = torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None
+    traj, status, choice, all_traj, all_status = _plan_outputs(B, K, T, dev, return_all)
     lib = _lib.load()
     per = int(lib.mpx_franka_plan_cloud_scratch(1, int(T), K, int(o["substeps"])))
     slab = max(B, 1) if per <= 0 else max(1, min(max(B, 1), PLAN_CLOUD_SCRATCH_BYTES // per))  # (per <= 0: the call refuses)
@@ -386,9 +355,7 @@ def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.
     for b0 in range(0, max(B, 1), slab):
         n = min(slab, B - b0)
         nbytes = max(int(lib.mpx_franka_plan_cloud_scratch(n, int(T), K, int(o["substeps"]))), 0)
-        buf = _plan_cloud_scratch.get(dev.index)
-        if buf is None or buf.numel() < nbytes:
-            buf = _plan_cloud_scratch[dev.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        buf = scratch_for(dev, nbytes)  # (fetched per call: CloudField.build above, or another entry, may have regrown it)
 
         def at(t, row):  # pointer to row b0 of a [B, ...] operand
             return None if t is None else t.data_ptr() + b0 * row * t.element_size()
@@ -582,17 +549,7 @@ class FrankaCollisionSampler:
         qc = _lib.f32c(q)
         flags = torch.zeros(B, dtype=torch.int32, device=q.device)
         msdf = torch.empty((B, T, self.num_spheres), dtype=torch.float32, device=q.device) if return_sdf else None
-        cf = cd = yf = yr = yh = None
-        M1 = M2 = 0
-        keep = []
-        if cuboids is not None:
-            M1 = cuboids.centers.size(1)
-            cf, cd = cuboids.inv_frames, _lib.f32c(cuboids.dims)
-            keep.append(cd)
-        if cylinders is not None:
-            M2 = cylinders.centers.size(1)
-            yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
-            keep += [yr, yh]
+        cf, cd, M1, yf, yr, yh, M2 = _primitive_operands(cuboids, cylinders)
         _lib.call("mpx_franka_collision", _lib.ptr(qc), B, T, self.finger, _lib.ptr(self.centers),
                   _lib.ptr(self.radii), _lib.ptr(self.links), self.num_spheres, _lib.ptr(cf), _lib.ptr(cd), M1,
                   _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2, _lib.ptr(flags), _lib.ptr(msdf))
@@ -621,23 +578,15 @@ class FrankaCollisionSampler:
             q = q.unsqueeze(1)
         _lib.require_cuda(q, cloud, counts)
         B, T, _ = q.shape
-        if cloud.ndim != 3 or cloud.size(0) != B or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32:
-            raise _lib.MpxError(f"check_cloud: cloud must be float32 [B={B},N,3] or [B,N,4], got {cloud.dtype} {tuple(cloud.shape)}")
-        N = cloud.size(1)
-        if N > 0 and B > 0 and cloud.stride(2) != 1:
-            raise _lib.MpxError("check_cloud: the cloud's last dimension must have stride 1")
-        ps = cloud.stride(1) if N > 1 else max(cloud.stride(1), 3)  # (a one-row view may carry any row stride)
+        N, cbs, ps = cloud_operand("check_cloud", cloud, B, empty_batch_any_stride=False)
         qc = _lib.f32c(q)
-        cn = None
-        if counts is not None:
-            assert counts.shape == (B,)
-            cn = _lib.i32c(counts)
+        cn = counts_operand(counts, B)
         flags = torch.zeros(B, dtype=torch.int32, device=q.device)
         S = self.num_spheres
         dist = torch.empty((B, T, S), dtype=torch.float32, device=q.device) if return_distance else None
         near = torch.empty((B, T, S), dtype=torch.int32, device=q.device) if return_nearest else None
         _lib.call("mpx_franka_cloud_collision", _lib.ptr(qc), B, T, self.finger, _lib.ptr(self.centers),
-                  _lib.ptr(self.radii), _lib.ptr(self.links), S, _lib.ptr(cloud), cloud.stride(0), ps, N,
+                  _lib.ptr(self.radii), _lib.ptr(self.links), S, _lib.ptr(cloud), cbs, ps, N,
                   _lib.ptr(cn), float(point_radius), float(clearance), _lib.ptr(flags), _lib.ptr(dist), _lib.ptr(near))
         out = (flags != 0,) + ((dist,) if return_distance else ()) + ((near,) if return_nearest else ())
         return out if len(out) > 1 else out[0]
@@ -657,23 +606,15 @@ class FrankaCollisionSampler:
             q = q.unsqueeze(1)
         _lib.require_cuda(q, cloud, counts, active)
         B, T, _ = q.shape
-        if cloud.ndim != 3 or cloud.size(0) != B or cloud.size(2) not in (3, 4) or cloud.dtype != torch.float32:
-            raise _lib.MpxError(f"check_cloud_each: cloud must be float32 [B={B},N,3] or [B,N,4], got {cloud.dtype} {tuple(cloud.shape)}")
-        N = cloud.size(1)
-        if N > 0 and B > 0 and cloud.stride(2) != 1:
-            raise _lib.MpxError("check_cloud_each: the cloud's last dimension must have stride 1")
-        ps = cloud.stride(1) if N > 1 else max(cloud.stride(1), 3)  # (a one-row view may carry any row stride)
+        N, cbs, ps = cloud_operand("check_cloud_each", cloud, B, empty_batch_any_stride=False)
         qc = _lib.f32c(q)
-        cn = None
-        if counts is not None:
-            assert counts.shape == (B,)
-            cn = _lib.i32c(counts)
+        cn = counts_operand(counts, B)
         ac = None
         if active is not None:
             assert active.shape == (B, T)
             ac = _lib.i32c(active)
         hit = torch.empty((B, T), dtype=torch.int32, device=q.device)
         _lib.call("mpx_franka_cloud_collision_each", _lib.ptr(qc), B, T, self.finger, _lib.ptr(self.centers),
-                  _lib.ptr(self.radii), _lib.ptr(self.links), self.num_spheres, _lib.ptr(cloud), cloud.stride(0), ps, N,
+                  _lib.ptr(self.radii), _lib.ptr(self.links), self.num_spheres, _lib.ptr(cloud), cbs, ps, N,
                   _lib.ptr(cn), float(point_radius), float(clearance), _lib.ptr(ac), _lib.ptr(hit))
         return hit != 0

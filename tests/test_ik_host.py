@@ -160,6 +160,49 @@ def test_python_entry_points_refuse_cpu_tensors_and_unknown_options():
     assert inspect.signature(scenes.make_problem_batch).parameters["collision_free"].default is False
 
 
+def test_option_helpers_merge_over_the_defaults(monkeypatch):
+    """``robot._ik_options`` / ``_plan_options``: the defaults, the ``lambda`` alias, the refusal of unknown names, and the
+    ``check_self`` default each IK entry hands over (the entries run on CPU tensors with the library call recorded)."""
+    from types import SimpleNamespace
+
+    from mpinets_amd import _lib, robot
+
+    def fields(c):
+        return {n: getattr(c, n) for n, _ in c._fields_}
+
+    f32 = lambda d: {k: (np.float32(v) if isinstance(v, float) else int(v)) for k, v in d.items()}  # noqa: E731
+    ik = fields(robot._ik_options("franka_ik", {}, check_self=False))
+    want = dict(robot.IK_DEFAULTS, check_self=False)
+    want["lambda_"] = want.pop("damping")
+    assert ik == f32(want)
+    copt, o = robot._plan_options("franka_plan", {})
+    assert o == robot.PLAN_DEFAULTS and fields(copt) == f32(robot.PLAN_DEFAULTS)
+    assert robot._plan_options("franka_plan_cloud", dict(candidates=3, clearance=0.05))[1] == dict(robot.PLAN_DEFAULTS, candidates=3, clearance=0.05)
+    assert robot._plan_options("franka_plan", {"check_self": False})[0].check_self == 0
+    assert robot._ik_options("franka_ik", {"check_self": True}, False).check_self == 1
+    assert robot._ik_options("franka_ik", {"lambda": 0.25}, False).lambda_ == 0.25
+    assert robot._ik_options("franka_ik_cloud", {"damping": 0.5, "iterations": 7}, True).iterations == 7
+    for helper, who, more in ((robot._ik_options, "franka_ik", (True,)), (robot._ik_options, "franka_ik_cloud", (True,)),
+                              (robot._plan_options, "franka_plan", ()), (robot._plan_options, "franka_plan_cloud", ())):
+        with pytest.raises(TypeError, match=rf"^{who}: unknown option\(s\) \['bogus', 'zeta'\]$"):
+            helper(who, {"zeta": 1, "bogus": 2}, *more)
+    assert robot._plan_options("franka_plan", {"iterations": 3})[1] is not robot.PLAN_DEFAULTS  # (the defaults are never written)
+
+    seen = {}
+    monkeypatch.setattr(_lib, "require_cuda", lambda *t: None)
+    monkeypatch.setattr(_lib, "call", lambda name, *a: seen.update({name: [x._obj for x in a if hasattr(x, "_obj")][0]}))
+    poses = torch.eye(4)[None]
+    robot.franka_ik(poses)
+    assert seen["mpx_franka_ik"].check_self == 0
+    box = SimpleNamespace(centers=torch.zeros(1, 2, 3), inv_frames=torch.zeros(1, 2, 16), dims=torch.ones(1, 2, 3))
+    robot.franka_ik(poses, box)
+    assert seen["mpx_franka_ik"].check_self == 1
+    robot.franka_ik(poses, box, check_self=False)
+    assert seen["mpx_franka_ik"].check_self == 0
+    robot.franka_ik_cloud(poses, torch.zeros(1, 5, 3))
+    assert seen["mpx_franka_ik_cloud"].check_self == 1
+
+
 def test_ik_kernel_uses_no_scratch():
     """The 6x6 solve and the seven joint frames live in registers: no private segment, no spills."""
     from test_code_objects import LIB, NO_SCRATCH_FIELDS, demangle_head, kernel_metadata
