@@ -546,8 +546,8 @@ int mpx_linear_segmax_bf16x3(const float *x, int ldx, const void *w_pairs, const
  *   mpx_pool_wgrad: dw[c,k] = sum_q gz[q,c] * x[arg[q,c], k], db[c] = sum_q gz[q,c]  (db NULL or == dw + C*K: one fixed-order
  *                   reduction over the query splits; scratch = mpx_pool_wgrad_scratch(Q, C, K) floats);
  *   mpx_pool_dgrad: gx[r,k] = below'(x[r,k]) * sum_{c: arg[q,c] == r} gz[q,c] * w[c,k] for EVERY row r of every segment (no
- *                   zero fill needed; `below` = activation code of the layer that produced x, 0 = none; max_rows = the
- *                   longest segment the caller expects (a hint, any value works); C <= 65535).
+ *                   zero fill needed; `below` = activation code of the layer that produced x, 0 = none; max_rows: reserved,
+ *                   ignored; C <= 65535).
  * fp32 FMAs in a fixed order: deterministic; the same sums as mpx_segment_max_grad_act + mpx_linear_wgrad / mpx_linear_dact
  * in another summation order.  (Reference: the autograd of pointnet2_ops' QueryAndGroup + max_pool2d, model.py:366-383.) */
 int64_t mpx_pool_wgrad_scratch(int64_t Q, int C, int K);

@@ -22,8 +22,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from .pointnet2 import (PRECISIONS, DerivedWeights, PointnetSAModule, SplitWeights, groupnorm_leaky, groupnorm_leaky_train,
-                        launch_sa, linear, linear_train, linear_x3, mlp_chain_train, sa_mlp_factored, use_factored)
+from .pointnet2 import (PRECISIONS, DerivedWeights, PointnetSAModule, SplitWeights, groupnorm_leaky, launch_sa, linear,
+                        linear_x3, sa_mlp_factored, use_factored)
+from .train_ops import groupnorm_leaky_train, linear_train, mlp_chain_train, sa_module_train, segment_offsets
 from .utils import unnormalize_franka_joints
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
@@ -196,8 +197,6 @@ class MPiNetsPointNet(nn.Module):
     def forward_train(self, point_cloud: torch.Tensor, aux: Optional[dict] = None) -> torch.Tensor:
         """Differentiable forward (training_step, model.py:185-240): sampling / neighbour search / grouping /
         max-pool are this engine's kernels (no padding rows), the dense layers are torch ops under autograd."""
-        from .pointnet2 import sa_module_train, segment_offsets
-
         pc = _lib.f32c(point_cloud)
         B, N, _ = pc.shape
         dev = pc.device

@@ -26,7 +26,7 @@ def small_batch(B, seed):
 
 
 def test_segment_ops_match_torch():
-    from mpinets_amd.pointnet2 import _SegmentMax
+    from mpinets_amd.train_ops import _SegmentMax
 
     g = torch.Generator(device="cpu").manual_seed(0)
     lens = torch.randint(1, 40, (50,), generator=g)
@@ -142,7 +142,7 @@ def test_gradient_step_decreases_loss_as_predicted():
 
 def test_linear_train_matches_torch_autograd():
     """Hand-written dense forward/backward (mpx_linear, mpx_act_backward, mpx_linear_wgrad) vs torch in float64."""
-    from mpinets_amd.pointnet2 import linear_train
+    from mpinets_amd.train_ops import linear_train
 
     rng = np.random.default_rng(0)
     for (M, N, K, act) in [(300, 64, 4, 1), (1000, 128, 67, 1), (129, 7, 128, 0), (4096, 512, 259, 1), (77, 32, 7, 2),
@@ -178,16 +178,17 @@ def test_mlp_chain_is_the_per_layer_backward_without_the_activation_passes(poole
     """``mlp_chain_train`` (one autograd node for a stack of dense layers; the activation's elementwise backward rides in
     the input-gradient GEMM's epilogue, mpx_linear_dact, or in the max-pool's backward, mpx_segment_max_grad_act) vs the
     per-layer nodes (``linear_train`` + ``_SegmentMax``): the same kernels' arithmetic per element -- gradients equal bit
-    for bit at sizes where both take the 128 x 128 tile GEMM -- and vs torch autograd in float64.
+    for bit at sizes where both take the 128 x 128 tile GEMM -- and vs torch autograd in float64.  The pooled stacks also
+    run in ``bf16x3`` against their own fp32 run.
     Widths as in the set-abstraction modules (67 -> 128 -> 128 -> 256; a 7-wide output for the decoder's shape)."""
-    from mpinets_amd import pointnet2
-    from mpinets_amd.pointnet2 import _SegmentMax, linear_train, mlp_chain_train
+    from mpinets_amd import train_ops
+    from mpinets_amd.train_ops import _SegmentMax, linear_train, mlp_chain_train
 
     # "sparse" (the default route): the pooled stack's last layer goes through mpx_pool_wgrad / mpx_pool_dgrad -- the same
     # sums in another order, so that case is held to the float64 reference only; True = the dense route (bit-equal)
     sparse = pooled == "sparse"
     pooled = bool(pooled)
-    monkeypatch.setattr(pointnet2, "SPARSE_POOL_BACKWARD", sparse)
+    monkeypatch.setattr(train_ops, "SPARSE_POOL_BACKWARD", sparse)
     rng = np.random.default_rng(3)
     M = 3000
     widths, acts = ((67, 128, 128, 256), (1, 1, 1)) if pooled else ((132, 512, 64, 7), (2, 2, 0))
@@ -204,12 +205,12 @@ def test_mlp_chain_is_the_per_layer_backward_without_the_activation_passes(poole
     n_out = (offsets.numel() - 1) if pooled else M
     g = mk(n_out, widths[-1])
 
-    def run(kind):
+    def run(kind, precision="fp32"):
         x = x0.clone().requires_grad_(True)
         w = [t.clone().requires_grad_(True) for t in ws]
         b = [t.clone().requires_grad_(True) for t in bs]
         if kind == "chain":
-            y = mlp_chain_train(x, list(zip(w, b)), acts, offsets=offsets)
+            y = mlp_chain_train(x, list(zip(w, b)), acts, offsets=offsets, precision=precision)
         else:
             h = x
             for i in range(3):
@@ -226,6 +227,12 @@ def test_mlp_chain_is_the_per_layer_backward_without_the_activation_passes(poole
             assert (a - b_).abs().max() <= 2e-5 * max(b_.abs().max().item(), 1e-6) * np.sqrt(M / 64)
         else:
             assert torch.equal(a, b_)
+    if pooled:
+        # the same stack in ``bf16x3`` (every layer here is large enough for the split-bf16 entries: segmax, dact, wgrad) vs
+        # its own fp32 run, at the bar of test_split_bf16_chain_follows_the_fp32_chain
+        y_x, g_x = run("chain", "bf16x3")
+        assert (y_x - y_c).abs().max() <= 1e-5 * y_c.abs().max()
+        assert max(_rel_l2(a, r) for a, r in zip(g_x, g_c)) <= 2e-3 and not torch.equal(g_x[1], g_c[1])
     # float64 reference
     xd = x0.double().requires_grad_(True)
     wd = [t.double().requires_grad_(True) for t in ws]
@@ -251,7 +258,7 @@ def test_pack_rows_and_its_scatter_backward_match_torch_indexing(C, N, npoint, n
     """mpx_pack_rows_ld / mpx_pack_rows_grad_ld (QueryAndGroup over the distinct neighbours, rows at a 16-byte pitch) vs plain
     torch indexing and its autograd: queries with 0 hits (one row: slot 0), with more than 64 rows (two id windows of the
     kernel), feature widths of 1 (the first module), 64 (the second, 68-float rows: not a multiple of the wave) and 5."""
-    from mpinets_amd.pointnet2 import _PackRows, segment_offsets
+    from mpinets_amd.train_ops import _PackRows, segment_offsets
 
     B = 3
     rng = np.random.default_rng(C * 100 + N)
@@ -423,7 +430,7 @@ def test_split_bf16_chain_follows_the_fp32_chain():
     the same stack in fp32: outputs within 1e-5 of the largest; every gradient tensor within 2e-3 in relative L2 -- a few
     arg-max rows / ReLU signs of values within 1e-5 of a tie may flip between the two arithmetics, which moves single
     elements, so the bound is on the norm (the kernels themselves are pinned to float64 in the test above)."""
-    from mpinets_amd.pointnet2 import mlp_chain_train
+    from mpinets_amd.train_ops import mlp_chain_train
 
     rng = np.random.default_rng(5)
     M = 5000
@@ -489,7 +496,7 @@ def test_training_step_in_split_bf16_matches_the_fp32_step():
 
 
 def test_groupnorm_leaky_backward_matches_torch():
-    from mpinets_amd.pointnet2 import groupnorm_leaky_train
+    from mpinets_amd.train_ops import groupnorm_leaky_train
 
     torch.manual_seed(3)
     for (M, C) in [(7, 4096), (256, 2048), (3, 64)]:

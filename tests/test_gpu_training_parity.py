@@ -96,7 +96,7 @@ WGRAD_TARGET = 1024     # csrc/dense_grad.hip:272 (S = cdiv(1024, tiles))
 PB_KC = 64              # csrc/train_ops.hip:165 (columns per pool_wgrad task)
 POOL_TARGET = 4096      # csrc/train_ops.hip:368 (S = cdiv(4096, blocks))
 POOL_MIN_Q = 8          # csrc/train_ops.hip:369 (>= 8 queries per split)
-X3_MIN_M, X3_MIN_N, X3_MIN_K = 1024, 128, 16  # pointnet2.py:473 (_MLPChainFn._use_x3)
+X3_MIN_M, X3_MIN_N, X3_MIN_K = 1024, 128, 16  # train_ops._MLPChainFn._use_x3
 
 
 def chain_u(n):
@@ -126,7 +126,7 @@ def pool_wgrad_splits(Q, C, K):  # csrc/train_ops.hip:366
     return max(1, min(S, 65535))
 
 
-def use_x3(x3, M, N, K):  # pointnet2.py:473
+def use_x3(x3, M, N, K):  # train_ops._MLPChainFn._use_x3
     return bool(x3) and M >= X3_MIN_M and N >= X3_MIN_N and K >= X3_MIN_K
 
 
@@ -147,7 +147,7 @@ def training_gemms(B, precision, R1, R2):
     / weight-gradient routes.  R1, R2: packed rows of SA1 / SA2 (data: B * npoint <= R <= B * npoint * nsample)."""
     x3 = precision == "bf16x3"
     out = []
-    for st, li, N, K in HEAD_LINEARS:  # _LinearFn (pointnet2.py:307): forward and dX through linear(), dW mpx_linear_wgrad
+    for st, li, N, K in HEAD_LINEARS:  # train_ops._LinearFn: forward and dX through linear(), dW mpx_linear_wgrad
         Np, Kp = _p4(N), _p4(K)
         out.append(dict(stage=st, layer=li, M=B, N=Np, K=Kp, fwd=linear_route(B, Np, Kp), dx=linear_route(B, Kp, Np),
                         wgrad=("linear", wgrad_splits(B, Np, Kp), wgrad_tile(Np, Kp)), x3=False, head=True))
@@ -155,10 +155,10 @@ def training_gemms(B, precision, R1, R2):
         for li, (N, K) in enumerate(layers):
             Np, Kp = _p4(N), _p4(K)
             dx = None if (st == "feature_encoder" and li == 0) else (
-                "split-K" if linear_route(B, Kp, Np) == "split-K" else "dact")  # pointnet2.py:603 (mpx_linear_workspace > 0)
+                "split-K" if linear_route(B, Kp, Np) == "split-K" else "dact")  # the skinny route of _MLPChainFn.backward
             out.append(dict(stage=st, layer=li, M=B, N=Np, K=Kp, fwd=linear_route(B, Np, Kp), dx=dx,
                             wgrad=("linear", wgrad_splits(B, Np, Kp), wgrad_tile(Np, Kp)), x3=False, head=True))
-    for st, layers in POOLED_CHAINS.items():  # _MLPChainFn with the pool (pointnet2.py:477 / :535)
+    for st, layers in POOLED_CHAINS.items():  # _MLPChainFn with the pool (_MLPChainFn.forward / .backward)
         M, Q = {"SA1": (R1, B * NP1), "SA2": (R2, B * NP2), "SA3": (B * NP2, B)}[st]
         for li, (N, K) in enumerate(layers):
             Np, Kp = _p4(N), _p4(K)

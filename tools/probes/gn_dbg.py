@@ -2,7 +2,7 @@ import os, sys
 ROOT = "/root/repo"
 sys.path[:0] = [ROOT, os.path.join(ROOT, "motion-policy-networks_amd")]
 import torch
-from mpinets_amd.pointnet2 import groupnorm_leaky_train
+from mpinets_amd.train_ops import groupnorm_leaky_train
 dev = torch.device("cuda:0")
 torch.manual_seed(3)
 for (M, C) in [(7, 4096), (256, 2048), (64, 2048), (65, 2048), (256, 64)]:
