@@ -29,7 +29,9 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_franka_cloud_collision_each,
+int mpx_version(void); /* 341: the route queries mpx_fps_route, mpx_franka_collision_route, mpx_linear_route, mpx_linear_wgrad_route,
+                          mpx_pool_wgrad_route, mpx_sa_mlp_route (additions only);
+                          340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_franka_cloud_collision_each,
                           mpx_franka_ik_cloud, mpx_franka_ik_cloud_scratch; 340 (unchanged, likewise): mpx_cloud_field_build,
                           mpx_cloud_field_sample, mpx_franka_plan_cloud, mpx_franka_plan_cloud_scratch, struct mpx_field_grid;
                           340 (unchanged, likewise): mpx_cloud_clean,
@@ -681,6 +683,38 @@ int mpx_fps(const float *xyz, int B, int N, int stride, int npoint, int32_t *idx
 #define MPX_VARIANT_COUNT_ 4
 int mpx_set_variant(int what, int value);
 int mpx_get_variant(int what); /* -1: unknown selector */
+
+/* Verification hooks (host calls; nothing is launched and no GPU is needed): the kernel form a launcher takes for a call of
+ * this shape, as the launcher itself computes it (csrc/launch_routes.h -- every launcher plans with these functions and then
+ * dispatches on the plan).  Each writes its fields to `route` (int32, the stated length) and returns 0.
+ *
+ * mpx_fps_route, route[4]: family (0 plain, 1 wave per environment, 2 Morton-culled with 8 waves, 3 culled with 4 waves),
+ * points per lane (the instantiation), threads per workgroup, dynamic LDS bytes.  Reads MPX_VARIANT_FPS as mpx_fps does. */
+int mpx_fps_route(int B, int N, int32_t *route);
+/* route[6]: form (0 nothing to launch, 1 general, 2 one wave per environment, 3 per-environment 256-thread form), pairs per
+ * thread (forms 2, 3: the instantiation), threads per workgroup, waypoints per chunk (forms 2, 3), chunks per environment
+ * (form 1: workgroups of the launch), (waypoint, sphere) pairs of the last chunk (form 1: of the last workgroup).
+ * frames_aligned: both frame pointers are 16-byte aligned.  The flags-only call takes the same route.                  */
+int mpx_franka_collision_route(int B, int T, int S, int M1, int M2, int frames_aligned, int32_t *route);
+/* mpx_linear / mpx_linear_ws, route[3]: form (0 gemv, 1 128 x 128 tiles, 2 split-K, taken by mpx_linear_ws with a workspace),
+ * slices of K, k per slice.  (mpx_linear's row-per-lane form for N = 128, K = 68 and the DMA staging of the tile kernel
+ * also depend on the operands' addresses and strides; they replace form 1 only.)                                        */
+int mpx_linear_route(int M, int N, int K, int32_t *route);
+/* mpx_linear_wgrad / _bf16x3, route[3]: tile (64 or 128), splits over the rows (mpx_linear_wgrad_scratch = splits *
+ * (N K + N) floats; 1: the gradient is written directly when db follows dw), rows per split.                            */
+int mpx_linear_wgrad_route(int M, int N, int K, int32_t *route);
+/* mpx_pool_wgrad, route[1]: splits over the queries (mpx_pool_wgrad_scratch = splits * (C K + C) floats).              */
+int mpx_pool_wgrad_route(int64_t Q, int C, int K, int32_t *route);
+/* The grouped-MLP entries mpx_sa_mlp (bf16x3 0, factored 0), mpx_sa_mlp_factored (0, 1), mpx_sa_mlp_bf16x3 (1, 0) and
+ * mpx_sa_mlp_bf16x3_factored (1, 1) on a device of `cus` compute units (<= 0: the current device's own count).  C: the
+ * module's feature channels (1 or 64); has_counts: cnt is given; out_aligned: out_stride % 4 == 0 and out 16-byte aligned.
+ * route[10]: packed kernel (fp32: the hit counts are honoured), queries per wave (the instantiation), pooling through LDS
+ * (fp32, C = 1), units (fp32 packed, bf16x3 factored) or workgroups (the other forms) covering the queries, units /
+ * workgroups per environment when whole environments go to one XCD (else 0), persistent grid fed from the unit queue wanted,
+ * its workgroups, bf16x3 weight-resident kernel (else lockstep), a wave's queries share their environment (resident),
+ * XCD-aware unit order (bf16x3 factored).                                                                               */
+int mpx_sa_mlp_route(int cus, int B, int npoint, int nsample, int has_counts, int C, int bf16x3, int factored,
+                     int out_aligned, int32_t *route);
 
 /* ball_query: first `nsample` indices (ascending) with d2 < radius^2, padded with the first
  * hit, zero when there is none.  idx int32 [B,npoint,nsample].  cnt (optional, int32

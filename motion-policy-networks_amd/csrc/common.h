@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "../../include/mpinets_hip.h"
+#include "launch_routes.h"
 
 #define MPX_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -70,7 +71,6 @@ inline int mpx_cu_count() {
 // THE grouped-MLP modules the fused SA kernels are built for, (C, c1, c2, c3): every dispatch and size query expands this
 #define MPX_SA_SHAPES(X) X(1, 64, 64, 64) X(64, 128, 128, 256)
 #define MPX_SA_SHAPE_IS(a, b, c, d) (C == a && c1 == b && c2 == c && c3 == d)
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ---- host helpers shared across files ----------------------------------------------------------------------------------
 // dense.hip: the segment max-pool's checks and key unpacking (mpx_linear_segmax, dense_bf16.hip's mpx_linear_segmax_bf16x3)

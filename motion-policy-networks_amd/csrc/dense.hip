@@ -18,7 +18,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BM = 128, BN = 128;
+constexpr int BM = LINEAR_BM, BN = LINEAR_BN;  // (launch_routes.h: linear_route counts these tiles)
 
 __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == MPX_ACT_RELU) return fmaxf(v, 0.0f);
@@ -338,8 +338,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static bool gemv_fits(int M, int K) { return M <= 8 && (int64_t)(M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8) * K * 4 <= 64 * 1024; }
-
 static void gemv_launch(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K, int act,
                         float *y, int ldy, mpx_stream_t stream) {
   const dim3 g(cdiv(N, 4 * GEMV_R)), t(256);
@@ -453,7 +451,7 @@ static int linear_launch(const char *name, const float *x, int ldx, const float 
     const int m = (int)(M - m0 < slab ? M - m0 : slab);
     const float *xs = x + m0 * ldx;
     float *ys = e.seg ? y : y + (POOL ? m0 / BM : m0) * ldy;  // (the keys are per segment, not per row)
-    if (e.gemv && gemv_fits(m, K)) {
+    if (e.gemv && linear_route(m, N, K).form == LINEAR_GEMV) {
       gemv_launch(xs, ldx, w, e.bias, m, N, K, e.act, ys, ldy, stream);
       continue;
     }
@@ -490,7 +488,7 @@ MPX_EXPORT int mpx_linear(const float *x, int ldx, const float *w, const float *
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear: unknown activation %d", act);
   if (M == 0) return 0;
   // short K, 128 outputs: a row per lane, W in registers (every M: one rounding order; a few rows take the gemv kernel)
-  if (!gemv_fits(M, K) && rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy)) {
+  if (linear_route(M, N, K).form != LINEAR_GEMV && rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy)) {
     int cus = mpx_cu_count();
     if (cus <= 0) cus = 256;
     const int64_t tiles = ((int64_t)M + 31) / 32, waves = (int64_t)cus * 4 * MPX_ROWLANE_WAVES;
@@ -520,25 +518,7 @@ MPX_EXPORT int mpx_linear_dact(const float *x, int ldx, const float *w, int M, i
   MPX_LAUNCH_CHECK("mpx_linear_dact");
 }
 
-// ---- split-K for skinny problems ------------------------------------------------------------------------
-// A rollout of ONE problem (or a few hundred) leaves the fc / decoder layers with 1..32 output tiles: 4096->2048
-// at M <= 128 is 16 workgroups walking K = 4096 alone (310 us on 6 % of the CUs).  With a workspace the K range
-// is cut into S slices (blockIdx.z), each writing a raw partial tile; splitk_reduce_kernel then adds the S
-// partials IN SLICE ORDER (deterministic), the bias and the activation.
-static int splitk_plan(int M, int N, int K, int *kslice) {
-  const int64_t tiles = (int64_t)cdiv(M, BM) * cdiv(N, BN);
-  *kslice = K;
-  // (M > 1024: the partial tiles would cost more HBM traffic than the idle CUs are worth)
-  if (tiles >= 128 || K < 256 || M > 1024 || gemv_fits(M, K)) return 1;
-  const int slabs = cdiv(K, 16);
-  int S = (int)((512 + tiles - 1) / tiles);
-  if (S > slabs / 4) S = slabs / 4;  // >= 64 k per slice
-  if (S < 2) return 1;
-  const int per = cdiv(slabs, S);
-  *kslice = per * 16;
-  return cdiv(K, *kslice);
-}
-
+// ---- split-K for skinny problems (the plan: linear_route, launch_routes.h) ------------------------------------------
 __global__ void __launch_bounds__(256)
     splitk_reduce_kernel(const float *__restrict__ part, int S, size_t zstride, const float *__restrict__ bias,
                          int M, int N, int act, float *__restrict__ y, int ldy) {
@@ -551,19 +531,22 @@ __global__ void __launch_bounds__(256)
   y[(size_t)row * ldy + col] = act_apply(acc, act);
 }
 
+MPX_EXPORT int mpx_linear_route(int M, int N, int K, int32_t *route) {
+  const LinearRoute r = linear_route(M, N, K);
+  route[0] = r.form, route[1] = r.S, route[2] = r.kslice;
+  return 0;
+}
 MPX_EXPORT int64_t mpx_linear_workspace(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  int kslice;
-  const int S = splitk_plan(M, N, K, &kslice);
-  return S > 1 ? (int64_t)S * M * N * (int64_t)sizeof(float) : 0;
+  const LinearRoute r = linear_route(M, N, K);
+  return r.form == LINEAR_SPLITK ? (int64_t)r.S * M * N * (int64_t)sizeof(float) : 0;
 }
 
 MPX_EXPORT int mpx_linear_ws(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K,
                              int act, float *y, int ldy, void *workspace, int64_t workspace_bytes,
                              mpx_stream_t stream) {
-  int kslice = K;
-  const int S = (M > 0 && N > 0 && K > 0) ? splitk_plan(M, N, K, &kslice) : 1;
-  if (S <= 1 || workspace == nullptr) return mpx_linear(x, ldx, w, bias, M, N, K, act, y, ldy, stream);
+  const LinearRoute r = (M > 0 && N > 0 && K > 0) ? linear_route(M, N, K) : LinearRoute{LINEAR_TILE, 1, K};
+  if (r.form != LINEAR_SPLITK || workspace == nullptr) return mpx_linear(x, ldx, w, bias, M, N, K, act, y, ldy, stream);
   if (linear_check("mpx_linear_ws", x, ldx, w, M, N, K, ldy)) return 1;
   MPX_REQUIRE(((uintptr_t)workspace & 15) == 0, "mpx_linear_ws: the workspace must be 16-byte aligned");
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_ws: unknown activation %d", act);
@@ -572,9 +555,9 @@ MPX_EXPORT int mpx_linear_ws(const float *x, int ldx, const float *w, const floa
               (long long)mpx_linear_workspace(M, N, K));
   float *part = static_cast<float *>(workspace);
   LinearEpi e;
-  e.S = S, e.kslice = kslice, e.zstride = (size_t)M * N;
+  e.S = r.S, e.kslice = r.kslice, e.zstride = (size_t)M * N;
   if (int rc = linear_launch<false>("mpx_linear_ws", x, ldx, w, M, N, K, part, N, e, stream)) return rc;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv((int64_t)M * N, 256)), dim3(256), 0, mpx_s(stream), part, S,
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv((int64_t)M * N, 256)), dim3(256), 0, mpx_s(stream), part, r.S,
                      e.zstride, bias, M, N, act, y, ldy);
   MPX_LAUNCH_CHECK("mpx_linear_ws");
 }

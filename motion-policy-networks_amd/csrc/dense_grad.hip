@@ -11,7 +11,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int WG_BK = 16, WG_LDT = WG_BK + 4;
+constexpr int WG_LDT = WG_BK + 4;  // (WG_BK: launch_routes.h)
 
 // T = 128: a 128 x 128 tile of dW per workgroup (four waves as 2 x 2, 64 x 64 each); T = 64 (layers of <= 64 inputs and
 // outputs -- the first set-abstraction module, whose three weight gradients reduce over ~2 M rows): a 64 x 64 tile, one
@@ -265,16 +265,13 @@ MPX_EXPORT int mpx_groupnorm_leaky_grad(const float *x, const float *gamma, cons
   MPX_LAUNCH_CHECK("mpx_groupnorm_leaky_grad");
 }
 
-static int wgrad_tile(int N, int K) { return (N <= 64 && K <= 64) ? 64 : 128; }
-static int wgrad_splits(int M, int N, int K) {
-  const int T = wgrad_tile(N, K);
-  const int tiles = cdiv(N, T) * cdiv(K, T);
-  int S = cdiv(1024, tiles);
-  const int maxs = cdiv(M, 4 * WG_BK);
-  return S < 1 ? 1 : (S > maxs ? (maxs < 1 ? 1 : maxs) : S);
+MPX_EXPORT int mpx_linear_wgrad_route(int M, int N, int K, int32_t *route) {
+  const WgradRoute r = wgrad_route(M, N, K);
+  route[0] = r.tile, route[1] = r.splits, route[2] = r.rows_per_split;
+  return 0;
 }
 MPX_EXPORT int64_t mpx_linear_wgrad_scratch(int M, int N, int K) {
-  return (int64_t)wgrad_splits(M, N, K) * ((int64_t)N * K + N);  // floats: weight partials + bias partials
+  return (int64_t)wgrad_route(M, N, K).splits * ((int64_t)N * K + N);  // floats: weight partials + bias partials
 }
 
 static int wgrad_run(const char *name, bool x3, const float *dy, int lddy, const float *x, int ldx, int M, int N, int K,
@@ -297,8 +294,8 @@ static int wgrad_run(const char *name, bool x3, const float *dy, int lddy, const
   MPX_REQUIRE((((uintptr_t)dy | (uintptr_t)x) & 15) == 0, "%s: operands must be 16-byte aligned", name);
   MPX_REQUIRE(dw && scratch, "%s: NULL output / scratch", name);
   const int64_t per = (int64_t)N * K + N;
-  const int S = wgrad_splits(M, N, K), T = wgrad_tile(N, K);
-  const int rps = cdiv(cdiv(M, S), WG_BK) * WG_BK;
+  const WgradRoute r = wgrad_route(M, N, K);
+  const int S = r.splits, T = r.tile, rps = r.rows_per_split;
   MPX_REQUIRE(cdiv(N, T) <= 65535 && S <= 65535, "%s: grid too large", name);
   // ONE split (few rows: the reference's batch of 10 through the dense heads) and dw | db adjacent, as every split's slice
   // is laid out: the kernel writes the gradients themselves.  (The reduction of a single split was a copy on 16 lanes per

@@ -133,9 +133,7 @@ MPX_EXPORT int mpx_pose_cloud(const float *poses, int B, const float *table_pts,
 // on COL_PPB lanes of wave 0; then each of the 4 waves takes pairs round-robin with the S spheres
 // on its lanes.  Primitive data of the pair's environment is wave-uniform (scalar loads).
 // Algorithmic bytes per pair: 28 (q) + per-env primitive data amortised over T; writes 4*S when
-// min_sdf is requested, else nothing but the rare atomicOr.
-constexpr int COL_PPB = 16;
-
+// min_sdf is requested, else nothing but the rare atomicOr.  (COL_PPB: launch_routes.h)
 __global__ void __launch_bounds__(256)
     franka_collision_kernel(const float *__restrict__ q, int G, int T, float finger,
                             const float *__restrict__ sc, const float *__restrict__ sr,
@@ -205,9 +203,7 @@ __global__ void __launch_bounds__(256)
 #ifndef MPX_COL_PACK
 #define MPX_COL_PACK 0  // 1: two pairs per packed-fp32 instruction (v_pk_fma_f32 ...) -- measured: no faster (see below)
 #endif
-#ifndef MPX_COL_TC
-#define MPX_COL_TC 64  // waypoints per workgroup of the swept-sphere check (A/B: tools/ab_build.sh)
-#endif
+// (MPX_COL_TC, waypoints per workgroup: launch_routes.h)
 template <int BLOCK, int COL_TC, int PPT>
 __global__ void __launch_bounds__(BLOCK)
     franka_collision_env_kernel(const float *__restrict__ q, int T, int chunks, float finger, const float *__restrict__ sc,
@@ -400,47 +396,40 @@ MPX_EXPORT int mpx_franka_collision(const float *q, int B, int T, float finger, 
                                     mpx_stream_t stream) {
   MPX_REQUIRE(B >= 0 && T >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "mpx_franka_collision: negative size");
   MPX_REQUIRE((int64_t)B * T < (int64_t)1 << 31, "mpx_franka_collision: B*T overflows int32");
-  if (B == 0 || T == 0 || S == 0) return 0;
-  // (the per-environment kernel stages the 4x4 frames as float4 rows: a frame pointer that is not 16-byte aligned -- a
-  // tensor view with an odd storage offset -- takes the general kernel below, which reads them with scalar loads)
-  const bool frames_aligned = (((uintptr_t)cub_frames | (uintptr_t)cyl_frames) & 15) == 0;
-  static_assert(MPX_COL_TC >= 1 && MPX_COL_TC <= 64 && MPX_COL_TC * 64 <= 16 * 256,
-                "MPX_COL_TC: FK runs on one thread per waypoint of a chunk and a thread holds at most 16 (waypoint, sphere) pairs");
-  if (M1 <= 64 && M2 <= 64 && S <= 64 && frames_aligned) {  // per-environment form: masks in two scalar words, pairs flattened over the lanes
-#define COL_ENV(BLOCK, TC, PPT)                                                                                        \
-  do {                                                                                                                 \
-    const int chunks = cdiv(T, TC);                                                                                    \
-    MPX_REQUIRE((int64_t)B * chunks < (int64_t)1 << 31, "mpx_franka_collision: too many workgroups");                  \
-    hipLaunchKernelGGL((franka_collision_env_kernel<BLOCK, TC, PPT>),                                                  \
-                       dim3((unsigned)(B * chunks)), dim3(BLOCK),                                                      \
-                       (size_t)(128 * 16 + min(T, TC) * FRAME_FLOATS) * sizeof(float), mpx_s(stream), q, T, chunks, finger,         \
-                       sph_centers, sph_radii, sph_link, S, cub_frames, cub_dims, M1, cyl_frames, cyl_radii,           \
-                       cyl_heights, M2, flags, min_sdf);                                                               \
-  } while (0)
-    // (waypoints per workgroup, measured at 8192 x 50: 64 -> 0.486 ms, 32 -> 0.508, 16 -> 0.570; one- and two-wave
-    // workgroups with 16 / 32 waypoints 0.735 / 0.673: FK runs once per chunk on as many lanes as the chunk has waypoints)
-    // (round 4, pairs in registers: MPX_COL_TC waypoints x <= 64 spheres over 256 threads = MPX_COL_TC / 4 pairs per thread)
-    if (T * S <= 64) COL_ENV(64, 64, 1);  // one waypoint (the rollout step): one wave per environment, one pair per lane
-    else {
-      switch ((min(T, MPX_COL_TC) * S + 511) / 512) {  // packed pairs per thread of a full chunk
-        case 1: COL_ENV(256, MPX_COL_TC, 2); break;
-        case 2: COL_ENV(256, MPX_COL_TC, 4); break;
-        case 3: COL_ENV(256, MPX_COL_TC, 6); break;
-        case 4: COL_ENV(256, MPX_COL_TC, 8); break;
-        case 5: COL_ENV(256, MPX_COL_TC, 10); break;
-        case 6: COL_ENV(256, MPX_COL_TC, 12); break;
-        case 7: COL_ENV(256, MPX_COL_TC, 14); break;
-        default: COL_ENV(256, MPX_COL_TC, 16); break;
-      }
-    }
-#undef COL_ENV
+  const CollisionRoute r = collision_route(B, T, S, M1, M2, (((uintptr_t)cub_frames | (uintptr_t)cyl_frames) & 15) == 0);
+  if (r.form == COL_NONE) return 0;
+  if (r.form == COL_GENERAL) {
+    hipLaunchKernelGGL(franka_collision_kernel, dim3(r.chunks), dim3(r.block), 0, mpx_s(stream), q, B * T, T, finger,
+                       sph_centers, sph_radii, sph_link, S, cub_frames, cub_dims, M1, cyl_frames, cyl_radii, cyl_heights, M2,
+                       flags, min_sdf);
     MPX_LAUNCH_CHECK("mpx_franka_collision");
   }
-  const int G = B * T;
-  hipLaunchKernelGGL(franka_collision_kernel, dim3(cdiv(G, COL_PPB)), dim3(256), 0, mpx_s(stream), q, G, T,
-                     finger, sph_centers, sph_radii, sph_link, S, cub_frames, cub_dims, M1, cyl_frames,
-                     cyl_radii, cyl_heights, M2, flags, min_sdf);
+  MPX_REQUIRE((int64_t)B * r.chunks < (int64_t)1 << 31, "mpx_franka_collision: too many workgroups");
+#define COL_ENV_GO(BLOCK, TC, PPT)                                                                                     \
+  case PPT:                                                                                                            \
+    hipLaunchKernelGGL((franka_collision_env_kernel<BLOCK, TC, PPT>), dim3((unsigned)(B * r.chunks)), dim3(BLOCK),     \
+                       (size_t)(128 * 16 + min(T, TC) * FRAME_FLOATS) * sizeof(float), mpx_s(stream), q, T, r.chunks,  \
+                       finger, sph_centers, sph_radii, sph_link, S, cub_frames, cub_dims, M1, cyl_frames, cyl_radii,   \
+                       cyl_heights, M2, flags, min_sdf);                                                               \
+    break
+  switch (r.ppt) {  // every instantiation collision_route can name (COL_WAVE: one pair per lane)
+    COL_ENV_GO(64, 64, 1);
+    COL_ENV_GO(256, MPX_COL_TC, 2);
+    COL_ENV_GO(256, MPX_COL_TC, 4);
+    COL_ENV_GO(256, MPX_COL_TC, 6);
+    COL_ENV_GO(256, MPX_COL_TC, 8);
+    COL_ENV_GO(256, MPX_COL_TC, 10);
+    COL_ENV_GO(256, MPX_COL_TC, 12);
+    COL_ENV_GO(256, MPX_COL_TC, 14);
+    COL_ENV_GO(256, MPX_COL_TC, 16);
+  }
+#undef COL_ENV_GO
   MPX_LAUNCH_CHECK("mpx_franka_collision");
+}
+MPX_EXPORT int mpx_franka_collision_route(int B, int T, int S, int M1, int M2, int frames_aligned, int32_t *route) {
+  const CollisionRoute r = collision_route(B, T, S, M1, M2, frames_aligned != 0);
+  route[0] = r.form, route[1] = r.ppt, route[2] = r.block, route[3] = r.tc, route[4] = r.chunks, route[5] = r.last;
+  return 0;
 }
 
 // ---- per-call robot-point subset ------------------------------------------------------------------------------------

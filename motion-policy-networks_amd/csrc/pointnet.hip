@@ -354,14 +354,7 @@ __device__ __forceinline__ u64 wave_max64_staged(u64 k) {
   return pack64(mlo, mhi);
 }
 
-constexpr int FPSC_CELLS = 4096;
-// dynamic LDS: [0,256) reduction slots, [256,768) scalars (position of point 0, cloud bounding box exchange), then the
-// cloud in sorted order sx | sy | sz (3 N floats); the prologue's histogram (16 KB) and position -> index map (2 N bytes)
-// live in the same area before the coordinates are written
-__host__ __device__ constexpr size_t fpsc_lds_bytes(int N, bool nocloud = false) {
-  const size_t cloud = nocloud ? 0 : (size_t)3 * N * 4, pro = (size_t)FPSC_CELLS * 4 + (((size_t)N * 2 + 15) & ~(size_t)15);
-  return 768 + (cloud > pro ? cloud : pro);
-}
+// (dynamic LDS: fpsc_lds_bytes, launch_routes.h)
 template <int PTS, int FPSC_WAVES>
 __global__ void __launch_bounds__(64 * FPSC_WAVES)
     __attribute__((amdgpu_waves_per_eu(FPSC_WAVES == 4 ? 3 : FPSC_WAVES / 2, FPSC_WAVES == 4 ? 3 : FPSC_WAVES / 2)))
@@ -626,18 +619,6 @@ __global__ void __launch_bounds__(64 * FPSC_WAVES)
   }
 }
 
-#ifndef MPX_FPS4_MIN_B
-#define MPX_FPS4_MIN_B 768  // from this many environments on, the 4-wave culled FPS (A/B: tools/ab_build.sh)
-#endif
-constexpr int FPS_MAX_N = 8192;                         // 512 threads x 16 points (include/mpinets_hip.h says the same)
-constexpr int FPS_MAX_LDS = 256 + 3 * FPS_MAX_N * 4;    // the cloud copy of the largest supported launch
-
-static int opt_n_threads_log2(int n) {
-  int l = 0;
-  while ((2 << l) <= n && (2 << l) <= 512) ++l;
-  return l;
-}
-
 // ---- verification hook: which kernel family serves mpx_fps / mpx_ball_query ---------------------------------------
 // Variant 1 (default) = the fast kernels (wave-per-environment / Morton-culled FPS; wave-per-query / bucketed ball
 // query), variant 0 = the plain kernels they are proven against (fps_kernel, ball_query_kernel).  Both produce the same
@@ -655,6 +636,11 @@ MPX_EXPORT int mpx_set_variant(int what, int value) {
 MPX_EXPORT int mpx_get_variant(int what) {
   return (what >= 0 && what < MPX_VARIANT_COUNT_) ? g_variant[what].load(std::memory_order_relaxed) : -1;
 }
+MPX_EXPORT int mpx_fps_route(int B, int N, int32_t *route) {
+  const FpsRoute r = fps_route(B, N, g_variant[MPX_VARIANT_FPS].load(std::memory_order_relaxed));
+  route[0] = r.family, route[1] = r.pts, route[2] = r.threads, route[3] = r.lds;
+  return 0;
+}
 
 MPX_EXPORT int mpx_fps(const float *xyz, int B, int N, int stride, int npoint, int32_t *idx, float *new_xyz,
                        int new_stride, mpx_stream_t stream) {
@@ -663,79 +649,39 @@ MPX_EXPORT int mpx_fps(const float *xyz, int B, int N, int stride, int npoint, i
   MPX_REQUIRE(new_xyz == nullptr || new_stride >= 3, "mpx_fps: new_stride < 3");
   if (B == 0 || npoint == 0) return 0;
   const int log2bs = opt_n_threads_log2(N);
-  const int fast = g_variant[MPX_VARIANT_FPS].load(std::memory_order_relaxed);
-  if (fast && N <= 512) {  // small cloud: one wave per environment, no LDS, no barrier
-    dim3 g1(B), t1(64);
-#define FPS_WAVE(P) hipLaunchKernelGGL(fps_wave_kernel<P>, g1, t1, 0, mpx_s(stream), xyz, N, stride, npoint, log2bs, idx, new_xyz, new_stride)
-    switch ((N + 63) / 64) {
-      case 1: FPS_WAVE(1); break;
-      case 2: FPS_WAVE(2); break;
-      case 3: case 4: FPS_WAVE(4); break;
-      default: FPS_WAVE(8); break;
-    }
-#undef FPS_WAVE
-    MPX_LAUNCH_CHECK("mpx_fps");
-  }
-  if (fast && N > 512) {  // (log2bs == 9 here: the key layout of fps_cull_kernel assumes it)
-    // large clouds (the first module's 6272 points): the 4-wave form without the LDS copy of the cloud -- three
-    // workgroups per CU instead of two (6.45 -> 6.11 ms at 8192 environments; with the LDS copy, two per CU: 7.10 ms)
-    // (a few hundred environments or fewer are latency-bound, not throughput-bound: they keep the 8-wave form, whose pick
-    // chain is shorter -- one planning problem: 0.69 vs 0.80 ms per step.  Same indices either way.)
-    const int waves = (N > 16 * 256 && B >= MPX_FPS4_MIN_B) ? 4 : 8;
-    const size_t lds_c = fpsc_lds_bytes(N, waves == 4);
-    // (wave counts measured in round 3 at 8192 environments x 6272 points: 16 waves x 7 points per lane 8.31 ms, 8 x 13
-    // 6.41 ms, 4 x 25 with the LDS cloud copy 7.10 ms, 4 x 25 without it 6.11 ms: the cross-wave reduction and the
-    // barrier get cheaper with fewer waves, the per-wave pass longer; what pays is the third workgroup per CU.)
-    dim3 gc(B), tc(64 * waves);
-#define FPS_CULL(P, W)                                                                                           \
-  do {                                                                                                           \
-    if (lds_c > 64 * 1024) MPX_LDS_LIMIT_ONCE((fps_cull_kernel<P, W>), fpsc_lds_bytes(FPS_MAX_N), "mpx_fps");     \
-    hipLaunchKernelGGL((fps_cull_kernel<P, W>), gc, tc, lds_c, mpx_s(stream), xyz, N, stride, npoint, idx, new_xyz, \
-                       new_stride);                                                                              \
-  } while (0)
-    const int pts_c = (N + 64 * waves - 1) / (64 * waves);
-    if (waves == 4) {
-      if (pts_c <= 20) FPS_CULL(20, 4);
-      else if (pts_c <= 25) FPS_CULL(25, 4);
-      else FPS_CULL(32, 4);
-    } else if (pts_c <= 2) FPS_CULL(2, 8);
-    else if (pts_c <= 4) FPS_CULL(4, 8);
-    else if (pts_c <= 6) FPS_CULL(6, 8);
-    else if (pts_c <= 8) FPS_CULL(8, 8);
-    else if (pts_c <= 10) FPS_CULL(10, 8);
-    else if (pts_c <= 13) FPS_CULL(13, 8);
-    else FPS_CULL(16, 8);
-#undef FPS_CULL
-    MPX_LAUNCH_CHECK("mpx_fps");
-  }
-  int block = ((N + 63) / 64) * 64;
-  if (block > 512) block = 512;  // measured: 512 threads x 13 points beat 1024 x 7
-  const int pts = (N + block - 1) / block;
-  const size_t lds = 256 + (size_t)3 * N * sizeof(float);
-  dim3 g(B), t(block);
-#define FPS_LAUNCH(P)                                                                                     \
-  do {                                                                                                    \
-    if (lds > 64 * 1024) MPX_LDS_LIMIT_ONCE(fps_kernel<P>, FPS_MAX_LDS, "mpx_fps");                       \
-    hipLaunchKernelGGL(fps_kernel<P>, g, t, lds, mpx_s(stream), xyz, N, stride, npoint, log2bs, idx,      \
-                       new_xyz, new_stride);                                                              \
-  } while (0)
-  switch (pts) {
-    case 1: FPS_LAUNCH(1); break;
-    case 2: FPS_LAUNCH(2); break;
-    case 3: FPS_LAUNCH(3); break;
-    case 4: FPS_LAUNCH(4); break;
-    case 5: FPS_LAUNCH(5); break;
-    case 6: FPS_LAUNCH(6); break;
-    case 7: FPS_LAUNCH(7); break;
-    case 8: FPS_LAUNCH(8); break;
-    case 9: case 10: FPS_LAUNCH(10); break;
-    case 11: case 12: case 13: FPS_LAUNCH(13); break;
-    case 14: case 15: case 16: FPS_LAUNCH(16); break;
+  const FpsRoute r = fps_route(B, N, g_variant[MPX_VARIANT_FPS].load(std::memory_order_relaxed));
+  const dim3 g(B), t(r.threads);
+  const size_t lds = (size_t)r.lds;
+#define FPS_KEY(FAMILY, P) ((FAMILY) * 100 + (P))
+#define FPS_WAVE_GO(P)                                                                                                  \
+  case FPS_KEY(FPS_WAVE, P):                                                                                            \
+    hipLaunchKernelGGL(fps_wave_kernel<P>, g, t, 0, mpx_s(stream), xyz, N, stride, npoint, log2bs, idx, new_xyz, new_stride); \
+    break
+#define FPS_CULL_GO(FAMILY, P, W)                                                                                       \
+  case FPS_KEY(FAMILY, P):                                                                                              \
+    if (lds > 64 * 1024) MPX_LDS_LIMIT_ONCE((fps_cull_kernel<P, W>), fpsc_lds_bytes(FPS_MAX_N), "mpx_fps");              \
+    hipLaunchKernelGGL((fps_cull_kernel<P, W>), g, t, lds, mpx_s(stream), xyz, N, stride, npoint, idx, new_xyz, new_stride); \
+    break
+#define FPS_PLAIN_GO(P)                                                                                                 \
+  case FPS_KEY(FPS_PLAIN, P):                                                                                           \
+    if (lds > 64 * 1024) MPX_LDS_LIMIT_ONCE(fps_kernel<P>, FPS_MAX_LDS, "mpx_fps");                                     \
+    hipLaunchKernelGGL(fps_kernel<P>, g, t, lds, mpx_s(stream), xyz, N, stride, npoint, log2bs, idx, new_xyz, new_stride); \
+    break
+  switch (FPS_KEY(r.family, r.pts)) {  // every instantiation fps_route can name
+    FPS_WAVE_GO(1); FPS_WAVE_GO(2); FPS_WAVE_GO(4); FPS_WAVE_GO(8);
+    FPS_CULL_GO(FPS_CULL8, 2, 8); FPS_CULL_GO(FPS_CULL8, 4, 8); FPS_CULL_GO(FPS_CULL8, 6, 8); FPS_CULL_GO(FPS_CULL8, 8, 8);
+    FPS_CULL_GO(FPS_CULL8, 10, 8); FPS_CULL_GO(FPS_CULL8, 13, 8); FPS_CULL_GO(FPS_CULL8, 16, 8);
+    FPS_CULL_GO(FPS_CULL4, 20, 4); FPS_CULL_GO(FPS_CULL4, 25, 4); FPS_CULL_GO(FPS_CULL4, 32, 4);
+    FPS_PLAIN_GO(1); FPS_PLAIN_GO(2); FPS_PLAIN_GO(3); FPS_PLAIN_GO(4); FPS_PLAIN_GO(5); FPS_PLAIN_GO(6); FPS_PLAIN_GO(7);
+    FPS_PLAIN_GO(8); FPS_PLAIN_GO(10); FPS_PLAIN_GO(13); FPS_PLAIN_GO(16);
     default:
-      mpx_set_error("mpx_fps: %d points per thread unsupported (N=%d, block=%d)", pts, N, block);
+      mpx_set_error("mpx_fps: no kernel for N=%d (%d threads)", N, r.threads);
       return 1;
   }
-#undef FPS_LAUNCH
+#undef FPS_KEY
+#undef FPS_WAVE_GO
+#undef FPS_CULL_GO
+#undef FPS_PLAIN_GO
   MPX_LAUNCH_CHECK("mpx_fps");
 }
 

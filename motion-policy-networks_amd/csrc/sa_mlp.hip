@@ -28,10 +28,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-constexpr int SA_MAX_NSAMPLE = 256;  // slots per neighbourhood the packed kernels index their row map for
-// queries per unit of the large launches (A/B builds: narrow module 16 / 32: 10.38 / 10.14 ms -- the tail of a unit's last
-// tile is 2.7 instead of 5.5 % of its rows; wide module 8 / 16: 46.6 / 46.8 ms -- its units are already 16 tiles)
-constexpr int SA1_Q = 32, SA2_Q = 8;
+// (SA_MAX_NSAMPLE, SA1_Q, SA2_Q -- the row map's slots and the queries per unit of the large launches: launch_routes.h)
 // rows of a neighbourhood are rounded up to GR (repeating its first member): 4 for the wide module (62 rows per query on
 // the bench scenes: 2 % of padding, eight pooling groups per tile), 2 for the narrow one (15 rows per query: the padding
 // was 9 % of its matrix work; sixteen pooling groups per tile instead of eight cost less than that)
@@ -745,26 +742,23 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF == 1
 }
 
 // ---- host entry points -----------------------------------------------------------------------------------
-// The launch plan of the packed kernel at Q queries per unit: units of whole environments per XCD when the grid is regular
-// (bpe; npoint % Q == 0, B % 8 == 0), and with many units per wave slot (per_cu one-wave workgroups per CU) the persistent
-// form: one workgroup per slot -- a multiple of 8: the hardware deals workgroups to the XCDs round-robin -- and the units
-// from the device-side queue.  A stream without a private queue slot keeps one unit per wave.
+// The launch plan of the packed kernel: sa_route (launch_routes.h) says how many units, whether whole environments go to
+// one XCD (bpe) and whether the persistent form is wanted; what is left here is the part that touches the stream -- taking
+// the unit-queue slot.  A stream without a private queue slot keeps one unit per wave.
 struct SaPlan {
   int64_t grid;
   int bpe;
   unsigned int *queue;
 };
-template <int Q>
-static int sa_plan(int64_t nq, int B, int npoint, int per_cu, mpx_stream_t stream, const char *name, SaPlan *p) {
-  p->grid = (nq + Q - 1) / Q;
-  p->bpe = (npoint % Q == 0 && B % 8 == 0) ? npoint / Q : 0;
+static int sa_plan(const SaRoute &r, mpx_stream_t stream, const char *name, SaPlan *p) {
+  p->grid = r.units;
+  p->bpe = r.epx;
   p->queue = nullptr;
-  const int64_t slots = ((int64_t)mpx_cu_count() * per_cu) & ~(int64_t)7;
-  if (slots > 0 && p->grid >= 4 * slots) {
+  if (r.persistent) {
     int exhausted = 0;
     p->queue = mpx_unit_queue_for(mpx_s(stream), &exhausted);
     MPX_REQUIRE(p->queue || exhausted, "%s: cannot reset the unit queue", name);
-    if (p->queue) p->grid = slots;
+    if (p->queue) p->grid = r.slots;
   }
   return 0;
 }
@@ -777,39 +771,32 @@ static int launch_sa(const float *xyz, int stride, const float *new_xyz, int new
   MPX_REQUIRE(!append_centre || (cnt && out_stride >= C3 + 4),
               "mpx_sa_mlp: append_centre needs the hit counts and out_stride >= c3 + 4");
   MPX_REQUIRE(!append_centre || nsample <= SA_MAX_NSAMPLE, "mpx_sa_mlp: append_centre needs nsample <= %d", SA_MAX_NSAMPLE);
-  if (cnt && nsample <= SA_MAX_NSAMPLE) {  // (more slots than the row map holds: every slot is walked -- the same result)
-    // queries per wave: 8-16 tiles of work on typical scenes.  A small batch (a single planning problem up to a few
-    // dozen) would leave most CUs idle at that size, so it runs QS queries per wave instead: same rows, same
-    // arithmetic per row (bit-identical results), 4x the waves and a quarter of the latency.
-    constexpr int QL = CF == 1 ? SA1_Q : 8, QS = CF == 1 ? 4 : 2;
-    int rc = 0;
-    auto go = [&](auto qtag) {
-      constexpr int Q = decltype(qtag)::value;
-      SaPlan plan;
-      if ((rc = sa_plan<Q>(nq, B, npoint, CF == 1 ? 16 : 8, stream, "mpx_sa_mlp", &plan))) return;
-      // (the narrow module with <= 128 slots per neighbourhood and 16-byte aligned output rows: the form with the small
-      // row map that pools through LDS, see LPOOL in the kernel)
-      bool lpool = false;
-      if constexpr (CF == 1) {
-        lpool = nsample <= 128 && out_stride % 4 == 0 && ((uintptr_t)out & 15) == 0;
-        if (lpool)
-          hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false, 128>), dim3((unsigned)plan.grid), dim3(64), 0,
-                             mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint,
-                             nsample, wpack, out, out_stride, plan.bpe, nullptr, nullptr, append_centre, plan.queue);
-      }
-      if (!lpool)
-        hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false>), dim3((unsigned)plan.grid), dim3(64), 0,
+  const SaRoute r = sa_route(mpx_cu_count(), B, npoint, nsample, cnt != nullptr, CF, false, false,
+                             out_stride % 4 == 0 && ((uintptr_t)out & 15) == 0);
+  if (!r.packed) {
+    hipLaunchKernelGGL((sa_mlp_kernel<CF, C1, C2, C3>), dim3((unsigned)r.units), dim3(256), 0, mpx_s(stream), xyz, stride,
+                       new_xyz, new_stride, feat, feat_stride, idx, nq, N, npoint, nsample, wpack, out, out_stride);
+    MPX_LAUNCH_CHECK("mpx_sa_mlp");
+  }
+  SaPlan plan;
+  if (int rc = sa_plan(r, stream, "mpx_sa_mlp", &plan)) return rc;
+  auto go = [&](auto qtag) {
+    constexpr int Q = decltype(qtag)::value;
+    if constexpr (CF == 1) {  // (LPOOL, see the kernel: built for the narrow module only)
+      if (r.lpool) {
+        hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false, 128>), dim3((unsigned)plan.grid), dim3(64), 0,
                            mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint,
                            nsample, wpack, out, out_stride, plan.bpe, nullptr, nullptr, append_centre, plan.queue);
-    };
-    if (nq >= 1024 * QL) go(std::integral_constant<int, QL>{});
-    else go(std::integral_constant<int, QS>{});
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL((sa_mlp_kernel<CF, C1, C2, C3>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0,
-                       mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, nq, N, npoint,
-                       nsample, wpack, out, out_stride);
-  }
+        return;
+      }
+    }
+    hipLaunchKernelGGL((sa_mlp_packed_kernel<CF, C1, C2, C3, Q, false>), dim3((unsigned)plan.grid), dim3(64), 0,
+                       mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint,
+                       nsample, wpack, out, out_stride, plan.bpe, nullptr, nullptr, append_centre, plan.queue);
+  };
+  constexpr int QL = CF == 1 ? SA1_Q : 8, QS = CF == 1 ? 4 : 2;  // the two instantiations sa_route names for this module
+  if (r.Q == QL) go(std::integral_constant<int, QL>{});
+  else go(std::integral_constant<int, QS>{});
   MPX_LAUNCH_CHECK("mpx_sa_mlp");
 }
 
@@ -846,20 +833,30 @@ MPX_EXPORT int mpx_sa_mlp_factored(const float *pre, const float *ctr, const int
   if (B == 0 || npoint == 0) return 0;
   const int64_t nq = (int64_t)B * npoint;
   MPX_REQUIRE(nq / 4 + 1 < ((int64_t)1 << 31), "mpx_sa_mlp_factored: too many query points");
-  int rc = 0;
-  auto go = [&](auto qtag) {  // queries per wave: 8, or 2 / 1 for small batches (see launch_sa)
+  const SaRoute r = sa_route(mpx_cu_count(), B, npoint, nsample, true, C, false, true, false);
+  SaPlan plan;
+  if (int rc = sa_plan(r, stream, "mpx_sa_mlp_factored", &plan)) return rc;
+  auto go = [&](auto qtag) {  // queries per wave: 8, or 2 / 1 for small batches (see sa_route)
     constexpr int Q = decltype(qtag)::value;
-    SaPlan plan;
-    if ((rc = sa_plan<Q>(nq, B, npoint, 8, stream, "mpx_sa_mlp_factored", &plan))) return;
     hipLaunchKernelGGL((sa_mlp_packed_kernel<64, 128, 128, 256, Q, true>), dim3((unsigned)plan.grid), dim3(64), 0,
                        mpx_s(stream), nullptr, 0, nullptr, 0, nullptr, 0, idx, cnt, nq, N, npoint, nsample, wpack, out,
                        out_stride, plan.bpe, pre, ctr, 0, plan.queue);
   };
-  if (nq >= 1024 * SA2_Q) go(std::integral_constant<int, SA2_Q>{});
-  else if (nq >= 1024) go(std::integral_constant<int, 2>{});
-  else go(std::integral_constant<int, 1>{});  // a handful of problems: one query (1-2 tiles) per wave
-  if (rc) return rc;
+  switch (r.Q) {
+    case SA2_Q: go(std::integral_constant<int, SA2_Q>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    default: go(std::integral_constant<int, 1>{}); break;
+  }
   MPX_LAUNCH_CHECK("mpx_sa_mlp_factored");
+}
+
+MPX_EXPORT int mpx_sa_mlp_route(int cus, int B, int npoint, int nsample, int has_counts, int C, int bf16x3, int factored,
+                                int out_aligned, int32_t *route) {
+  const SaRoute r = sa_route(cus > 0 ? cus : mpx_cu_count(), B, npoint, nsample, has_counts != 0, C, bf16x3 != 0, factored != 0,
+                             out_aligned != 0);
+  const int32_t v[10] = {r.packed, r.Q, r.lpool, (int32_t)r.units, r.epx, r.persistent, r.slots, r.resident, r.one_env, r.xcd_aware};
+  for (int i = 0; i < 10; ++i) route[i] = v[i];
+  return 0;
 }
 
 MPX_EXPORT int64_t mpx_sa_pack_size(int C, int c1, int c2, int c3) {

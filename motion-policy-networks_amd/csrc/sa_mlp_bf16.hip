@@ -24,7 +24,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int G = 8;                      // step-tiles per chunk
 constexpr int TILE_BYTES = 2048;          // w_hi (64 lanes x 16 B) + w_lo
 constexpr int CHUNK_BYTES = G * TILE_BYTES;
-constexpr int WAVES = 8;                  // lockstep waves per workgroup
+constexpr int WAVES = SA_BF16_WAVES;      // lockstep waves per workgroup (launch_routes.h)
 
 template <int CF, int C1, int C2, int C3>
 struct BCfg {
@@ -483,7 +483,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 // arithmetic (split products, fp32 accumulate, exact fp32 bias) and operand layouts -- the pack of mpx_sa_pack_bf16x3 is
 // used as it is.  Four waves per SIMD cover each other's gather / split / pooling phases.
 namespace res {
-constexpr int WV = 4, OCC = 4;  // waves per workgroup; waves per SIMD
+constexpr int WV = SA_BF16_RES_WV, OCC = 4;  // waves per workgroup (launch_routes.h); waves per SIMD
 }
 template <int CF, int C1, int C2, int C3, int Q, bool ONE_ENV>
 __global__ void __launch_bounds__(64 * res::WV) __attribute__((amdgpu_waves_per_eu(res::OCC, res::OCC)))
@@ -767,7 +767,7 @@ __global__ void __launch_bounds__(64 * res::WV) __attribute__((amdgpu_waves_per_
 // Arithmetic, operand layouts and the weight pack are exactly those of sa_mlp_bf16_kernel<64,128,128,256,Q,true>.
 namespace v2 {
 using Cfg = BCfg<64, 128, 128, 256>;
-constexpr int Q = 8, WV = 4;
+constexpr int Q = SA_BF16_V2_Q, WV = 4;  // (Q: launch_routes.h)
 constexpr int C1 = 128, C2 = 128, C3 = 256;
 constexpr int W2_OFF = Cfg::O2 * TILE_BYTES;                 // first layer-2 step-tile (s-major, output tile inner)
 constexpr int W3_OFF = Cfg::O3 * TILE_BYTES;                 // first layer-3 step-tile (output tile major, s inner)
@@ -1260,12 +1260,7 @@ __global__ void __launch_bounds__(64 * v2::WV) __attribute__((amdgpu_waves_per_e
 }
 
 // ---- host entry points --------------------------------------------------------------------------------------------
-// Which kernel serves mpx_sa_mlp_bf16x3: the weight-resident one for the first module (pack fits LDS) up to 128 slots
-// per neighbourhood, the lockstep one otherwise.  ONE predicate for the launcher and for mpx_sa_mlp_bf16x3_wants_order.
-static bool bf16_uses_resident(int C, int c1, int c2, int c3, int nsample) {
-  return C == 1 && c1 == 64 && c2 == 64 && c3 == 64 && nsample <= 128;
-}
-
+// (which kernel serves mpx_sa_mlp_bf16x3 -- bf16_uses_resident -- and every launch shape below: sa_route, launch_routes.h)
 template <int CF, int C1, int C2, int C3>
 static int launch_sa_bf16(const float *xyz, int stride, const float *new_xyz, int new_stride, const float *feat,
                           int feat_stride, const int32_t *idx, const int32_t *cnt, const int32_t *order, int B, int N,
@@ -1274,28 +1269,25 @@ static int launch_sa_bf16(const float *xyz, int stride, const float *new_xyz, in
   const int64_t nq = (int64_t)B * npoint;
   MPX_REQUIRE(nq < ((int64_t)1 << 31), "mpx_sa_mlp_bf16x3: too many query points");
   constexpr int Q = CF == 1 ? 16 : 4;  // queries per wave
+  const SaRoute r = sa_route(mpx_cu_count(), B, npoint, nsample, cnt != nullptr, CF, true, false, false);
+  const dim3 grid((unsigned)r.units);
+  const unsigned char *wp = static_cast<const unsigned char *>(wpack);
   if constexpr (CF == 1) {
-    if (bf16_uses_resident(CF, C1, C2, C3, nsample)) {  // (walks the queries in their natural order: `order` is not needed)
-      const int64_t per_wg = (int64_t)res::WV * Q;
-      const int wpe = (npoint % per_wg == 0 && B % 8 == 0) ? (int)(npoint / per_wg) : 0;
+    if (r.resident) {  // (walks the queries in their natural order: `order` is not needed)
       const int row16 = (feat == xyz + 3 && stride == 4 && feat_stride == 4 && ((uintptr_t)xyz & 15) == 0) ? 1 : 0;
-      const dim3 grid((unsigned)((nq + per_wg - 1) / per_wg));
-      const unsigned char *wp = static_cast<const unsigned char *>(wpack);
       auto go = [&](auto one_env) {  // ONE_ENV: a wave's queries share their environment
         hipLaunchKernelGGL((sa_mlp_bf16_resident_kernel<CF, C1, C2, C3, Q, decltype(one_env)::value>), grid, dim3(64 * res::WV), 0,
                            mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, nq, N, npoint, nsample,
-                           wp, out, out_stride, wpe, row16, append_centre);
+                           wp, out, out_stride, r.epx, row16, append_centre);
       };
-      if (npoint % Q == 0) go(std::true_type{});
+      if (r.one_env) go(std::true_type{});
       else go(std::false_type{});
       MPX_LAUNCH_CHECK("mpx_sa_mlp_bf16x3");
     }
   }
   MPX_REQUIRE(!append_centre, "mpx_sa_mlp_bf16x3: append_centre is implemented by the weight-resident kernel only");
-  const int64_t per_block = (int64_t)WAVES * Q;
-  hipLaunchKernelGGL((sa_mlp_bf16_kernel<CF, C1, C2, C3, Q>), dim3((unsigned)((nq + per_block - 1) / per_block)),
-                     dim3(64 * WAVES), 0, mpx_s(stream), xyz, stride, new_xyz, new_stride, feat, feat_stride, idx, cnt, order, nq, N, npoint, nsample,
-                     static_cast<const unsigned char *>(wpack), out, out_stride);
+  hipLaunchKernelGGL((sa_mlp_bf16_kernel<CF, C1, C2, C3, Q>), grid, dim3(64 * WAVES), 0, mpx_s(stream), xyz, stride, new_xyz,
+                     new_stride, feat, feat_stride, idx, cnt, order, nq, N, npoint, nsample, wp, out, out_stride);
   MPX_LAUNCH_CHECK("mpx_sa_mlp_bf16x3");
 }
 
@@ -1322,9 +1314,9 @@ MPX_EXPORT int mpx_sa_mlp_bf16x3_factored(const float *pre, const float *ctr, co
   const int64_t nq = (int64_t)B * npoint;
   MPX_REQUIRE(nq < ((int64_t)1 << 31), "mpx_sa_mlp_bf16x3_factored: too many query points");
   (void)order;  // the persistent kernel takes its units from a device-side queue: no sorting pass
-  const int grid = mpx_cu_count();
+  const SaRoute r = sa_route(mpx_cu_count(), B, npoint, nsample, true, C, true, true, false);
+  const int grid = r.slots, xcd_aware = r.xcd_aware;
   MPX_REQUIRE(grid > 0, "mpx_sa_mlp_bf16x3_factored: cannot query the CU count");
-  const int xcd_aware = (B % 8 == 0 && grid % 8 == 0 && npoint % v2::Q == 0) ? 1 : 0;
   int exhausted = 0;
   unsigned int *queue = mpx_unit_queue_for(mpx_s(stream), &exhausted);
   MPX_REQUIRE(queue != nullptr, exhausted ? "mpx_sa_mlp_bf16x3_factored: no unit-queue slot left for this stream (256 "

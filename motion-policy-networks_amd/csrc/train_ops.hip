@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256)
 // fp32 FMAs in an order fixed by the launch (a different summation order than the dense kernels; inside a row of
 // mpx_pool_dgrad the channels are added in the order of an LDS counter's ranks: the hardware's lane order, the same
 // from run to run -- tests/test_gpu_training.py asserts repeated launches bit-identical).
-constexpr int PB_KC = 64;  // columns of a wave's task: one per lane
+// (PB_KC, the columns of a wave's task -- one per lane: launch_routes.h)
 __device__ __forceinline__ float pool_gz(float g, float o, int act) {
   return act == MPX_ACT_RELU ? (o > 0.0f ? g : 0.0f) : (act == MPX_ACT_LEAKY ? (o >= 0.0f ? g : 0.01f * g) : g);
 }
@@ -363,14 +363,10 @@ __global__ void __launch_bounds__(64)
   if (with_bias && blockIdx.y == 0 && c < C) p[(size_t)C * K + c] = accb;
 }
 
-static int64_t pool_wgrad_splits(int64_t Q, int C, int K) {
-  const int64_t blocks = (int64_t)cdiv(C, 64) * cdiv(K, PB_KC);
-  int64_t S = cdiv((int64_t)4096, blocks);
-  const int64_t maxs = cdiv(Q, (int64_t)8);  // >= 8 queries per split
-  if (S > maxs) S = maxs;
-  return S < 1 ? 1 : (S > 65535 ? 65535 : S);
+MPX_EXPORT int mpx_pool_wgrad_route(int64_t Q, int C, int K, int32_t *route) {
+  route[0] = (int32_t)pool_wgrad_splits(Q, C, K);
+  return 0;
 }
-
 MPX_EXPORT int64_t mpx_pool_wgrad_scratch(int64_t Q, int C, int K) {
   return pool_wgrad_splits(Q, C, K) * ((int64_t)C * K + C);  // floats
 }

@@ -69,6 +69,12 @@ PROTOTYPES = {
     "mpx_scene_cloud": [P, P, P, I, P, P, P, P, I, I, I, ctypes.c_uint64, L, P, P, P, P, L, I, I, P],
     "mpx_set_variant": [I, I],
     "mpx_get_variant": [I],
+    "mpx_fps_route": [I, I, P],
+    "mpx_franka_collision_route": [I, I, I, I, I, I, P],
+    "mpx_linear_route": [I, I, I, P],
+    "mpx_linear_wgrad_route": [I, I, I, P],
+    "mpx_pool_wgrad_route": [L, I, I, P],
+    "mpx_sa_mlp_route": [I, I, I, I, I, I, I, I, I, P],
     "mpx_fps": [P, I, I, I, I, P, P, I, P],
     "mpx_ball_query": [P, I, P, I, I, I, I, F, I, P, P, P],
     "mpx_ball_query_hits": [P, I, P, I, I, I, I, F, I, P, P, P],

@@ -1,5 +1,5 @@
-"""Restatement of the primitive collision sweep (csrc/franka.hip, ``mpx_franka_collision``) on the CPU in float64, a
-mirror of its launcher's routing, and the shapes and seeded inputs of tests/test_gpu_collision_forms.py.
+"""Restatement of the primitive collision sweep (csrc/franka.hip, ``mpx_franka_collision``) on the CPU in float64, its
+launcher's routing as the library reports it, and the shapes and seeded inputs of tests/test_gpu_collision_forms.py.
 
 ``restate`` works from what the kernel itself works from: FLOAT32 sphere centres (``FrankaCollisionSampler.sphere_centers``,
 which the sweep reproduces bit for bit) and the float32 inverse frames the device produced (``TorchCuboids.inv_frames``);
@@ -23,38 +23,18 @@ from collections import namedtuple
 
 import numpy as np
 
+from launch_routes import collision_fields, collision_route as route  # noqa: F401  (the launcher's own routing)
+
 MEASURED_GAP = 2.25e-07   # largest |restate32 - restate64| over the finite entries of all CASES (see the module docstring)
 SDF_BAR = 9.0e-07         # = 4 x MEASURED_GAP, metres
 UNDECIDED_CAP = 0.02      # share of a case's environments that may be undecided
 
-# ---- constants of the launcher (each one: where it is defined) -----------------------------------------------------------
-COL_PPB = 16      # csrc/franka.hip:137 (constexpr int COL_PPB): (environment, waypoint) pairs per workgroup, general kernel
-MPX_COL_TC = 64   # csrc/franka.hip:209 (#define MPX_COL_TC): waypoints per workgroup, per-environment kernel
-ENV_BLOCK = 256   # csrc/franka.hip:426-433 (COL_ENV(256, ...)): threads of the per-environment kernel's workgroup
 
-
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def route(B, T, S, M1, M2, aligned=True):
-    """-> (name, chunks, last): the kernel ``mpx_franka_collision`` launches for this shape -- "general", "wave" or
-    "ppt2" .. "ppt16" -- the number of waypoint chunks per environment and the (waypoint, sphere) pairs of the last
-    chunk.  For the general kernel: the number of workgroups and the pairs of the last one.  None where nothing is
-    launched.  The flags-only form (``min_sdf == NULL``) takes the same route: the launcher never looks at that pointer."""
-    if B == 0 or T == 0 or S == 0:                                   # csrc/franka.hip:403
-        return None
-    if M1 <= 64 and M2 <= 64 and S <= 64 and aligned:                # csrc/franka.hip:409
-        if T * S <= 64:                                              # csrc/franka.hip:423  COL_ENV(64, 64, 1)
-            return "wave", _cdiv(T, 64), (T - (_cdiv(T, 64) - 1) * 64) * S
-        chunks = _cdiv(T, MPX_COL_TC)                                # csrc/franka.hip:412
-        last = (T - (chunks - 1) * MPX_COL_TC) * S                   # csrc/franka.hip:223,268 (nt, npairs of the last block)
-        sel = (min(T, MPX_COL_TC) * S + 511) // 512                  # csrc/franka.hip:425
-        ppt = {1: 2, 2: 4, 3: 6, 4: 8, 5: 10, 6: 12, 7: 14}.get(sel, 16)  # csrc/franka.hip:426-433
-        return "ppt%d" % ppt, chunks, last
-    G = B * T                                                        # csrc/franka.hip:439
-    groups = _cdiv(G, COL_PPB)                                       # csrc/franka.hip:440
-    return "general", groups, (G - (groups - 1) * COL_PPB) * S       # csrc/franka.hip:148 (ng of the last block)
+def env_form():
+    """-> (threads, waypoints per chunk) of the per-environment 256-thread form, as the library reports them."""
+    form, _, threads, tc, _, _ = collision_fields(2, 64, 56, 16, 16)
+    assert form == 3
+    return threads, tc
 
 
 ROUTES = ("general", "wave") + tuple("ppt%d" % p for p in range(2, 17, 2))

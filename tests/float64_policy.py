@@ -1,7 +1,7 @@
 """The float64 policy of the parity tests, shared by the inference-forward test (test_gpu_batch_parity.py) and the
 training-step test (test_gpu_training_parity.py): the benchmark problem and the seeded weights, the per-module float64
-references with their magnitude pass (see test_gpu_batch_parity.py's docstring for the bars), the C launchers' dense-GEMM
-route predicates and the per-element comparator.  A plain module, imported by the tests: it holds no test of its own."""
+references with their magnitude pass (see test_gpu_batch_parity.py's docstring for the bars) and the per-element
+comparator.  (Which kernel a shape takes is asked of the library: launch_routes.py.)  A plain module, imported by the tests: it holds no test of its own."""
 import numpy as np
 import pytest
 import torch
@@ -10,26 +10,10 @@ import torch.nn.functional as F
 KAPPA = {"fp32": 1e-6, "bf16x3": 3e-5}  # relative rounding bar per module (see the forward test's docstring)
 SLAB = 64  # environments per float64 slab: SA1's padded rows, 64 * 512 * 128 x 64 channels x 8 B = 2.1 GB per activation
 NP1, NP2, NS = 512, 128, 128            # model.py MPiNetsPointNet._build_model: npoint / nsample of SA1, SA2
-DENSE_BM = DENSE_BN = 128               # csrc/dense.hip:21
 
 
 def _cdiv(a, b):
     return -(-a // b)
-
-
-def gemv_fits(M, K):  # csrc/dense.hip:341
-    return M <= 8 and (1 if M <= 1 else 2 if M <= 2 else 4 if M <= 4 else 8) * K * 4 <= 64 * 1024
-
-
-def linear_route(M, N, K):
-    """Which kernel ``pointnet2.linear`` (mpx_linear / mpx_linear_ws) runs: csrc/dense.hip:341 gemv_fits, :529 splitk_plan."""
-    if gemv_fits(M, K):
-        return "gemv"
-    tiles = _cdiv(M, DENSE_BM) * _cdiv(N, DENSE_BN)
-    if tiles >= 128 or K < 256 or M > 1024:
-        return "tile"
-    S = min(_cdiv(512, tiles), _cdiv(K, 16) // 4)
-    return "split-K" if S >= 2 else "tile"
 
 
 def cu_count():

@@ -95,7 +95,7 @@ def test_symbols_are_exported_bound_and_declared():
     for name, nargs in ((NAME, 26), (NAME + "_scratch", 2)):
         assert hasattr(lib, name) and name in header_symbols()
         assert name in _lib.PROTOTYPES and len(_lib.PROTOTYPES[name]) == nargs
-    assert _lib.load().mpx_version() == 340
+    assert _lib.load().mpx_version() == 341
     assert _lib.RESTYPES[NAME + "_scratch"] is ctypes.c_int64
     np.testing.assert_array_equal(capture.REFERENCE_WORKSPACE, f64.WORKSPACE)
     assert capture.REFERENCE_WORKSPACE.dtype == np.float32 and capture.REFERENCE_WORKSPACE.shape == (2, 6)

@@ -62,7 +62,7 @@ def test_symbol_is_exported_bound_and_declared():
     assert hasattr(lib, NAME)
     assert NAME in _lib.PROTOTYPES and len(_lib.PROTOTYPES[NAME]) == 19
     assert NAME in header_symbols()
-    assert _lib.load().mpx_version() == 340
+    assert _lib.load().mpx_version() == 341
     # the constants the tests restate are the header's
     assert f64.WAYPOINT_CHUNK == f64._header_constant("MPX_CLOUD_TC")
     assert f64.TILE == f64._header_constant("MPX_CLOUD_TILE")

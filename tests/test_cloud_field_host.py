@@ -157,7 +157,7 @@ def test_bad_arguments_are_refused_on_the_host():
     from mpinets_amd import _lib
 
     lib = _lib.load()
-    assert lib.mpx_version() == 340
+    assert lib.mpx_version() == 341
     one = ctypes.c_void_p(256)  # any non-NULL "device pointer": validation fails before it is touched
 
     def build(grid=None, B=2, N=8, stride=3, cloud=one, field=one):

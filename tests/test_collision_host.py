@@ -1,4 +1,4 @@
-"""CPU: the cases of tests/test_gpu_collision_forms.py are sound before anything runs on a GPU -- the route mirror of
+"""CPU: the cases of tests/test_gpu_collision_forms.py are sound before anything runs on a GPU -- the route query of
 ``mpx_franka_collision`` says they reach every launch form at both ends of its range, the float64 restatement agrees with
 closed forms and with the C oracle, ``SDF_BAR`` can be derived again, and the restatement alone stays inside the undecided
 cap on the seeds the GPU test uses."""
@@ -65,7 +65,7 @@ def test_closed_forms_to_round_off():
 
 
 def test_cases_reach_every_route_at_both_ends_of_its_range():
-    """``route`` mirrors the launcher; over CASES it takes every value.  Every case runs in the full and in the
+    """``route`` is the launcher's own plan; over CASES it takes every value.  Every case runs in the full and in the
     flags-only form (the launcher does not look at ``min_sdf``), so both forms reach every route."""
     routes = {c: fc.case_route(c) for c in fc.CASES}
     for c, r in routes.items():
@@ -74,10 +74,12 @@ def test_cases_reach_every_route_at_both_ends_of_its_range():
     assert fc.FORMS == ("full", "flags_only")
     # an unaligned frame pointer sends every case to the general kernel (the bit-for-bit comparison of the GPU test)
     assert {fc.case_route(c, aligned=False)[0] for c in fc.CASES} == {"general"}
-    # S = 56 and S = 57: the lowest and the highest T of every form's range, found by walking the mirror itself
+    env_block, col_tc = fc.env_form()
+    assert (env_block, col_tc) == (256, 64)
+    # S = 56 and S = 57: the lowest and the highest T of every form's range, found by walking the route query itself
     for S, table in ((56, "S56"), (57, "S57")):
         spans = {}
-        for T in range(1, fc.MPX_COL_TC + 1):
+        for T in range(1, col_tc + 1):
             spans.setdefault(fc.route(2, T, S, 16, 16)[0], []).append(T)
         have = {(routes[c][0], c.T) for c in fc.CASES if c.table == table}
         for name, ts in spans.items():
@@ -89,22 +91,16 @@ def test_cases_reach_every_route_at_both_ends_of_its_range():
     for p in range(2, 17, 2):
         mine = [r for r in routes.values() if r[0] == "ppt%d" % p]
         assert any(ch == 1 for _, ch, _ in mine), p
-        assert any(ch > 1 and last < fc.ENV_BLOCK for _, ch, last in mine), p
+        assert any(ch > 1 and last < env_block for _, ch, last in mine), p
     # the shapes the issue names
     by_id = {fc.case_id(c): r for c, r in routes.items()}
-    assert by_id["B3-T64-S64tile-M16x16"] == ("ppt16", 1, 16 * fc.ENV_BLOCK)  # every thread 16 live pairs
+    assert by_id["B3-T64-S64tile-M16x16"] == ("ppt16", 1, 16 * env_block)  # every thread 16 live pairs
     assert by_id["B4-T1-S64tile-M16x16"] == ("wave", 1, 64) and by_id["B3-T64-S1tile-M16x16"] == ("wave", 1, 64)
     assert by_id["B3-T65-S1tile-M16x16"] == ("ppt2", 2, 1)
     assert by_id["B3-T3-S65tile-M16x16"][0] == by_id["B3-T9-S56-M70x16"][0] == by_id["B2-T2-S56-M16x65"][0] == "general"
     assert by_id["B70-T50-S56-M40x16"] == ("ppt12", 1, 2800)
     # nothing to launch
     assert fc.route(0, 5, 56, 16, 16) is None and fc.route(3, 0, 56, 16, 16) is None and fc.route(3, 5, 0, 16, 16) is None
-    # the constants the mirror restates are the source's
-    import os
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "motion-policy-networks_amd", "csrc",
-                            "franka.hip")).read()
-    assert "constexpr int COL_PPB = %d;" % fc.COL_PPB in src and "#define MPX_COL_TC %d " % fc.MPX_COL_TC in src
-    assert "COL_ENV(256, MPX_COL_TC, 16)" in src and "COL_ENV(64, 64, 1)" in src
 
 
 def test_scene_edges_are_what_they_claim(evaluated):

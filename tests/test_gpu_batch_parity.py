@@ -3,8 +3,8 @@
 The kernels switch launch shapes with the batch size (queries per wave, a persistent grid fed from a device-side unit queue,
 whole environments per XCD, the fused group-all chain, XCD remaps in the pairs GEMMs, split-K / gemv heads).  A unit
 claimed twice or skipped, a wrong tail unit or a remap that sends a tile to the wrong rows stays deterministic and finite,
-so only a full-tensor comparison with an independent reference can see it.  ``route_table`` mirrors the C predicates and
-``test_parametrization_covers_every_route`` makes sure the cases below turn each route on AND off.
+so only a full-tensor comparison with an independent reference can see it.  ``route_table`` asks the library which forms
+its launchers take (launch_routes.py) and ``test_parametrization_covers_every_route`` makes sure the cases below turn each route on AND off.
 
 Reference: float64, torch ops only (gather, matmul, amax, group_norm, leaky_relu), nothing from ``libmpinets_hip``
 except the sampling / neighbour INDICES, which depend on geometry alone (checked bit-exact against the C oracle on a
@@ -39,8 +39,9 @@ import numpy as np
 import pytest
 import torch
 
-from float64_policy import (KAPPA, NP1, NP2, NS, _cdiv, _gather, _sa_layers, check, cu_count, linear_route,  # noqa: F401
+from float64_policy import (KAPPA, NP1, NP2, NS, _cdiv, _gather, _sa_layers, check, cu_count,  # noqa: F401
                             offending_envs, problem, reference, sa1_rows, sa2_rows, weights)
+from launch_routes import linear_route, sa_route
 
 pytestmark = pytest.mark.gpu
 
@@ -64,39 +65,25 @@ CASES = [
     (4, "bf16x3", True),
 ]
 
-# ---- constants of the C launchers (each one: where it is defined) -----------------------------------------------------
-MPX_SA1_Q = 32                          # csrc/sa_mlp.hip:34  (constexpr int SA1_Q)
-MPX_SA2_Q = 8                           # csrc/sa_mlp.hip:34  (constexpr int SA2_Q)
-SA1_QS = 4                              # csrc/sa_mlp.hip:784 (QS = CF == 1 ? 4 : 2) -- SA1's small-batch queries per wave
-SA2_QS = (2, 1)                         # csrc/sa_mlp.hip:858-860 (mpx_sa_mlp_factored: 2 at nq >= 1024, else 1)
-SA1_SLOTS_PER_CU = 16                   # csrc/sa_mlp.hip:789 (sa_plan<Q>(..., CF == 1 ? 16 : 8, ...): wave slots per CU)
-SA2_SLOTS_PER_CU = 8                    # csrc/sa_mlp.hip:853 (sa_plan<Q>(..., 8, ...))
-SA3_CHAIN_MIN_BATCH = 256               # csrc/policy.hip:137, model.py:39
-BF16_SA1_Q, BF16_RES_WV = 16, 4         # csrc/sa_mlp_bf16.hip:1276 (Q), :486 (res::WV) -- the weight-resident SA1 kernel
-BF16_SA2_Q = 8                          # csrc/sa_mlp_bf16.hip:770 (v2::Q) -- the persistent SA2 kernel
-PAIRS_BM = 256                          # csrc/dense_bf16.hip:253 (Y_BM)
+SA3_CHAIN_MIN_BATCH = 256               # model.py (asserted equal below)
+PAIRS_BM = 256                          # rows per tile of the bf16x3 pairs GEMMs (gridDim.y = cdiv(rows, 256))
 
 
 def route_table(B, precision, elide, cus, aux):
     """{route: True / False, or None where the route does not exist in this precision} for one forward call."""
     fp32 = precision == "fp32"
     r = {}
-    # -- SA1 grouped MLP (csrc/sa_mlp.hip launch_sa; csrc/sa_mlp_bf16.hip launch_sa_bf16) --
-    nq1 = B * NP1
-    packed = elide  # counts given: the packed kernel; without them sa_mlp_kernel walks every slot
-    q1 = MPX_SA1_Q if nq1 >= 1024 * MPX_SA1_Q else SA1_QS
-    r["SA1 non-packed sa_mlp_kernel (padding kept)"] = (not elide) if fp32 else None
-    r["SA1 large Q (32 queries / wave)"] = (packed and q1 == MPX_SA1_Q) if fp32 else None
-    r["SA1 persistent grid from the unit queue"] = (packed and _cdiv(nq1, q1) >= 4 * ((cus * SA1_SLOTS_PER_CU) & ~7)) if fp32 else None
-    r["SA1 whole environments per XCD (bpe / wpe)"] = ((packed and NP1 % q1 == 0 and B % 8 == 0) if fp32 else
-                                                       (NP1 % (BF16_RES_WV * BF16_SA1_Q) == 0 and B % 8 == 0))
+    # -- SA1 grouped MLP (mpx_sa_mlp; mpx_sa_mlp_bf16x3): counts given = the packed kernel; without them every slot is walked --
+    sa1 = sa_route(cus, B, NP1, NS, elide, 1, precision, False)
+    r["SA1 non-packed sa_mlp_kernel (padding kept)"] = (not sa1.packed) if fp32 else None
+    r["SA1 large Q (32 queries / wave)"] = bool(sa1.packed and sa1.Q == 32) if fp32 else None
+    r["SA1 persistent grid from the unit queue"] = bool(sa1.packed and sa1.persistent) if fp32 else None
+    r["SA1 whole environments per XCD (bpe / wpe)"] = bool(sa1.packed and sa1.per_env > 0) if fp32 else sa1.per_env > 0
     # -- SA2 grouped MLP, factored (mpx_sa_mlp_factored; mpx_sa_mlp_bf16x3_factored is always persistent) --
-    nq2 = B * NP2
-    q2 = MPX_SA2_Q if nq2 >= 1024 * MPX_SA2_Q else SA2_QS[0] if nq2 >= 1024 else SA2_QS[1]
-    r["SA2 large Q (8 queries / wave)"] = (q2 == MPX_SA2_Q) if fp32 else None
-    r["SA2 persistent grid from the unit queue"] = (_cdiv(nq2, q2) >= 4 * ((cus * SA2_SLOTS_PER_CU) & ~7)) if fp32 else None
-    r["SA2 whole environments per XCD (bpe / xcd_aware)"] = ((NP2 % q2 == 0 and B % 8 == 0) if fp32 else
-                                                             (B % 8 == 0 and cus % 8 == 0 and NP2 % BF16_SA2_Q == 0))
+    sa2 = sa_route(cus, B, NP2, NS, True, 64, precision, True)
+    r["SA2 large Q (8 queries / wave)"] = (sa2.Q == 8) if fp32 else None
+    r["SA2 persistent grid from the unit queue"] = bool(sa2.persistent) if fp32 else None
+    r["SA2 whole environments per XCD (bpe / xcd_aware)"] = sa2.per_env > 0 if fp32 else bool(sa2.xcd_aware)
     # -- group-all module (model.py MPiNetsPointNet.forward) --
     r["group-all as one kernel (mpx_sa3_chain)"] = (B >= SA3_CHAIN_MIN_BATCH) if fp32 else None
     r["bf16x3 group-all last layer: XCD remap (gridDim.y % 8 == 0)"] = None if fp32 else _cdiv(B * NP2, PAIRS_BM) % 8 == 0

@@ -161,10 +161,11 @@ def test_flags_are_ored_into_the_callers_buffer(case):
 
 
 def _owner(case, t, s):
-    """(chunk, k): the waypoint chunk of pair (t, s) and which of its thread's pairs it is (csrc/franka.hip:269:
+    """(chunk, k): the waypoint chunk of pair (t, s) and which of its thread's pairs it is (franka_collision_env_kernel:
     p = threadIdx.x + k * BLOCK over the chunk's flattened pairs)."""
     S = fc.num_spheres(case)
-    return t // fc.MPX_COL_TC, ((t % fc.MPX_COL_TC) * S + s) // fc.ENV_BLOCK
+    env_block, col_tc = fc.env_form()
+    return t // col_tc, ((t % col_tc) * S + s) // env_block
 
 
 def test_flags_only_boundary_in_the_256_thread_forms():

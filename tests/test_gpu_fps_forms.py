@@ -2,43 +2,42 @@
 uniform cloud and on a cloud of exact ties, bit for bit against the scalar oracle -- and the row strides no other test
 uses, for each kernel family of ``mpx_fps`` and of ``mpx_ball_query``.
 
-``fps_route`` mirrors the launcher's predicates; ``test_fps_cases_reach_every_instantiation`` (CPU) walks it over every N
-the entry point accepts and shows that the cases reach each instantiation at both ends of its range.  The highest N of a
-range fills the last per-lane slot on every lane, the lowest leaves it empty on most; the tie order (k mod bs, k)
-meets a different layout of points over lanes in every instantiation, so each one gets a tied cloud of its own."""
+``launch_routes.fps_route`` asks the library which instantiation a shape takes (the launcher obeys the same function);
+``test_fps_cases_reach_every_instantiation`` (CPU) walks it over every N the entry point accepts and shows that the cases
+reach each instantiation at both ends of its range.  The highest N of a range fills the last per-lane slot on every lane,
+the lowest leaves it empty on most; the tie order (k mod bs, k) meets a different layout of points over lanes in every
+instantiation, so each one gets a tied cloud of its own."""
 import numpy as np
 import pytest
 import torch
 
-# ---- constants of the launcher (each one: where it is defined) -----------------------------------------------------------
-MPX_FPS4_MIN_B = 768   # csrc/pointnet.hip:630 (#define MPX_FPS4_MIN_B)
-FPS_MAX_N = 8192       # csrc/pointnet.hip:632 (constexpr int FPS_MAX_N)
-MPX_VARIANT_FPS, MPX_VARIANT_BALL_QUERY = 0, 1  # include/mpinets_hip.h (selectors of mpx_set_variant)
+from launch_routes import FPS_MAX_N, MPX_VARIANT_BALL_QUERY, MPX_VARIANT_FPS, fps_route
+
+MPX_FPS4_MIN_B = 768   # the smallest batch at which the 4-wave form exists (asserted of the library below)
 NPOINT, NPOINT_4WAVE = 48, 16
-
-
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def fps_route(B, N, variant=1):
-    """-> ("wave" | "cull8" | "cull4" | "plain", P): the kernel family and the points-per-lane instantiation of ``mpx_fps``."""
-    assert 1 <= N <= FPS_MAX_N                                        # csrc/pointnet.hip:661-662
-    if variant and N <= 512:                                          # csrc/pointnet.hip:667
-        return "wave", {1: 1, 2: 2, 3: 4, 4: 4}.get(_cdiv(N, 64), 8)  # csrc/pointnet.hip:670-675
-    if variant and N > 512:                                           # csrc/pointnet.hip:679
-        waves = 4 if (N > 16 * 256 and B >= MPX_FPS4_MIN_B) else 8    # csrc/pointnet.hip:684
-        pts_c = _cdiv(N, 64 * waves)                                  # csrc/pointnet.hip:696
-        if waves == 4:                                                # csrc/pointnet.hip:697-700
-            return "cull4", 20 if pts_c <= 20 else 25 if pts_c <= 25 else 32
-        return "cull8", next((p for p in (2, 4, 6, 8, 10, 13) if pts_c <= p), 16)  # csrc/pointnet.hip:701-707
-    block = min(_cdiv(N, 64) * 64, 512)                               # csrc/pointnet.hip:711-712
-    pts = _cdiv(N, block)                                             # csrc/pointnet.hip:713
-    return "plain", {9: 10, 11: 13, 12: 13, 14: 16, 15: 16}.get(pts, pts)  # csrc/pointnet.hip:722-733
-
 
 INSTANTIATIONS = ([("wave", p) for p in (1, 2, 4, 8)] + [("cull8", p) for p in (2, 4, 6, 8, 10, 13, 16)]
                   + [("cull4", p) for p in (20, 25, 32)] + [("plain", p) for p in (1, 2, 3, 4, 5, 6, 7, 8, 10, 13, 16)])
+
+# (family, B, variant, npoint, {P: (the lowest, the highest N of the instantiation's range)}): the cases, written out --
+# test_fps_cases_reach_every_instantiation holds every tag and every range end against the library
+TAGGED = [
+    ("wave", 2, 1, NPOINT, {1: (1, 64), 2: (65, 128), 4: (129, 256), 8: (257, 512)}),
+    ("cull8", 2, 1, NPOINT, {2: (513, 1024), 4: (1025, 2048), 6: (2049, 3072), 8: (3073, 4096), 10: (4097, 5120),
+                             13: (5121, 6656), 16: (6657, 8192)}),
+    ("plain", 2, 0, NPOINT, {1: (1, 512), 2: (513, 1024), 3: (1025, 1536), 4: (1537, 2048), 5: (2049, 2560), 6: (2561, 3072),
+                             7: (3073, 3584), 8: (3585, 4096), 10: (4097, 5120), 13: (5121, 6656), 16: (6657, 8192)}),
+    # 768 is the smallest batch at which the 4-wave form exists
+    ("cull4", MPX_FPS4_MIN_B, 1, NPOINT_4WAVE, {20: (4097, 5120), 25: (5121, 6400), 32: (6401, 8192)}),
+]
+CASES = [(B, N, variant, npoint) for _, B, variant, npoint, ends in TAGGED for lo_hi in ends.values() for N in lo_hi]
+TAGS = {(B, N, variant): (fam, P) for fam, B, variant, _, ends in TAGGED for P, lo_hi in ends.items() for N in lo_hi}
+
+
+def case_id(case):
+    B, N, variant, npoint = case
+    fam, P = TAGS[B, N, variant]
+    return f"{fam}{P}-B{B}-N{N}"
 
 
 def _ranges(B, variant):
@@ -48,32 +47,17 @@ def _ranges(B, variant):
     return {k: (v[0], v[-1]) for k, v in spans.items()}
 
 
-def _cases():
-    cases = []
-    for B, variant, npoint in ((2, 1, NPOINT), (2, 0, NPOINT)):
-        for lo, hi in _ranges(B, variant).values():
-            cases += [(B, lo, variant, npoint), (B, hi, variant, npoint)]
-    # 768 is the smallest batch at which the 4-wave form exists
-    cases += [(MPX_FPS4_MIN_B, N, 1, NPOINT_4WAVE) for N in (4097, 5120, 5121, 6400, 6401, 8192)]
-    return cases
-
-
-CASES = _cases()
-
-
-def case_id(case):
-    B, N, variant, npoint = case
-    fam, P = fps_route(B, N, variant)
-    return f"{fam}{P}-B{B}-N{N}"
-
-
 def test_fps_cases_reach_every_instantiation():
-    """CPU: the mirror takes exactly the instantiations the launcher has, and CASES holds both ends of each one's range."""
+    """CPU: the launcher takes exactly the instantiations listed, every case's tag is the library's route for it, and CASES
+    holds both ends of each instantiation's range."""
     reach = {}
     for B, variant in ((2, 1), (2, 0), (MPX_FPS4_MIN_B, 1), (MPX_FPS4_MIN_B - 1, 1)):
         for key, span in _ranges(B, variant).items():
             reach.setdefault(key, set()).add(span)
     assert set(reach) == set(INSTANTIATIONS)
+    assert len(CASES) == 50 and len(TAGS) == len(CASES)
+    for B, N, v, _ in CASES:
+        assert fps_route(B, N, v) == TAGS[B, N, v], (B, N, v)
     have = {(fps_route(B, N, v), N) for B, N, v, _ in CASES}
     for key, spans in sorted(reach.items()):
         print(key, sorted(spans))
@@ -83,12 +67,9 @@ def test_fps_cases_reach_every_instantiation():
     assert fps_route(MPX_FPS4_MIN_B - 1, 8192)[0] == "cull8" and fps_route(MPX_FPS4_MIN_B, 4096) == ("cull8", 8)
     assert fps_route(MPX_FPS4_MIN_B, 4097) == ("cull4", 20) and fps_route(2, 512) == ("wave", 8) and fps_route(2, 513) == ("cull8", 2)
     assert fps_route(2, 512, 0) == ("plain", 1) and fps_route(2, 513, 0) == ("plain", 2) and fps_route(2, 8192, 0) == ("plain", 16)
-    # the constants the mirror restates are the source's
+    # the selectors this file passes to mpx_set_variant are the header's
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "motion-policy-networks_amd", "csrc", "pointnet.hip")).read()
-    assert "#define MPX_FPS4_MIN_B %d " % MPX_FPS4_MIN_B in src and "constexpr int FPS_MAX_N = %d;" % FPS_MAX_N in src
-    assert "(N > 16 * 256 && B >= MPX_FPS4_MIN_B) ? 4 : 8" in src
     hdr = open(os.path.join(root, "include", "mpinets_hip.h")).read()
     assert "#define MPX_VARIANT_FPS %d\n" % MPX_VARIANT_FPS in hdr and "#define MPX_VARIANT_BALL_QUERY %d\n" % MPX_VARIANT_BALL_QUERY in hdr
 

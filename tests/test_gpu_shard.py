@@ -7,7 +7,7 @@ batch BIT FOR BIT.  That holds because every random draw is keyed by the global 
 (mpx_scene_cloud's env_offset) and no kernel couples environments.
 
 Batch sizes: the dense layers pick their launch shape from the row count (split-K below 1025 rows and few output
-tiles, csrc/dense.hip splitk_plan), which changes the fp32 summation order; E and 2E are chosen inside one regime
+tiles, csrc/launch_routes.h linear_route), which changes the fp32 summation order; E and 2E are chosen inside one regime
 (24 | 48: both split the same way; 1040 | 2080: neither splits), like the 8192-per-rank bench shards.
 """
 import os

@@ -62,7 +62,7 @@ test_gpu_batch_parity.py (float64_policy.reference).
 
 Controls, each planted into a fresh copy of the HIP result at >= 20 spread places where the defect changes the result at
 all; fp32 must flag >= 90 %, bf16x3 some (share printed): a dropped weight-gradient split (SA2's first layer minus the
-float64 contribution of one split's rows, split bounds from ``wgrad_splits``, splits whose rows carry gradient), a
+float64 contribution of one split's rows, split bounds from ``wgrad_route``, splits whose rows carry gradient), a
 misrouted pool gradient (SA1's last layer: one (query, channel) gradient of the largest tenth moved to the row of
 its segment that differs most), a lost scatter update (one packed row with a gradient missing from the f1 gradient).
 """
@@ -73,8 +73,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from float64_policy import (KAPPA, NP1, NP2, NS, _cdiv, check, dev, linear_route, problem, reference,  # noqa: F401
+from float64_policy import (KAPPA, NP1, NP2, NS, _cdiv, check, dev, problem, reference,  # noqa: F401
                             weights)
+from launch_routes import linear_route, pool_wgrad_splits, wgrad_route
 
 CASES = [(4, "fp32"), (4, "bf16x3"), (10, "fp32"), (10, "bf16x3"), (256, "fp32"), (256, "bf16x3")]
 MIN_CAUGHT = {"fp32": 0.9, "bf16x3": 1e-9}
@@ -90,12 +91,6 @@ U_FP32, U_X3 = 1e-6, 3e-5  # per GEMM (float64_policy.KAPPA)
 NAMES = ("cuboid_centers", "cuboid_dims", "cuboid_quats", "cylinder_centers", "cylinder_radii", "cylinder_heights",
          "cylinder_quats")
 
-# ---- constants of the C launchers (each one: where it is defined) -----------------------------------------------------
-WG_BK = 16              # csrc/dense_grad.hip:14 (rows per staged slab of mpx_linear_wgrad)
-WGRAD_TARGET = 1024     # csrc/dense_grad.hip:272 (S = cdiv(1024, tiles))
-PB_KC = 64              # csrc/train_ops.hip:165 (columns per pool_wgrad task)
-POOL_TARGET = 4096      # csrc/train_ops.hip:368 (S = cdiv(4096, blocks))
-POOL_MIN_Q = 8          # csrc/train_ops.hip:369 (>= 8 queries per split)
 X3_MIN_M, X3_MIN_N, X3_MIN_K = 1024, 128, 16  # train_ops._MLPChainFn._use_x3
 
 
@@ -106,24 +101,9 @@ def chain_u(n):
     return 3.5e-7 * max(1.0, (n / 4096) ** 0.5) + 2.0 ** -24 * n ** 0.5
 
 
-def wgrad_tile(N, K):  # csrc/dense_grad.hip:268
-    return 64 if (N <= 64 and K <= 64) else 128
-
-
-def wgrad_splits(M, N, K):  # csrc/dense_grad.hip:269
-    T = wgrad_tile(N, K)
-    S = _cdiv(WGRAD_TARGET, _cdiv(N, T) * _cdiv(K, T))
-    maxs = _cdiv(M, 4 * WG_BK)
-    return 1 if S < 1 else (max(maxs, 1) if S > maxs else S)
-
-
-def wgrad_rows_per_split(M, N, K):  # csrc/dense_grad.hip:301
-    return _cdiv(_cdiv(M, wgrad_splits(M, N, K)), WG_BK) * WG_BK
-
-
-def pool_wgrad_splits(Q, C, K):  # csrc/train_ops.hip:366
-    S = min(_cdiv(POOL_TARGET, _cdiv(C, 64) * _cdiv(K, PB_KC)), _cdiv(Q, POOL_MIN_Q))
-    return max(1, min(S, 65535))
+def _wgrad(kind, M, N, K):
+    r = wgrad_route(M, N, K)
+    return kind, r.splits, r.tile
 
 
 def use_x3(x3, M, N, K):  # train_ops._MLPChainFn._use_x3
@@ -150,14 +130,14 @@ def training_gemms(B, precision, R1, R2):
     for st, li, N, K in HEAD_LINEARS:  # train_ops._LinearFn: forward and dX through linear(), dW mpx_linear_wgrad
         Np, Kp = _p4(N), _p4(K)
         out.append(dict(stage=st, layer=li, M=B, N=Np, K=Kp, fwd=linear_route(B, Np, Kp), dx=linear_route(B, Kp, Np),
-                        wgrad=("linear", wgrad_splits(B, Np, Kp), wgrad_tile(Np, Kp)), x3=False, head=True))
+                        wgrad=_wgrad("linear", B, Np, Kp), x3=False, head=True))
     for st, layers in HEAD_CHAINS.items():  # _MLPChainFn without a pool, fp32 (model.py:597)
         for li, (N, K) in enumerate(layers):
             Np, Kp = _p4(N), _p4(K)
             dx = None if (st == "feature_encoder" and li == 0) else (
                 "split-K" if linear_route(B, Kp, Np) == "split-K" else "dact")  # the skinny route of _MLPChainFn.backward
             out.append(dict(stage=st, layer=li, M=B, N=Np, K=Kp, fwd=linear_route(B, Np, Kp), dx=dx,
-                            wgrad=("linear", wgrad_splits(B, Np, Kp), wgrad_tile(Np, Kp)), x3=False, head=True))
+                            wgrad=_wgrad("linear", B, Np, Kp), x3=False, head=True))
     for st, layers in POOLED_CHAINS.items():  # _MLPChainFn with the pool (_MLPChainFn.forward / .backward)
         M, Q = {"SA1": (R1, B * NP1), "SA2": (R2, B * NP2), "SA3": (B * NP2, B)}[st]
         for li, (N, K) in enumerate(layers):
@@ -166,7 +146,7 @@ def training_gemms(B, precision, R1, R2):
             last = li == len(layers) - 1
             dx = None if (st == "SA1" and li == 0) else ("pool_dgrad" if last else "dact-x3" if lx3 else "dact")
             wg = ("pool", pool_wgrad_splits(Q, Np, Kp), None) if last else \
-                ("linear-x3" if lx3 else "linear", wgrad_splits(M, Np, Kp), wgrad_tile(Np, Kp))
+                _wgrad("linear-x3" if lx3 else "linear", M, Np, Kp)
             out.append(dict(stage=st, layer=li, M=M, N=Np, K=Kp, fwd="segmax-x3" if (last and lx3) else "segmax" if last else
                             "x3" if lx3 else linear_route(M, Np, Kp), dx=dx, wgrad=wg, x3=lx3, head=False, Q=Q))
     return out
@@ -377,8 +357,8 @@ def chain_stage(name, rec, tm, x3, T, split_control=None):
             kw.append(chain_u(_cdiv(Q, S)) + chain_u(S))
         else:
             u_dx.append(U_X3 if lx3 else U_FP32)
-            S = wgrad_splits(M, Np, Kp)
-            kw.append(chain_u(wgrad_rows_per_split(M, Np, Kp)) + chain_u(S) + (U_X3 if lx3 else 0.0))
+            _, S, rps = wgrad_route(M, Np, Kp)
+            kw.append(chain_u(rps) + chain_u(S) + (U_X3 if lx3 else 0.0))
     dev_ = g.device
     dW = [torch.zeros_like(w) for w in Ws]
     db = [torch.zeros_like(b) for b in bs]
@@ -474,7 +454,8 @@ def linear_stage(name, rec, tm, T):
     x = xp[:, :K].double()
     g = rec["gout"][0].double()
     M = x.size(0)
-    kw = chain_u(wgrad_rows_per_split(M, _p4(N), _p4(K))) + chain_u(wgrad_splits(M, _p4(N), _p4(K)))
+    _, S, rps = wgrad_route(M, _p4(N), _p4(K))
+    kw = chain_u(rps) + chain_u(S)
     T.cmp(f"{name} dX", rec["gin"][0], g @ W, U_FP32 * (g.abs() @ W.abs()))
     return {rec["params"][0]: (g.t() @ x, kw * (g.abs().t() @ x.abs())),
             rec["params"][1]: (g.sum(0), kw * g.abs().sum(0))}
@@ -734,7 +715,7 @@ def test_training_step_matches_float64_every_stage(weights, train_model, oracle,
     assert torch.equal(nodes["SA1"]["gout"][0].reshape(B * NP1, -1), gf1)
     # chain, with the dropped-split control's row ranges of layer 0 (mpx_linear_wgrad's split bounds)
     M2, (N0, K0) = rows2.size(0), (128, rows2.size(1))
-    S0, rps0 = wgrad_splits(M2, N0, K0), wgrad_rows_per_split(M2, N0, K0)
+    _, S0, rps0 = wgrad_route(M2, N0, K0)
     ctrl_splits = _spread(S0, 2 * N_PLANT)
     ranges = [(s * rps0, min(M2, (s + 1) * rps0)) for s in ctrl_splits]
     refs2, contrib = chain_stage("SA2", nodes["SA2"], tm, x3, T, split_control=ranges)

@@ -51,7 +51,7 @@ def test_each_refuses_bad_arguments_on_the_host():
     from mpinets_amd import _lib
 
     lib = _lib.load()
-    assert lib.mpx_version() == 340
+    assert lib.mpx_version() == 341
     err = lib.mpx_last_error
     for bad in (dict(B=-1), dict(T=-1), dict(S=-1), dict(N=-1)):
         assert _each(lib, **bad) != 0 and b"negative" in err(), bad

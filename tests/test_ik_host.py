@@ -133,7 +133,7 @@ def test_bad_arguments_are_refused_on_the_host():
     from mpinets_amd import _lib
 
     lib = _lib.load()
-    assert lib.mpx_version() == 340
+    assert lib.mpx_version() == 341
     good = dict(iterations=64, lambda_=0.05, step_clip=0.5, pos_tol=1e-3, rot_tol=8.7e-3, clearance=0.0, check_self=0)
     assert _call(lib, q_out=0) != 0 and b"NULL output" in lib.mpx_last_error()
     assert _call(lib, status=0) != 0 and b"NULL output" in lib.mpx_last_error()

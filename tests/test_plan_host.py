@@ -217,7 +217,7 @@ def test_bad_arguments_are_refused_on_the_host():
     from mpinets_amd import _lib
 
     lib = _lib.load()
-    assert lib.mpx_version() == 340
+    assert lib.mpx_version() == 341
     good = dict(candidates=8, iterations=10, step=1e-3, smooth_weight=1.0, epsilon=0.05, spread=0.5, substeps=4,
                 check_margin=1e-4, clearance=0.0, max_jerk=0.15, check_self=1)
     assert _call(lib, traj=0) != 0 and b"NULL output" in lib.mpx_last_error()
