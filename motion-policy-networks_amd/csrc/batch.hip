@@ -6,6 +6,7 @@
 // quantities for a whole batch; the clouds come from the kernels of the inference path
 // (mpx_franka_cloud, mpx_pose_cloud, mpx_scene_cloud) writing straight into the [B,6272,4] slab.
 #include "common.h"
+#include "franka_device.h"
 #include "philox.h"
 
 enum { STREAM_JOINT_NOISE = 7 };

@@ -41,6 +41,7 @@
 // kernel's), and their instruction streams are pinned (tools/isa_diff.py, profiles/ik_cloud_timing.md).
 #include "common.h"
 #include "franka_host.h"
+#include "franka_device.h"
 
 constexpr int FRAME_FLOATS = MPX_NUM_FRAMES * 12;  // 180
 constexpr int CC_TC = MPX_CLOUD_TC;                // waypoints per workgroup

@@ -236,13 +236,14 @@ MPX_EXPORT int mpx_cloud_field_sample(const float *field, const mpx_field_grid *
 
 // ---- the planner ---------------------------------------------------------------------------------------------------------------
 
-// PLAN_BIT_SELF of one configuration (the frames of the self model are all the FK the compiler keeps)
+// PLAN_BIT_SELF of one configuration (the frames of the self model are all the FK the compiler keeps).  (Its own walk: through
+// plan.hip's plan_config_bits without an environment this kernel was 0.6 - 1.3 % slower, profiles/franka_device_timing.md)
 __device__ __forceinline__ int plan_self_bits(const float *q, float finger, float self_margin) {
   int bits = 0;
   franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
     constexpr int id = decltype(ID)::value;
-    if constexpr (id == 7 || id == 9 || id == 12 || id == 13) {
-      if (plan_self_hit<id>(g, self_margin)) bits |= PLAN_BIT_SELF;
+    if constexpr (franka_self_sphere(id) >= 0) {
+      if (franka_self_hit<id>(g, self_margin)) bits |= PLAN_BIT_SELF;
     }
   });
   return bits;
@@ -294,13 +295,7 @@ __global__ void __launch_bounds__(64 * MAXK)
   const int t = lane < T ? lane : T - 1;  // (lanes past the trajectory repeat the goal and never store)
 
   float lo[7], hi[7], qs[7], qg[7];
-  bool bad_end = false;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
-    qs[j] = q_start[(size_t)b * 7 + j], qg[j] = q_goal[(size_t)b * 7 + j];
-    bad_end |= !(qs[j] >= lo[j] && qs[j] <= hi[j]) || !(qg[j] >= lo[j] && qg[j] <= hi[j]);  // (NaN fails both)
-  }
+  bool bad_end = plan_endpoints(limits, q_start, q_goal, b, lo, hi, qs, qg);
   plan_fill_metric(Mtab, T, n);
   __syncthreads();
 
@@ -326,7 +321,8 @@ __global__ void __launch_bounds__(64 * MAXK)
   plan_candidate(k, t, T, env0 + (uint32_t)b, seed_lo, seed_hi, opt.spread, qs, qg, lo, hi, L, q);
   const bool interior = lane >= 1 && lane <= n;
 
-  // ---- covariant gradient descent ------------------------------------------------------------------------------------------
+  // ---- covariant gradient descent: franka_plan_kernel's loop with the field as its environment term.  (Its own copy:
+  // one shared loop made this kernel 1.5 % slower, profiles/franka_device_timing.md) --------------------------------------------
   const float inv_eps = 1.0f / opt.epsilon;
   const float *f = test_env ? field + (size_t)b * ((size_t)G.nx * G.ny * G.nz) : nullptr;
   for (int it = 0; it < opt.iterations; ++it) {
@@ -344,7 +340,7 @@ __global__ void __launch_bounds__(64 * MAXK)
           for (int s = 0; s < S; ++s) {
             if (sl[s] != id) continue;  // (wave-uniform)
             float x, y, zz, D, nx, ny, nz;
-            plan_apply(fr, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, zz);
+            rigid_apply(fr, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, zz);
             field_sample<true>(f, G, x, y, zz, D, nx, ny, nz);
             const float d = ((D - point_radius) - sr[s]) - opt.clearance;
             if (D < G.trunc && d < opt.epsilon) {  // (D >= trunc: saturated, or outside the grid)

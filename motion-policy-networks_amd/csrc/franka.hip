@@ -13,6 +13,7 @@
 // lanes at once (one instruction stream), parks the 15 frames of each in LDS and then all 256
 // threads stream table points through them.
 #include "common.h"
+#include "franka_device.h"
 #include "sdf_device.h"
 #include "philox.h"
 #include "select_device.h"
@@ -224,10 +225,7 @@ __global__ void __launch_bounds__(BLOCK)
     for (int j = 0; j < 7; ++j) qq[j] = q[((size_t)b * T + t0 + threadIdx.x) * 7 + j];
     franka_fk_frames(qq, finger, frames + threadIdx.x * FRAME_FLOATS);
   }
-  // live primitives, COMPACTED into LDS rows [R (3 x 4 floats: rotation row | Rt) | half sizes]: lane m of the staging
-  // wave tests primitive m, a live one takes the slot = number of live ones before it.  The evaluation loops below read
-  // a row with four broadcast ds_read_b128 (every lane the same address) -- a masked primitive costs nothing at all.
-  // Staging runs on the LAST waves of the workgroup (the first one is busy with FK).
+  // live primitives, compacted as franka_live_rows.inc does, in this kernel's own form: HALF sizes, float4 rows (read by four broadcast ds_read_b128), staged by the LAST waves (the first is busy with FK)
   const float *cf = cub_f + (size_t)b * M1 * 16;
   const float *cd = cub_d + (size_t)b * M1 * 3;
   const float *yf = cyl_f + (size_t)b * M2 * 16;
@@ -541,8 +539,8 @@ MPX_EXPORT int mpx_franka_success(const float *q, const float *target_poses, int
 // joint-limit test (metrics.py:311-322, published limits), self-collision test.  Per trajectory:
 // final position error [cm] and orientation error [deg] vs the target (metrics.py:338-361), end-effector
 // path lengths (metrics.py:410-434), flags.  Self collision uses the in-repo Geometric-Fabrics model
-// (config/franka_fabric_config.yaml:120-140: body cylinder (0,0,-0.3)-(0,0,0.333) r 0.15 vs spheres on
-// link7 (r 0.1), hand and finger tips (r 0.01)); the reference Evaluator asks PyBullet meshes instead.
+// (franka_device.h: the body cylinder vs spheres on link7, hand and finger tips); the reference Evaluator asks
+// PyBullet meshes instead.
 // `lengths` (optional) = number of valid waypoints per trajectory (>= 1); later rows are ignored.
 // Angle of E = A B^T (row-major 3x3 each) in degrees: sine from the antisymmetric part of E, cosine from its trace,
 // angle = atan2(sine, cosine) -- the form of ik_rotvec (ik.hip).  Well conditioned at every angle; acos of the trace alone
@@ -590,16 +588,10 @@ __global__ void __launch_bounds__(64)
       franka_fk_frames(q, finger, fr);
 #pragma unroll
       for (int k = 0; k < 12; ++k) eff[lane * 12 + k] = fr[12 * 14 + k];
-      // self collision: distance of the sphere centres to the base segment (0,0,-0.3)-(0,0,0.333)
-      const int links[4] = {7, 9, 12, 13};
-      const float radii[4] = {0.1f, 0.01f, 0.01f, 0.01f};
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const float *c = fr + 12 * links[s] + 9;
-        const float zc = fminf(fmaxf(c[2], -0.3f), 0.333f);
-        const float dz = c[2] - zc;
-        const float d = sqrtf(mpx_fma(dz, dz, mpx_fma(c[1], c[1], c[0] * c[0])));
-        bad_self |= d < 0.15f + radii[s];
+      for (int s = 0; s < FRANKA_SELF_SPHERES; ++s) {
+        const float *c = fr + 12 * FRANKA_SELF_FRAME[s] + 9;
+        bad_self |= franka_self_hit(c[0], c[1], c[2], FRANKA_SELF_RADIUS[s]);
       }
     }
     __syncthreads();

@@ -15,8 +15,8 @@
 // A lane is ACCEPTED when one more FK of its final q -- the code mpx_franka_fk runs -- is within pos_tol / rot_tol of the
 // target.  Accepted lanes are then visited in lane order and the WAVE tests one candidate together: lane = collision
 // sphere against the problem's live primitives (compacted into LDS once, sdf_device.h forms, `sdf <= radius + clearance`
-// is a hit: with clearance 0 exactly mpx_franka_collision's test), then the body-cylinder self test of
-// trajectory_metrics_kernel (franka.hip).  The first candidate without a hit is the result: "the lowest seed that
+// is a hit: with clearance 0 exactly mpx_franka_collision's test), then the self model of franka_device.h, the one
+// mpx_trajectory_metrics applies.  The first candidate without a hit is the result: "the lowest seed that
 // converges and is free".
 //
 // Against a point cloud (mpx_franka_ik_cloud, at the end of this file): the same kernel without primitives, every start's
@@ -25,6 +25,7 @@
 // whose bits equal 1.
 #include "common.h"
 #include "franka_host.h"
+#include "franka_device.h"
 #include "sdf_device.h"
 #include "philox.h"
 
@@ -187,37 +188,10 @@ __global__ void __launch_bounds__(64)
     conv = perr <= opt.pos_tol * MPX_IK_ACCEPT_SHARE && theta <= opt.rot_tol * MPX_IK_ACCEPT_SHARE - MPX_IK_ACCEPT_ANGLE_MARGIN;
   }
 
-  // ---- live primitives, compacted into LDS rows [R | Rt (3 x 4 floats) | sizes] ---------------------------------------------
-  const float *cf = cub_f + (size_t)b * M1 * 16;
-  const float *cd = cub_d + (size_t)b * M1 * 3;
-  const float *yf = cyl_f + (size_t)b * M2 * 16;
-  const float *yr = cyl_r + (size_t)b * M2;
-  const float *yh = cyl_h + (size_t)b * M2;
-  bool clive = false, ylive = false;
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, r0 = 0.0f, h0 = 0.0f;
-  if (lane < M1) {
-    c0 = cd[3 * lane + 0], c1 = cd[3 * lane + 1], c2 = cd[3 * lane + 2];
-    clive = !(mpx_is_zero(c0) || mpx_is_zero(c1) || mpx_is_zero(c2));
-  }
-  if (lane < M2) {
-    r0 = yr[lane], h0 = yh[lane];
-    ylive = !(mpx_is_zero(r0) || mpx_is_zero(h0));
-  }
-  const unsigned long long cmask = __builtin_amdgcn_ballot_w64(clive), ymask = __builtin_amdgcn_ballot_w64(ylive);
-  const int n_cub = __builtin_popcountll(cmask), n_cyl = __builtin_popcountll(ymask);
-  const unsigned long long below = ((unsigned long long)1 << lane) - 1;
-  if (clive) {
-    float *dst = prim_rows + 16 * __builtin_popcountll(cmask & below);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) dst[k] = cf[16 * lane + k];
-    dst[12] = c0, dst[13] = c1, dst[14] = c2;
-  }
-  if (ylive) {
-    float *dst = prim_rows + 16 * (64 + __builtin_popcountll(ymask & below));
-#pragma unroll
-    for (int k = 0; k < 12; ++k) dst[k] = yf[16 * lane + k];
-    dst[12] = r0, dst[13] = h0;
-  }
+  // ---- the problem's live primitives, compacted into LDS (every lane of the one wave stores) -------------------------------
+#define FRANKA_LIVE_ROWS_STORE true
+#include "franka_live_rows.inc"
+#undef FRANKA_LIVE_ROWS_STORE
   __syncthreads();
 
   // ---- candidates in lane order: the wave tests one at a time, lane = collision sphere ----------------------------------------
@@ -251,14 +225,18 @@ __global__ void __launch_bounds__(64)
         hit = best <= sr[lane] + opt.clearance;
       }
       bool self = false;
-      if (test_self && lane < 4) {  // trajectory_metrics_kernel's model: link7 / hand / fingertips against the base segment
-        const int link = lane == 0 ? 7 : lane == 1 ? 9 : lane == 2 ? 12 : 13;
-        const float radius = lane == 0 ? 0.1f : 0.01f;
+      if (test_self && lane < FRANKA_SELF_SPHERES) {  // lane = sphere of the self model
+        static_assert(FRANKA_SELF_SPHERES == 4, "the two selects below");
+        const int link = lane == 0   ? FRANKA_SELF_FRAME[0]
+                         : lane == 1 ? FRANKA_SELF_FRAME[1]
+                         : lane == 2 ? FRANKA_SELF_FRAME[2]
+                                     : FRANKA_SELF_FRAME[3];
+        const float radius = lane == 0   ? FRANKA_SELF_RADIUS[0]
+                             : lane == 1 ? FRANKA_SELF_RADIUS[1]
+                             : lane == 2 ? FRANKA_SELF_RADIUS[2]
+                                         : FRANKA_SELF_RADIUS[3];
         const float *p = frames + 12 * link + 9;
-        const float zc = fminf(fmaxf(p[2], -0.3f), 0.333f);
-        const float dz = p[2] - zc;
-        const float d = sqrtf(mpx_fma(dz, dz, mpx_fma(p[1], p[1], p[0] * p[0])));
-        self = d < 0.15f + radius;
+        self = franka_self_hit(p[0], p[1], p[2], radius);
       }
       const bool any_env = __any(hit), any_self = __any(self);
       if (lane == c) my_env = any_env, my_self = any_self;

@@ -8,6 +8,7 @@
 // All three reduce per environment inside one workgroup in a fixed order (no atomics: results
 // are run-to-run identical); the mean over the batch is left to the caller ([B] partial sums).
 #include "sdf_grad_device.h"
+#include "franka_device.h"
 
 
 

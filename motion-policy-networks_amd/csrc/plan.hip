@@ -8,13 +8,13 @@
 // One workgroup per problem, one wave per candidate, lane = waypoint (T <= 64).  FK, the sphere loop and the gradient of
 // a waypoint stay in the lane's registers: franka_fk_visit hands over each frame as it exists, the lane then walks the
 // sphere table (wave-uniform: scalar loads) for the spheres of that link, tests them against the problem's live primitives
-// (compacted into LDS once per workgroup, as ik.hip does) and adds c'(d) n . (z_j x (x - o_j)) for the joints upstream.
+// (compacted into LDS once per workgroup: franka_live_rows.inc) and adds c'(d) n . (z_j x (x - o_j)) for the joints upstream.
 // g goes to LDS once per iteration for the M g product (n x 7 FMAs per lane, M in LDS, broadcast reads of g).
 // The validity sweep reuses the mapping with lane = refined configuration, in passes of 64.
 #include "common.h"
 #include "franka_host.h"
 #include "sdf_grad_device.h"
-#include "plan_device.h"  // what the planner shares with cloud_field.hip: candidates, M g, the jerk and self tests
+#include "plan_device.h"  // what the planner shares with cloud_field.hip: endpoints, candidates, M g, the jerk test
 
 // min over the live primitives (LDS rows [R | Rt (3 x 4 floats) | sizes]; cuboids from row 0, cylinders from row 64) and
 // the row that attains it: the first minimum, cuboids before cylinders (-1: no live primitive)
@@ -48,14 +48,14 @@ __device__ __forceinline__ int plan_config_bits(const float *q, float finger, co
       for (int s = 0; s < S; ++s) {
         if (sl[s] != id) continue;  // (wave-uniform)
         float x, y, z;
-        plan_apply(g, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, z);
+        rigid_apply(g, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, z);
         int arg;
         const float best = plan_min_sdf(prim_rows, n_cub, n_cyl, x, y, z, arg);
         if (best <= sr[s] + reach) bits |= PLAN_BIT_ENV;
       }
     }
-    if constexpr (id == 7 || id == 9 || id == 12 || id == 13) {  // trajectory_metrics_kernel's self model
-      if (test_self && plan_self_hit<id>(g, self_margin)) bits |= PLAN_BIT_SELF;
+    if constexpr (franka_self_sphere(id) >= 0) {
+      if (test_self && franka_self_hit<id>(g, self_margin)) bits |= PLAN_BIT_SELF;
     }
   });
   return bits;
@@ -87,45 +87,12 @@ __global__ void __launch_bounds__(64 * MAXK)
   const int t = lane < T ? lane : T - 1;  // (lanes past the trajectory repeat the goal and never store)
 
   float lo[7], hi[7], qs[7], qg[7];
-  bool bad_end = false;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
-    qs[j] = q_start[(size_t)b * 7 + j], qg[j] = q_goal[(size_t)b * 7 + j];
-    bad_end |= !(qs[j] >= lo[j] && qs[j] <= hi[j]) || !(qg[j] >= lo[j] && qg[j] <= hi[j]);  // (NaN fails both)
-  }
+  bool bad_end = plan_endpoints(limits, q_start, q_goal, b, lo, hi, qs, qg);
 
-  // ---- live primitives, compacted into LDS rows [R | Rt (3 x 4 floats) | sizes] (wave 0) ------------------------------------
-  const float *cf = cub_f + (size_t)b * M1 * 16;
-  const float *cd = cub_d + (size_t)b * M1 * 3;
-  const float *yf = cyl_f + (size_t)b * M2 * 16;
-  const float *yr = cyl_r + (size_t)b * M2;
-  const float *yh = cyl_h + (size_t)b * M2;
-  bool clive = false, ylive = false;
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, r0 = 0.0f, h0 = 0.0f;
-  if (lane < M1) {
-    c0 = cd[3 * lane + 0], c1 = cd[3 * lane + 1], c2 = cd[3 * lane + 2];
-    clive = !(mpx_is_zero(c0) || mpx_is_zero(c1) || mpx_is_zero(c2));
-  }
-  if (lane < M2) {
-    r0 = yr[lane], h0 = yh[lane];
-    ylive = !(mpx_is_zero(r0) || mpx_is_zero(h0));
-  }
-  const unsigned long long cmask = __builtin_amdgcn_ballot_w64(clive), ymask = __builtin_amdgcn_ballot_w64(ylive);
-  const int n_cub = __builtin_popcountll(cmask), n_cyl = __builtin_popcountll(ymask);  // (every wave: the same counts)
-  const unsigned long long below = ((unsigned long long)1 << lane) - 1;
-  if (k == 0 && clive) {
-    float *dst = prim_rows + 16 * __builtin_popcountll(cmask & below);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) dst[i] = cf[16 * lane + i];
-    dst[12] = c0, dst[13] = c1, dst[14] = c2;
-  }
-  if (k == 0 && ylive) {
-    float *dst = prim_rows + 16 * (64 + __builtin_popcountll(ymask & below));
-#pragma unroll
-    for (int i = 0; i < 12; ++i) dst[i] = yf[16 * lane + i];
-    dst[12] = r0, dst[13] = h0;
-  }
+  // ---- the problem's live primitives, compacted into LDS: wave 0 stores, every wave gets the counts ---------------------------
+#define FRANKA_LIVE_ROWS_STORE (k == 0)
+#include "franka_live_rows.inc"
+#undef FRANKA_LIVE_ROWS_STORE
   plan_fill_metric(Mtab, T, n);
   __syncthreads();
 
@@ -177,7 +144,7 @@ __global__ void __launch_bounds__(64 * MAXK)
           for (int s = 0; s < S; ++s) {
             if (sl[s] != id) continue;  // (wave-uniform)
             float x, y, zz;
-            plan_apply(fr, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, zz);
+            rigid_apply(fr, sc[3 * s + 0], sc[3 * s + 1], sc[3 * s + 2], x, y, zz);
             int arg;
             const float best = plan_min_sdf(prim_rows, n_cub, n_cyl, x, y, zz, arg);
             const float d = (best - sr[s]) - opt.clearance;

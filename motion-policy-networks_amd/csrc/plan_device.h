@@ -2,28 +2,25 @@
 // shared by plan.hip (cuboids and cylinders) and cloud_field.hip (a distance field of a point cloud).  Every function
 // states one clause of mpx_franka_plan's contract (include/mpinets_hip.h) and is inlined into its caller.
 #pragma once
-#include "common.h"
+#include "franka_device.h"
 #include "philox.h"
 
 enum { STREAM_PLAN = 14 };
 enum { PLAN_BIT_ENV = 1, PLAN_BIT_SELF = 2, PLAN_BIT_JERK = 4 };
 
-// the centre of a table sphere on a frame held in registers: rigid_apply's operations in rigid_apply's order
-__device__ __forceinline__ void plan_apply(const Rigid &g, float x, float y, float z, float &ox, float &oy, float &oz) {
-  ox = mpx_fma(g.r[2], z, mpx_fma(g.r[1], y, g.r[0] * x)) + g.t[0];
-  oy = mpx_fma(g.r[5], z, mpx_fma(g.r[4], y, g.r[3] * x)) + g.t[1];
-  oz = mpx_fma(g.r[8], z, mpx_fma(g.r[7], y, g.r[6] * x)) + g.t[2];
-}
-
-// trajectory_metrics_kernel's self model on frame `id` (7: link7, 9: hand, 12 / 13: the fingertips)
-template <int id>
-__device__ __forceinline__ bool plan_self_hit(const Rigid &g, float self_margin) {
-  static_assert(id == 7 || id == 9 || id == 12 || id == 13, "the self model's frames");
-  const float radius = id == 7 ? 0.1f : 0.01f;
-  const float zc = fminf(fmaxf(g.t[2], -0.3f), 0.333f);
-  const float dz = g.t[2] - zc;
-  const float d = sqrtf(mpx_fma(dz, dz, mpx_fma(g.t[1], g.t[1], g.t[0] * g.t[0])));
-  return d < 0.15f + radius + self_margin;
+// joint limits and the endpoints of problem b -> an endpoint lies outside the limits (NaN fails both comparisons).
+// (& and | on purpose: all four operands are loaded either way, and with && / || here franka_plan_cloud_kernel spills
+// 8 SGPRs that it does not spill otherwise -- profiles/franka_device_isa.md)
+__device__ __forceinline__ bool plan_endpoints(const float *limits, const float *q_start, const float *q_goal, int b,
+                                               float (&lo)[7], float (&hi)[7], float (&qs)[7], float (&qg)[7]) {
+  bool bad_end = false;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
+    qs[j] = q_start[(size_t)b * 7 + j], qg[j] = q_goal[(size_t)b * 7 + j];
+    bad_end |= !((qs[j] >= lo[j]) & (qs[j] <= hi[j])) | !((qg[j] >= lo[j]) & (qg[j] <= hi[j]));
+  }
+  return bad_end;
 }
 
 // M[t,u] = min(t,u) (n + 1 - max(t,u)) / (n + 1): an exact integer product, one division

@@ -5,7 +5,9 @@ franka_fabric_config.yaml:117-140 by tests/golden/gen_franka_golden.py.  Joint l
 mesh-sampled point tables live in the un-vendored robofin (parity unpinned, DESIGN.md section 2);
 tools/dump_robofin_tables.py produces them for users who have it.
 """
+import ast
 import os
+import re
 
 import numpy as np
 import pytest
@@ -65,11 +67,26 @@ def test_fabric_self_collision_model(gold):
     ref = dict(zip((str(n) for n in gold["self_sphere_name"]), gold["self_sphere_radius"].tolist()))
     for name, radius in ft.FABRIC_SELF_SPHERES:
         assert ref[name] == radius and name in ft.LINK_ID
-    # the kernel's literals are these numbers (csrc/franka.hip trajectory_metrics_kernel)
-    src = open(os.path.join(ROOT, "motion-policy-networks_amd", "csrc", "franka.hip")).read()
-    for lit in ("-0.3f", "0.333f", "0.15f", "{0.1f, 0.01f, 0.01f, 0.01f}", "{7, 9, 12, 13}"):
-        assert lit in src, lit
-    assert [ft.LINK_ID[n] for n, _ in ft.FABRIC_SELF_SPHERES] == [7, 9, 12, 13]
+    # the kernels' one statement of the model (csrc/franka_device.h) holds these numbers ...
+    csrc = os.path.join(ROOT, "motion-policy-networks_amd", "csrc")
+    src = open(os.path.join(csrc, "franka_device.h")).read()
+
+    def constant(name):
+        (text,) = re.findall(r"^constexpr (?:float|int) %s(?:\[\w+\])? = (.+?);" % name, src, re.M)
+        return ast.literal_eval(re.sub(r"(?<=\d)f\b", "", text).replace("{", "[").replace("}", "]"))
+
+    z0, z1 = constant("FRANKA_SELF_SEGMENT_Z0"), constant("FRANKA_SELF_SEGMENT_Z1")
+    assert (0.0, 0.0, z1) == ft.FABRIC_BODY_CYLINDER["pt1"] and (0.0, 0.0, z0) == ft.FABRIC_BODY_CYLINDER["pt2"]
+    assert constant("FRANKA_SELF_BODY_RADIUS") == ft.FABRIC_BODY_CYLINDER["radius"]
+    assert constant("FRANKA_SELF_SPHERES") == len(ft.FABRIC_SELF_SPHERES)
+    assert constant("FRANKA_SELF_FRAME") == [ft.LINK_ID[n] for n, _ in ft.FABRIC_SELF_SPHERES] == [7, 9, 12, 13]
+    assert constant("FRANKA_SELF_RADIUS") == [r for _, r in ft.FABRIC_SELF_SPHERES]
+    # ... and nothing else under csrc/ writes the comparison's literal
+    others = [f for f in sorted(os.listdir(csrc)) if f != "franka_device.h" and os.path.isfile(os.path.join(csrc, f))
+              and not f.endswith((".o", ".so"))]
+    assert len(others) > 20 and src.count("0.15f") == 1
+    for f in others:
+        assert "0.15f" not in open(os.path.join(csrc, f), errors="replace").read(), f
 
 
 def test_dumped_point_tables_round_trip(tmp_path):

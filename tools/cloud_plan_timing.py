@@ -19,7 +19,7 @@ Once: ``CloudField.sample`` of 2^20 points (one environment), with and without t
 HIP events around each call, 3 untimed calls, then the median of 10 with the spread (min .. max), as tools/plan_timing.py.
 The timed calls are the Python entry points as a user makes them (wrapper host work included).
 
-    python tools/cloud_plan_timing.py [--envs 1 64 1024]
+    python tools/cloud_plan_timing.py [--envs 1 64 1024] [--candidates K]
 """
 import argparse
 import json
@@ -40,6 +40,7 @@ MIXED = ("tabletop", "cubby", "dresser")
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, nargs="+", default=[1, 64, 1024])
+    ap.add_argument("--candidates", type=int, default=None, help="16: the <16> kernel instantiations")
     args = ap.parse_args()
     from mpinets_amd import robot, scenes
     from mpinets_amd.field import CloudField
@@ -48,7 +49,8 @@ def main():
 
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    res = {"options": dict(robot.PLAN_DEFAULTS), "T": 50, "cases": {}}
+    kw = {} if args.candidates is None else {"candidates": args.candidates}
+    res = {"options": dict(robot.PLAN_DEFAULTS, **kw), "T": 50, "cases": {}}
     sampler = FrankaCollisionSampler(dev)
     for B in args.envs:
         prob = scenes.make_problem_batch(B, seed=0, kinds=MIXED, M1=40, M2=16, scene_pool=min(B, 256), device_clouds=True,
@@ -69,20 +71,20 @@ def main():
         field = CloudField.build(cloud, truncation=trunc)
         out["field_nodes"], out["field_truncation_m"] = list(field.shape), trunc
         pr = 0.5 * spacing
-        out["plan_cloud"] = timed(lambda: robot.franka_plan_cloud(qs, qg, cloud, field=field, point_radius=pr))
-        out["plan_cloud_with_field_build"] = timed(lambda: robot.franka_plan_cloud(qs, qg, cloud, point_radius=pr))
+        out["plan_cloud"] = timed(lambda: robot.franka_plan_cloud(qs, qg, cloud, field=field, point_radius=pr, **kw))
+        out["plan_cloud_with_field_build"] = timed(lambda: robot.franka_plan_cloud(qs, qg, cloud, point_radius=pr, **kw))
         none = cloud[:, :0]
-        out["plan_cloud_no_flag_calls"] = timed(lambda: robot.franka_plan_cloud(qs, qg, none, field=field, point_radius=pr))
-        out["plan_cloud_drawn_only"] = timed(lambda: robot.franka_plan_cloud(qs, qg, none, field=field, point_radius=pr, iterations=0))
+        out["plan_cloud_no_flag_calls"] = timed(lambda: robot.franka_plan_cloud(qs, qg, none, field=field, point_radius=pr, **kw))
+        out["plan_cloud_drawn_only"] = timed(lambda: robot.franka_plan_cloud(qs, qg, none, field=field, point_radius=pr, iterations=0, **kw))
         full, noflag, drawn = (out[k]["median_ms"] for k in ("plan_cloud", "plan_cloud_no_flag_calls", "plan_cloud_drawn_only"))
         out["split_ms"] = {"optimise": noflag - drawn, "validity": full - noflag, "draw_tests_refine_select": drawn}
-        out["plan_primitives"] = timed(lambda: robot.franka_plan(qs, qg, cub, cyl))
+        out["plan_primitives"] = timed(lambda: robot.franka_plan(qs, qg, cub, cyl, **kw))
         out["ratio_cloud_over_primitives"] = full / out["plan_primitives"]["median_ms"]
-        st_p = robot.franka_plan(qs, qg, cub, cyl)[1]
+        st_p = robot.franka_plan(qs, qg, cub, cyl, **kw)[1]
         out["share_solved_primitives"] = float((st_p[posed] == 0).float().mean()) if int(posed.sum()) else None
         for name, radius in (("point_radius_0", 0.0), ("point_radius_half_spacing", pr)):
             f = field if radius == pr else CloudField.build(cloud, truncation=robot.plan_cloud_truncation(radius))
-            traj, st = robot.franka_plan_cloud(qs, qg, cloud, field=f, point_radius=radius)
+            traj, st = robot.franka_plan_cloud(qs, qg, cloud, field=f, point_radius=radius, **kw)
             ok = (st == 0) & posed
             rows = torch.nonzero(ok)[:, 0]
             rej = None

@@ -6,7 +6,7 @@ The timed call is ``robot.franka_plan`` as a user makes it: besides the kernel i
 inward rounding of the limits and their copy to the device, the option struct, four output allocations); the kernel alone
 is the ``franka_plan_kernel`` line of ``rocprofv3 --kernel-trace --stats``.
 
-    python tools/plan_timing.py [--envs 8192] [--iterations N]
+    python tools/plan_timing.py [--envs 8192] [--iterations N] [--candidates K]
 """
 import argparse
 import json
@@ -26,13 +26,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--iterations", type=int, default=None)
+    ap.add_argument("--candidates", type=int, default=None, help="16: the <16> kernel instantiations")
     args = ap.parse_args()
     from mpinets_amd import robot, scenes
     from mpinets_amd.geometry import TorchCuboids, TorchCylinders
 
     dev = torch.device("cuda:0")
     B = args.envs
-    opts = {} if args.iterations is None else {"iterations": args.iterations}
+    opts = {k: v for k, v in (("iterations", args.iterations), ("candidates", args.candidates)) if v is not None}
     res = {"envs": B, "options": dict(robot.PLAN_DEFAULTS, **opts)}
 
     def case(kinds, M1, M2):
