@@ -29,7 +29,9 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341: the route queries mpx_fps_route, mpx_franka_collision_route, mpx_linear_route, mpx_linear_wgrad_route,
+int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_roadmap,
+                          struct mpx_roadmap_options, mpx_franka_plan_seeded;
+                          341: the route queries mpx_fps_route, mpx_franka_collision_route, mpx_linear_route, mpx_linear_wgrad_route,
                           mpx_pool_wgrad_route, mpx_sa_mlp_route (additions only);
                           340 (unchanged: additions, no caller of an earlier 340 library needs rebuilding): mpx_franka_cloud_collision_each,
                           mpx_franka_ik_cloud, mpx_franka_ik_cloud_scratch; 340 (unchanged, likewise): mpx_cloud_field_build,
@@ -318,6 +320,80 @@ int mpx_franka_plan(const float *q_start, const float *q_goal, int B, int T, flo
                     const float *cyl_radii, const float *cyl_heights, int M2, const mpx_plan_options *options,
                     uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *choice, float *all_traj,
                     int32_t *all_status, mpx_stream_t stream);
+
+/* mpx_franka_plan with caller-supplied candidates: seeds [B,Ks,T,7], Ks >= 0, candidates + Ks <= MPX_PLAN_MAX_CANDIDATES.
+ *   Candidates 0 .. K-1 (K = options->candidates) are drawn and optimised exactly as by mpx_franka_plan; candidate K + i
+ *   starts from seeds[b,i]: its interior waypoints clamped into the limits, waypoints 0 and T-1 replaced by q_start / q_goal.
+ *   L stays the straight line for every candidate (the smoothness term's q - L pulls a seed toward the line as it pulls a
+ *   drawn candidate).  A seed with an entry that is not finite is not optimised: its all_traj rows are NaN and its
+ *   all_status is 7.  Iterations, validity, the bits, "the LOWEST valid candidate" and status 2 are mpx_franka_plan's;
+ *   all_traj is [B,K+Ks,T,7], all_status [B,K+Ks], choice counts over K + Ks.  Hence: with Ks = 0 every output is bit-equal
+ *   to mpx_franka_plan's (it is that launch); with any Ks candidates 0 .. K-1 are bit-equal, and a row mpx_franka_plan
+ *   solves comes back identical.  seeds may be NULL when Ks = 0.                                                          */
+int mpx_franka_plan_seeded(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                           const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                           const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                           const float *cyl_radii, const float *cyl_heights, int M2, const mpx_plan_options *options,
+                           uint64_t seed, int64_t env_offset, const float *seeds, int Ks, float *traj, int32_t *status,
+                           int32_t *choice, float *all_traj, int32_t *all_status, mpx_stream_t stream);
+
+/* A lazy probabilistic roadmap per problem: the GLOBAL half of what the reference asks of OMPL, whose path seeds the local
+ * optimiser above (mpx_franka_plan_seeded smooths and judges it as it judges its own candidates).  One workgroup per
+ * problem; the result depends on the inputs alone (no atomics on results, no dependence on lane timing).
+ *   Nodes.  V = options->nodes, 2 <= V <= MPX_ROADMAP_MAX_NODES.  Node 0 is q_start, node 1 q_goal; node v >= 2 has
+ *   q_j = fma(u_j, hi_j - lo_j, lo_j), u_j = u01 of word j (j < 4) of Philox4x32-10(counter = {2v, GLOBAL problem id =
+ *   env_offset + b, stream 16, 0}, key = seed) or word j - 4 of the block with counter word 0 = 2v + 1: a shard of a
+ *   larger batch computes what one process computes.
+ *   A configuration is VALID by mpx_franka_plan's validity test, unchanged: no sphere with sdf <= r_s + clearance +
+ *   check_margin, and with check_self no self-test sphere inside 0.15 + radius + check_margin.
+ *   status int32 [B]: 2 an endpoint is not finite, outside the limits or invalid (mpx_franka_plan's rule; no search is
+ *   done, rounds = 0); 0 a path was found; 1 none was.  Invalid nodes other than the endpoints take no part in the search.
+ *   Edge (a,b), a < b: d = q_b - q_a, w = sqrtf(fma(d_6, d_6, ... fma(d_1, d_1, d_0 d_0))) (the same bits for (b,a));
+ *   n = min(2^20, max(1, (int)ceilf(w / resolution))) pieces; interior configuration i = 1 .. n-1 is
+ *   fma((float)i / (float)n, d, q_a).  The edge is BLOCKED exactly when an interior configuration is invalid; an edge with
+ *   w > connect_radius does not exist.
+ *   Search, at most max_rounds rounds.  A round finds the shortest path from node 0 to node 1 over the valid nodes and the
+ *   edges that are not blocked (untested edges count as free) by Jacobi sweeps to a fixed point: d_0 = 0, every other
+ *   d = +inf, no predecessors; a sweep reads the previous sweep's distances only and gives every valid node v != 0
+ *   d_v <- min(d_v, min_u (d_u + w_uv)) in float32, evaluated for u = 0 .. V-1 ascending with a strict "<" against the
+ *   running minimum that starts at the old d_v; the predecessor becomes the u that last lowered it (the lowest u among
+ *   equal sums) and is kept when none did.  The sweeps end when one changes no distance.  d_1 = +inf: status 1.  Else every
+ *   untested edge of the path 1, pred(1), .. 0 is tested in full and becomes free or blocked; if none is blocked the path is
+ *   the answer (status 0), else the next round searches again.  Rounds used up: status 1.
+ *   path int32 [B,V]: the node indices from 0 to 1, then -1; hops int32 [B]: its edges.  Rows with status != 0: hops 0,
+ *   path all -1.  Optional: nodes [B,V,7]; edge_state uint8 [B,V,V], symmetric, 0 untested / 1 free / 2 blocked, the
+ *   diagonal 1 for a valid node and 2 for an invalid one; rounds int32 [B], the searches run.
+ *   traj [B,T,7], 2 <= T <= MPX_PLAN_MAX_T, the seed trajectory.  A one-edge path gives mpx_franka_plan's line L_t bit for
+ *   bit (not resampled, not smoothed).  Otherwise, with c_0 = 0, c_{i+1} = c_i + w_i summed in path order in float32 and
+ *   s_t = ((float)t / (float)(T-1)) c_hops: waypoint t lies on the last edge i with c_i <= s_t, at
+ *   fma(f, p_{i+1} - p_i, p_i), f = min((s_t - c_i) / w_i, 1) (0 if w_i = 0), p_i the path's nodes in path order; then
+ *   smooth_passes passes of q_t <- fma(0.25, q_{t-1} + q_{t+1}, 0.5 q_t) on t = 1 .. T-2, each from the previous pass (the
+ *   corners are rounded so that the optimiser's third-difference test has a chance).  Waypoints 0 and T-1 are bit-equal to
+ *   q_start / q_goal.  Rows with status != 0 are NaN.
+ *   q_start, q_goal, limits, the sphere table and the primitives exactly as for mpx_franka_plan.  No allocation, no
+ *   scratch, no global atomics; everything is enqueued on `stream` (capturable).  B == 0 launches nothing.              */
+#define MPX_ROADMAP_MAX_NODES 256
+#define MPX_ROADMAP_DEFAULT_NODES 64
+#define MPX_ROADMAP_DEFAULT_RESOLUTION 0.05f
+#define MPX_ROADMAP_DEFAULT_MAX_ROUNDS 64
+#define MPX_ROADMAP_DEFAULT_SMOOTH_PASSES 8
+typedef struct mpx_roadmap_options { /* NULL options: the defaults above, connect_radius +inf, check_margin
+                                        MPX_PLAN_DEFAULT_CHECK_MARGIN, clearance 0, check_self 1 */
+  int nodes;                         /* 2 .. MPX_ROADMAP_MAX_NODES, start and goal included              */
+  float resolution;                  /* > 0 [rad]: the longest piece of an edge (joint-space 2-norm)     */
+  float connect_radius;              /* [rad], longer edges do not exist; +inf: the complete graph       */
+  int max_rounds;                    /* >= 1: searches before giving up                                   */
+  int smooth_passes;                 /* >= 0: (1/4, 1/2, 1/4) passes over the resampled polyline          */
+  float check_margin;                /* >= 0 [m], as in mpx_plan_options                                  */
+  float clearance;                   /* [m], added to the radii                                           */
+  int check_self;                    /* non-zero: self collisions invalidate a configuration              */
+} mpx_roadmap_options;
+int mpx_franka_roadmap(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                       const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                       const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                       const float *cyl_radii, const float *cyl_heights, int M2, const mpx_roadmap_options *options,
+                       uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *path, int32_t *hops,
+                       float *nodes, uint8_t *edge_state, int32_t *rounds, mpx_stream_t stream);
 
 /* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
  * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at

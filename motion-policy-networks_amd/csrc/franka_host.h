@@ -1,5 +1,5 @@
 // franka_host.h -- host-only (no __device__ code): the argument checks and the cloud launch table that the Franka geometry
-// entries share (ik.hip, plan.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for env_offset and scratch size); a
+// entries share (ik.hip, plan.hip, roadmap.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for env_offset and scratch size); a
 // new entry takes its checks from here.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
 // returns 0 or 1 (field_grid_check's idiom).  Sizes and values are checked before an entry's "nothing to do" return, pointers after.
 #pragma once

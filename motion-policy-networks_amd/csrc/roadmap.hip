@@ -1,0 +1,294 @@
+// roadmap.hip -- a lazy probabilistic roadmap per problem: the global half of what the reference's data generator asks of
+// OMPL (data_pipeline/gen_data.py:106-153), in front of plan.hip's local optimiser.  V configurations (start, goal, V - 2
+// Philox draws inside the limits) are judged by the planner's own validity test (plan_prims_device.h); the shortest path from
+// start to goal over the complete graph is searched with every untested edge counted as free, the untested edges of that path
+// are then tested in full, and the search repeats without the blocked ones until a path survives.  The surviving polyline,
+// resampled to T waypoints and rounded at its corners, is a candidate for mpx_franka_plan_seeded.  The contract (draws, edge
+// pieces, sweeps, resampling) is stated in include/mpinets_hip.h.
+//
+// One workgroup of 256 threads per problem, everything in LDS, no scratch memory and no global atomics.  Three mappings:
+// thread = node (the node draw, node validity, one Bellman-Ford sweep: V <= 256), thread = interior configuration across the
+// concatenated untested edges of the round's path (the planner's validity-sweep mapping, in passes of 256), thread = waypoint
+// (resampling and the corner filter: T <= 64).  The path walk and the prefix sums over its <= V - 1 edges are serial on
+// thread 0.  Every branch around a barrier is workgroup-uniform: it reads a value from LDS behind a barrier, or a barrier's
+// own reduction.
+#include "common.h"
+#include "franka_host.h"
+#include "plan_prims_device.h"
+
+enum { STREAM_ROADMAP = 16 };
+enum { ROADMAP_THREADS = 256, ROADMAP_MAX_PIECES = 1 << 20 };
+enum { ROADMAP_UNTESTED = 0, ROADMAP_FREE = 1, ROADMAP_BLOCKED = 2 };
+
+// LDS, in 4-byte words: [128 primitive rows x 16 | nodes V x 7 | dist 2 x V (later: cumulative and edge lengths) |
+// two trajectories 64 x 7 | pred, path, rev, pieces, blocked, valid: V ints each | first V + 1 | hops | edge bits]
+__host__ __device__ static inline size_t roadmap_lds_words(int V) {
+  return (size_t)128 * 16 + (size_t)V * 7 + 2 * (size_t)V + 2 * 64 * 7 + 6 * (size_t)V + (size_t)V + 1 + 1 +
+         ((size_t)V * V + 15) / 16;
+}
+
+// |q_b - q_a|: j ascending, the first square rounded on its own, the others fused.  (x - y)^2 is (y - x)^2 bit for bit, so
+// the length of an edge does not depend on the order of its ends.
+__device__ __forceinline__ float roadmap_length(const float *qa, const float *qb) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    const float d = qb[j] - qa[j];
+    acc = j == 0 ? d * d : mpx_fma(d, d, acc);
+  }
+  return sqrtf(acc);
+}
+__device__ __forceinline__ int roadmap_pieces(float w, float resolution) {
+  const float n = ceilf(w / resolution);
+  return n >= (float)ROADMAP_MAX_PIECES ? ROADMAP_MAX_PIECES : n >= 1.0f ? (int)n : 1;
+}
+
+// 2 bits per pair, at bit 2 (lo V + hi) for lo < hi
+__device__ __forceinline__ int roadmap_edge_get(const unsigned *bits, int V, int a, int b) {
+  const int idx = (a < b ? a : b) * V + (a < b ? b : a);
+  return (int)((bits[idx >> 4] >> ((idx & 15) * 2)) & 3u);
+}
+// (from ROADMAP_UNTESTED only: an OR sets the state, whichever lanes share the word)
+__device__ __forceinline__ void roadmap_edge_set(unsigned *bits, int V, int a, int b, int state) {
+  const int idx = (a < b ? a : b) * V + (a < b ? b : a);
+  atomicOr(&bits[idx >> 4], (unsigned)state << ((idx & 15) * 2));
+}
+
+__global__ void __launch_bounds__(ROADMAP_THREADS)
+    franka_roadmap_kernel(const float *__restrict__ q_start, const float *__restrict__ q_goal, int T, float finger,
+                          const float *__restrict__ limits, const float *__restrict__ sc, const float *__restrict__ sr,
+                          const int32_t *__restrict__ sl, int S, const float *__restrict__ cub_f,
+                          const float *__restrict__ cub_d, int M1, const float *__restrict__ cyl_f,
+                          const float *__restrict__ cyl_r, const float *__restrict__ cyl_h, int M2, mpx_roadmap_options opt,
+                          uint32_t seed_lo, uint32_t seed_hi, uint32_t env0, float *__restrict__ traj,
+                          int32_t *__restrict__ status, int32_t *__restrict__ path_out, int32_t *__restrict__ hops_out,
+                          float *__restrict__ nodes_out, uint8_t *__restrict__ edge_out, int32_t *__restrict__ rounds_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int V = opt.nodes;
+  float *prim_rows = lds;
+  float *nodes = prim_rows + 128 * 16;
+  float *dist = nodes + V * 7;
+  float *tbuf = dist + 2 * V;
+  int *pred = reinterpret_cast<int *>(tbuf + 2 * 64 * 7);
+  int *path = pred + V, *rev = path + V, *pieces = rev + V, *blocked = pieces + V, *valid = blocked + V;
+  int *first = valid + V;  // first[i]: index of edge i's first interior configuration among the round's tests
+  int *hops_lds = first + V + 1;
+  unsigned *ebits = reinterpret_cast<unsigned *>(hops_lds + 1);
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int k = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const float inf = __builtin_inff(), nan = __builtin_nanf("");
+
+  float lo[7], hi[7], qs[7], qg[7];
+  plan_endpoints(limits, q_start, q_goal, b, lo, hi, qs, qg);
+
+#define FRANKA_LIVE_ROWS_STORE (k == 0)
+#include "franka_live_rows.inc"
+#undef FRANKA_LIVE_ROWS_STORE
+  for (int i = tid; i < (V * V + 15) / 16; i += ROADMAP_THREADS) ebits[i] = 0u;
+
+  // ---- nodes: thread = node ------------------------------------------------------------------------------------------------------
+  float mine[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool inside = true;
+  if (tid < V) {
+    const Philox p0 = philox4x32(2u * (uint32_t)tid, env0 + (uint32_t)b, STREAM_ROADMAP, 0u, seed_lo, seed_hi);
+    const Philox p1 = philox4x32(2u * (uint32_t)tid + 1u, env0 + (uint32_t)b, STREAM_ROADMAP, 0u, seed_lo, seed_hi);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      const float drawn = mpx_fma(u01(j < 4 ? p0.c[j] : p1.c[j - 4]), hi[j] - lo[j], lo[j]);
+      mine[j] = tid == 0 ? qs[j] : tid == 1 ? qg[j] : drawn;
+      inside &= (mine[j] >= lo[j]) & (mine[j] <= hi[j]);  // (an endpoint: NaN fails)
+      nodes[tid * 7 + j] = mine[j];
+      if (nodes_out) nodes_out[((size_t)b * V + tid) * 7 + j] = mine[j];
+    }
+  }
+  __syncthreads();  // (the primitive rows, the nodes, the cleared edge bits)
+
+  const bool test_self = opt.check_self != 0;
+  const float reach = opt.clearance + opt.check_margin;
+  if (tid < V)
+    valid[tid] = inside && plan_config_bits(mine, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self,
+                                            opt.check_margin) == 0;
+  __syncthreads();
+
+  // ---- the lazy search -----------------------------------------------------------------------------------------------------------
+  int st = (valid[0] && valid[1]) ? 1 : 2, rounds = 0, hops = 0;
+  for (int round = 0; st == 1 && round < opt.max_rounds; ++round) {
+    rounds = round + 1;
+    if (tid < V) dist[tid] = tid == 0 ? 0.0f : inf, pred[tid] = -1;
+    __syncthreads();
+    int cur = 0;
+    for (int sweep = 0; sweep < V; ++sweep) {  // (Jacobi: a sweep reads dist[cur], writes the other half; V - 1 suffice)
+      const float *dp = dist + cur * V;
+      int changed = 0;
+      if (tid < V) {
+        float best = dp[tid];
+        int bp = pred[tid];
+        if (tid != 0 && valid[tid]) {
+          for (int u = 0; u < V; ++u) {
+            const float du = dp[u];
+            if (u == tid || !(du < inf) || roadmap_edge_get(ebits, V, u, tid) == ROADMAP_BLOCKED) continue;
+            const float w = roadmap_length(nodes + u * 7, mine);
+            if (w > opt.connect_radius) continue;
+            const float cand = du + w;
+            if (cand < best) best = cand, bp = u;
+          }
+        }
+        changed = best < dp[tid];
+        dist[(cur ^ 1) * V + tid] = best, pred[tid] = bp;
+      }
+      cur ^= 1;
+      if (!__syncthreads_or(changed)) break;
+    }
+    if (!(dist[cur * V + 1] < inf)) break;  // the goal cannot be reached over what is not blocked
+
+    // the path, and where each of its untested edges starts among this round's tests
+    if (tid == 0) {
+      int n = 0, v = 1;
+      for (; v > 0 && n < V; v = pred[v]) rev[n++] = v;
+      if (v != 0) n = 0;  // (a finite distance has a chain of predecessors down to node 0: never taken)
+      path[0] = 0;
+      first[0] = 0;
+      for (int i = 0; i < n; ++i) {
+        path[i + 1] = rev[n - 1 - i];
+        const int a = path[i] < path[i + 1] ? path[i] : path[i + 1], c = path[i] < path[i + 1] ? path[i + 1] : path[i];
+        pieces[i] = roadmap_pieces(roadmap_length(nodes + a * 7, nodes + c * 7), opt.resolution);
+        first[i + 1] = first[i] + (roadmap_edge_get(ebits, V, a, c) == ROADMAP_UNTESTED ? pieces[i] - 1 : 0);
+        blocked[i] = 0;
+      }
+      *hops_lds = n;
+    }
+    __syncthreads();
+    hops = *hops_lds;
+    if (hops == 0) break;
+    const int total = first[hops];
+    for (int c = tid; c < total; c += ROADMAP_THREADS) {  // thread = interior configuration
+      int i = 0, top = hops;                              // the last edge with first[i] <= c
+      while (top - i > 1) {
+        const int mid = (i + top) >> 1;
+        if (first[mid] <= c) i = mid; else top = mid;
+      }
+      const int a = path[i] < path[i + 1] ? path[i] : path[i + 1], e = path[i] < path[i + 1] ? path[i + 1] : path[i];
+      const float f = (float)(c - first[i] + 1) / (float)pieces[i];
+      float q[7];
+#pragma unroll
+      for (int j = 0; j < 7; ++j) q[j] = mpx_fma(f, nodes[e * 7 + j] - nodes[a * 7 + j], nodes[a * 7 + j]);
+      if (plan_config_bits(q, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin))
+        blocked[i] = 1;  // (every lane that stores, stores 1)
+    }
+    __syncthreads();
+    int hit = 0;
+    if (tid < hops && roadmap_edge_get(ebits, V, path[tid], path[tid + 1]) == ROADMAP_UNTESTED) {
+      hit = blocked[tid];
+      roadmap_edge_set(ebits, V, path[tid], path[tid + 1], hit ? ROADMAP_BLOCKED : ROADMAP_FREE);
+    }
+    if (!__syncthreads_or(hit)) st = 0;
+  }
+  if (st != 0) hops = 0;
+
+  // ---- what the search found -----------------------------------------------------------------------------------------------------
+  if (tid == 0) {
+    status[b] = st, hops_out[b] = hops;
+    if (rounds_out) rounds_out[b] = rounds;
+  }
+  if (tid < V) path_out[(size_t)b * V + tid] = (st == 0 && tid <= hops) ? path[tid] : -1;
+  if (edge_out)
+    for (int i = tid; i < V * V; i += ROADMAP_THREADS) {
+      const int a = i / V, c = i - a * V;
+      edge_out[(size_t)b * V * V + i] =
+          (uint8_t)(a == c ? (valid[a] ? ROADMAP_FREE : ROADMAP_BLOCKED) : roadmap_edge_get(ebits, V, a, c));
+    }
+
+  // ---- the seed trajectory: thread = waypoint ------------------------------------------------------------------------------------
+  float *out = traj + (size_t)b * T * 7;
+  if (st != 0) {
+    for (int i = tid; i < T * 7; i += ROADMAP_THREADS) out[i] = nan;
+    return;
+  }
+  const bool end = tid == 0 || tid == T - 1;
+  if (hops == 1) {  // the planner's line itself
+    if (tid < T) {
+      const float s = (float)tid / (float)(T - 1);
+#pragma unroll
+      for (int j = 0; j < 7; ++j)
+        out[tid * 7 + j] = tid == 0 ? qs[j] : tid == T - 1 ? qg[j] : mpx_fma(s, qg[j] - qs[j], qs[j]);
+    }
+    return;
+  }
+  float *cum = dist, *len = dist + V;  // (the search is over: cum[i] = arc length at path node i, len[i] = |edge i|)
+  __syncthreads();
+  if (tid == 0) {
+    cum[0] = 0.0f;
+    for (int i = 0; i < hops; ++i) {
+      len[i] = roadmap_length(nodes + path[i] * 7, nodes + path[i + 1] * 7);
+      cum[i + 1] = cum[i] + len[i];
+    }
+  }
+  __syncthreads();
+  if (tid < T) {
+    const float s = ((float)tid / (float)(T - 1)) * cum[hops];
+    int i = 0;
+    for (int e = 1; e < hops; ++e)
+      if (cum[e] <= s) i = e;
+    const float f = len[i] > 0.0f ? fminf((s - cum[i]) / len[i], 1.0f) : 0.0f;
+    const float *pa = nodes + path[i] * 7, *pb = nodes + path[i + 1] * 7;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) tbuf[tid * 7 + j] = tid == 0 ? qs[j] : tid == T - 1 ? qg[j] : mpx_fma(f, pb[j] - pa[j], pa[j]);
+  }
+  __syncthreads();
+  float *src = tbuf, *dst = tbuf + 64 * 7;
+  for (int pass = 0; pass < opt.smooth_passes; ++pass) {  // (1/4, 1/2, 1/4) on the interior, each pass from the previous one
+    if (tid < T) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j)
+        dst[tid * 7 + j] = end ? src[tid * 7 + j]
+                               : mpx_fma(0.25f, src[(tid - 1) * 7 + j] + src[(tid + 1) * 7 + j], 0.5f * src[tid * 7 + j]);
+    }
+    __syncthreads();
+    float *swap = src;
+    src = dst, dst = swap;
+  }
+  if (tid < T) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j) out[tid * 7 + j] = src[tid * 7 + j];
+  }
+}
+
+static inline mpx_roadmap_options franka_roadmap_defaults() {
+  return {MPX_ROADMAP_DEFAULT_NODES, MPX_ROADMAP_DEFAULT_RESOLUTION, __builtin_inff(), MPX_ROADMAP_DEFAULT_MAX_ROUNDS,
+          MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
+}
+
+MPX_EXPORT int mpx_franka_roadmap(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                                  const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                                  const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                                  const float *cyl_radii, const float *cyl_heights, int M2, const mpx_roadmap_options *options,
+                                  uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *path,
+                                  int32_t *hops, float *nodes, uint8_t *edge_state, int32_t *rounds, mpx_stream_t stream) {
+  const char *who = "mpx_franka_roadmap";
+  const mpx_roadmap_options opt = options ? *options : franka_roadmap_defaults();
+  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "%s: negative size", who);
+  MPX_REQUIRE(franka_plan_T_ok(T), "%s: T = %d waypoints, need 2 .. %d (one lane each)", who, T, MPX_PLAN_MAX_T);
+  MPX_REQUIRE(opt.nodes >= 2 && opt.nodes <= MPX_ROADMAP_MAX_NODES, "%s: nodes = %d, need 2 .. %d (one thread each)", who,
+              opt.nodes, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
+  MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
+  MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
+  MPX_REQUIRE(opt.smooth_passes >= 0, "%s: smooth_passes = %d, need >= 0", who, opt.smooth_passes);
+  MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
+  if (franka_counts_check(who, S, M1, M2) || franka_env_offset_check(who, env_offset, B)) return 1;
+  if (B == 0) return 0;
+  MPX_REQUIRE(traj && status && path && hops, "%s: NULL output (traj, status, path, hops)", who);
+  MPX_REQUIRE(q_start && q_goal && limits, "%s: NULL operand (q_start, q_goal, limits)", who);
+  if (franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link) ||
+      franka_primitive_arrays_check(who, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii, cyl_heights, M2))
+    return 1;
+  const size_t lds = 4 * roadmap_lds_words(opt.nodes);  // 44 552 B at 256 nodes
+  hipLaunchKernelGGL(franka_roadmap_kernel, dim3((unsigned)B), dim3(ROADMAP_THREADS), lds, mpx_s(stream), q_start, q_goal, T,
+                     finger, limits, sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames,
+                     cyl_radii, cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, traj,
+                     status, path, hops, nodes, edge_state, rounds);
+  MPX_LAUNCH_CHECK(who);
+}

@@ -41,6 +41,8 @@ PROTOTYPES = {
     "mpx_franka_ik_cloud_scratch": [I],
     "mpx_franka_ik_cloud": [P, I, F, P, P, P, P, P, I, P, L, I, I, P, F, P, ctypes.c_uint64, L, P, P, P, P, P, L, P],
     "mpx_franka_plan": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P],
+    "mpx_franka_plan_seeded": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, I, P, P, P, P, P, P],
+    "mpx_franka_roadmap": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
     "mpx_franka_plan_cloud_scratch": [I, I, I, I],
@@ -143,6 +145,12 @@ class PlanOptions(ctypes.Structure):
     _fields_ = [("candidates", c_int), ("iterations", c_int), ("step", c_float), ("smooth_weight", c_float),
                 ("epsilon", c_float), ("spread", c_float), ("substeps", c_int), ("check_margin", c_float),
                 ("clearance", c_float), ("max_jerk", c_float), ("check_self", c_int)]
+
+
+class RoadmapOptions(ctypes.Structure):
+    """``mpx_roadmap_options`` (include/mpinets_hip.h); the defaults are the header's MPX_ROADMAP_DEFAULT_*."""
+    _fields_ = [("nodes", c_int), ("resolution", c_float), ("connect_radius", c_float), ("max_rounds", c_int),
+                ("smooth_passes", c_int), ("check_margin", c_float), ("clearance", c_float), ("check_self", c_int)]
 
 
 class FieldGrid(ctypes.Structure):

@@ -265,7 +265,7 @@ def _plan_outputs(B: int, K: int, T: int, dev: torch.device, return_all: bool): 
 
 def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
                 env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
-                finger: float = ft.FINGER_OPENING, **options):
+                finger: float = ft.FINGER_OPENING, seeds: Optional[torch.Tensor] = None, **options):
     """Batched collision-free trajectories from ``q_start`` to ``q_goal`` on the GPU (csrc/plan.hip): covariant gradient
     descent on ``T`` waypoints from ``candidates`` starting trajectories per problem (the straight line, and the line bent
     by Philox draws keyed by (``seed``, ``env_offset`` + row, candidate)), then a validity sweep of every candidate; the
@@ -275,6 +275,10 @@ def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylin
     :param q_start, q_goal: [B,7], inside ``limits`` and collision free (e.g. from ``franka_ik``)
     :param cuboids, cylinders: ``geometry.TorchCuboids`` / ``TorchCylinders`` (batch B) or None, as for ``franka_ik``
     :param limits: [7,2]; cast to float32 toward the inside of the interval, as ``franka_ik`` does
+    :param seeds: None (``mpx_franka_plan``), or [B,Ks,T,7] caller-supplied starting trajectories (``mpx_franka_plan_seeded``,
+        e.g. ``franka_roadmap``'s): candidates ``candidates`` .. ``candidates`` + Ks - 1, behind the drawn ones, which stay
+        bit-equal; interior waypoints are clamped into ``limits``, the endpoints replaced, a seed with a non-finite entry
+        is not optimised (NaN rows, bits 7); ``candidates`` + Ks <= 16.  ``all_traj`` / ``all_status`` then have K + Ks rows.
     :param options: the fields of ``mpx_plan_options``, see ``PLAN_DEFAULTS``
     :returns: ``traj`` [B,T,7] (NaN rows where ``status`` != 0; waypoints 0 and T-1 are bit-equal to the inputs) and
         ``status`` int32 [B]: 0 solved, 1 no valid candidate, 2 an endpoint is non-finite, outside the limits or in
@@ -291,12 +295,99 @@ def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylin
     cf, cd, M1, yf, yr, yh, M2 = _primitive_operands(cuboids, cylinders, B)
     sc, sr, sl = _ik_sphere_table(dev, with_base_link) if M1 + M2 > 0 else (None, None, None)
     S = 0 if sc is None else int(sc.size(0))
-    traj, status, choice, all_traj, all_status = _plan_outputs(B, max(int(o["candidates"]), 0), T, dev, return_all)
-    _lib.call("mpx_franka_plan", _lib.ptr(qs), _lib.ptr(qg), B, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
+    if seeds is None:
+        traj, status, choice, all_traj, all_status = _plan_outputs(B, max(int(o["candidates"]), 0), T, dev, return_all)
+        _lib.call("mpx_franka_plan", _lib.ptr(qs), _lib.ptr(qg), B, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
+                  _lib.ptr(sr), _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
+                  ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(traj), _lib.ptr(status),
+                  _lib.ptr(choice), _lib.ptr(all_traj), _lib.ptr(all_status))
+        return (traj, status, choice, all_traj, all_status) if return_all else (traj, status)
+    _lib.require_cuda(seeds)
+    assert seeds.ndim == 4 and seeds.size(0) == B and tuple(seeds.shape[2:]) == (int(T), 7)
+    sd, Ks = _lib.f32c(seeds), seeds.size(1)
+    traj, status, choice, all_traj, all_status = _plan_outputs(B, max(int(o["candidates"]), 0) + Ks, T, dev, return_all)
+    _lib.call("mpx_franka_plan_seeded", _lib.ptr(qs), _lib.ptr(qg), B, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
+              _lib.ptr(sr), _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
+              ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(sd) if Ks else None, Ks,
+              _lib.ptr(traj), _lib.ptr(status), _lib.ptr(choice), _lib.ptr(all_traj), _lib.ptr(all_status))
+    return (traj, status, choice, all_traj, all_status) if return_all else (traj, status)
+
+
+ROADMAP_FOUND, ROADMAP_NO_PATH, ROADMAP_BAD_ENDPOINT = 0, 1, 2  # status values of ``franka_roadmap``
+ROADMAP_EDGE_UNTESTED, ROADMAP_EDGE_FREE, ROADMAP_EDGE_BLOCKED = 0, 1, 2  # ``edge_state`` of ``return_graph``
+# MPX_ROADMAP_DEFAULT_* (include/mpinets_hip.h; profiles/roadmap_timing.md holds the runs behind them)
+ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.05, connect_radius=float("inf"), max_rounds=64, smooth_passes=8,
+                        check_margin=1e-4, clearance=0.0, check_self=True)
+
+
+def _roadmap_options(who: str, options: dict):
+    if not options.keys() <= ROADMAP_DEFAULTS.keys():
+        raise TypeError(f"{who}: unknown option(s) {sorted(options.keys() - ROADMAP_DEFAULTS.keys())}")
+    o = dict(ROADMAP_DEFAULTS, **options) if options else ROADMAP_DEFAULTS
+    return _lib.RoadmapOptions(int(o["nodes"]), float(o["resolution"]), float(o["connect_radius"]), int(o["max_rounds"]),
+                               int(o["smooth_passes"]), float(o["check_margin"]), float(o["clearance"]),
+                               int(bool(o["check_self"]))), o
+
+
+def franka_roadmap(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
+                   env_offset: int = 0, return_graph: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                   finger: float = ft.FINGER_OPENING, **options):
+    """A lazy probabilistic roadmap per problem on the GPU (csrc/roadmap.hip): ``nodes`` configurations (start, goal and
+    Philox draws inside ``limits`` keyed by (``seed``, ``env_offset`` + row, node)) judged by ``franka_plan``'s validity test,
+    the shortest start-goal path over the edges not known to be blocked, its untested edges tested every ``resolution`` rad,
+    searched again until a path survives.  The path, resampled to ``T`` waypoints and rounded by ``smooth_passes`` passes
+    of (1/4, 1/2, 1/4), is a seed for ``franka_plan(seeds=...)``: it is collision free as a polyline, not yet smooth enough.
+
+    :param q_start, q_goal, cuboids, cylinders, limits: as for ``franka_plan``
+    :param options: the fields of ``mpx_roadmap_options``, see ``ROADMAP_DEFAULTS``
+    :returns: ``traj`` [B,T,7] (NaN rows where ``status`` != 0; a one-edge path is ``franka_plan``'s straight line bit for
+        bit), ``status`` int32 [B] (0 path found, 1 none, 2 an endpoint is non-finite, outside the limits or in collision),
+        ``path`` int32 [B,V] (node indices from 0 = start to 1 = goal, then -1) and ``hops`` int32 [B]; with
+        ``return_graph`` also ``nodes`` [B,V,7], ``edge_state`` uint8 [B,V,V] (0 untested, 1 free, 2 blocked; the diagonal
+        1 for a valid node, 2 for an invalid one) and ``rounds`` int32 [B]."""
+    _lib.require_cuda(q_start, q_goal)
+    assert q_start.ndim == 2 and q_start.size(1) == 7 and q_goal.shape == q_start.shape
+    B, dev = q_start.size(0), q_start.device
+    qs, qg = _lib.f32c(q_start), _lib.f32c(q_goal)
+    lim = limits_operand(limits, dev)
+    copt, o = _roadmap_options("franka_roadmap", options)
+    V = max(int(o["nodes"]), 0)
+    cf, cd, M1, yf, yr, yh, M2 = _primitive_operands(cuboids, cylinders, B)
+    sc, sr, sl = _ik_sphere_table(dev, with_base_link) if M1 + M2 > 0 else (None, None, None)
+    S = 0 if sc is None else int(sc.size(0))
+    traj = torch.empty((B, T, 7), dtype=torch.float32, device=dev)
+    status, hops = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+    path = torch.empty((B, V), dtype=torch.int32, device=dev)
+    nodes = torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None
+    edge_state = torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None
+    rounds = torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None
+    _lib.call("mpx_franka_roadmap", _lib.ptr(qs), _lib.ptr(qg), B, int(T), float(finger), _lib.ptr(lim), _lib.ptr(sc),
               _lib.ptr(sr), _lib.ptr(sl), S, _lib.ptr(cf), _lib.ptr(cd), M1, _lib.ptr(yf), _lib.ptr(yr), _lib.ptr(yh), M2,
               ctypes.byref(copt), int(seed) & (2 ** 64 - 1), int(env_offset), _lib.ptr(traj), _lib.ptr(status),
-              _lib.ptr(choice), _lib.ptr(all_traj), _lib.ptr(all_status))
-    return (traj, status, choice, all_traj, all_status) if return_all else (traj, status)
+              _lib.ptr(path), _lib.ptr(hops), _lib.ptr(nodes), _lib.ptr(edge_state), _lib.ptr(rounds))
+    return (traj, status, path, hops, nodes, edge_state, rounds) if return_graph else (traj, status, path, hops)
+
+
+def franka_plan_global(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
+                       env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL,
+                       with_base_link: bool = False, finger: float = ft.FINGER_OPENING, roadmap: Optional[dict] = None,
+                       **options):
+    """``franka_roadmap``, then ``franka_plan`` with the roadmap's trajectory as one more candidate behind the drawn ones:
+    a row ``franka_plan`` solves comes back identical, a row whose straight line is blocked gets a start that already
+    goes round the obstacle.  Rows where the roadmap found nothing pass a NaN seed (bits 7).
+
+    :param roadmap: options of ``franka_roadmap`` (``ROADMAP_DEFAULTS``); ``check_margin``, ``clearance`` and ``check_self``
+        default to the planner's values in ``options``
+    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 <= 16
+    :returns: what ``franka_plan`` returns (``all_traj`` / ``all_status`` with ``candidates`` + 1 rows, the seed last), then
+        the roadmap's ``status`` int32 [B]."""
+    _, o = _plan_options("franka_plan_global", options)
+    shared = {k: o[k] for k in ("check_margin", "clearance", "check_self")}
+    seed_traj, rm_status, _, _ = franka_roadmap(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, False, limits,
+                                                with_base_link, finger, **dict(shared, **(roadmap or {})))
+    out = franka_plan(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, return_all, limits, with_base_link, finger,
+                      seeds=seed_traj[:, None], **options)
+    return tuple(out) + (rm_status,)
 
 
 PLAN_CLOUD_SCRATCH_BYTES = 256 << 20  # ``franka_plan_cloud`` runs a large batch in slabs of problems whose scratch stays below this

@@ -275,7 +275,7 @@ EXPERT_LENGTH = 50  # the reference's SEQUENCE_LENGTH (data_pipeline/gen_data.py
 
 
 def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
-                         seed: int, env_offset: int) -> Dict[str, torch.Tensor]:
+                         seed: int, env_offset: int, roadmap: bool = False) -> Dict[str, torch.Tensor]:
     from .geometry import TorchCuboids, TorchCylinders
     from .robot import franka_plan
 
@@ -283,7 +283,12 @@ def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
     cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
                          prims["cylinder_quats"])
     # (invalid rows have a NaN goal: the kernel reports status 2 and writes a NaN row for them)
-    traj, status = franka_plan(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
+    if roadmap:  # ``expert_from="roadmap"``: the same planner with the roadmap's path as one more candidate
+        from .robot import franka_plan_global
+
+        traj, status, _ = franka_plan_global(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
+    else:
+        traj, status = franka_plan(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
     return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
 
 
@@ -346,12 +351,15 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     candidate draws are keyed by the global row, so shards agree.  ``expert_from="cloud"`` plans against the batch's own
     scene cloud (the scene rows of ``xyz``) with ``robot.franka_plan_cloud`` at ``expert_point_radius`` instead of against
     the primitives: what a depth or captured cloud, which has no primitives, allows.  Valid then means free by
-    ``FrankaCollisionSampler.check_cloud`` at that radius, which is not the primitive test."""
+    ``FrankaCollisionSampler.check_cloud`` at that radius, which is not the primitive test.
+    ``expert_from="roadmap"`` plans against the primitives with ``robot.franka_plan_global``: a lazy roadmap's path seeds one
+    more candidate, so a problem whose straight line is blocked is not silently dropped; every row ``franka_plan`` solves
+    is returned as ``expert_from="primitives"`` returns it."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
-    if expert_from not in ("primitives", "cloud"):
-        raise ValueError(f"expert_from must be 'primitives' or 'cloud', got {expert_from!r}")
+    if expert_from not in ("primitives", "cloud", "roadmap"):
+        raise ValueError(f"expert_from must be 'primitives', 'cloud' or 'roadmap', got {expert_from!r}")
 
     dev = torch.device(device)
     total = env_offset + B if total_envs is None else int(total_envs)
@@ -368,8 +376,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if collision_free:
         q, q_target, q_goal, valid = _collision_free_problems(out, q, q_target, seed, env_offset, max_redraws)
         out.update(q_goal=q_goal, valid=valid)
-        if expert and expert_from == "primitives":
-            out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset))
+        if expert and expert_from in ("primitives", "roadmap"):
+            out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset, roadmap=expert_from == "roadmap"))
     state = np.random.get_state()
     np.random.seed(seed)
     sampler = FrankaSampler(dev)
