@@ -1,6 +1,7 @@
-// franka_host.h -- host-only (no __device__ code): the argument checks and the cloud launch table that the Franka geometry
-// entries share (ik.hip, plan.hip, roadmap.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for env_offset and scratch size); a
-// new entry takes its checks from here.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
+// franka_host.h -- host-only (no __device__ code): the option defaults, the argument checks and the cloud launch table that
+// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
+// env_offset and scratch size); a new entry takes its defaults and its checks from here, and states a refusal of its own only
+// where no other entry has it.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
 // returns 0 or 1 (field_grid_check's idiom).  Sizes and values are checked before an entry's "nothing to do" return, pointers after.
 #pragma once
 #include <cstdint>
@@ -20,6 +21,10 @@ static inline mpx_plan_options franka_plan_defaults() {
           MPX_PLAN_DEFAULT_EPSILON, MPX_PLAN_DEFAULT_SPREAD, MPX_PLAN_DEFAULT_SUBSTEPS, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f,
           MPX_PLAN_DEFAULT_MAX_JERK, 1};
 }
+static inline mpx_roadmap_options franka_roadmap_defaults() {
+  return {MPX_ROADMAP_DEFAULT_NODES, MPX_ROADMAP_DEFAULT_RESOLUTION, __builtin_inff(), MPX_ROADMAP_DEFAULT_MAX_ROUNDS,
+          MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
+}
 static inline int franka_ik_options_check(const char *who, const mpx_ik_options &opt) {
   MPX_REQUIRE(opt.iterations >= 1, "%s: iterations = %d, need >= 1", who, opt.iterations);
   MPX_REQUIRE(opt.lambda > 0.0f, "%s: lambda must be > 0 (the 6x6 solve has no pivoting)", who);
@@ -32,8 +37,12 @@ static inline int franka_ik_options_check(const char *who, const mpx_ik_options 
 static inline bool franka_plan_T_ok(int T) { return T >= 2 && T <= MPX_PLAN_MAX_T; }
 static inline bool franka_plan_candidates_ok(int K) { return K >= 1 && K <= MPX_PLAN_MAX_CANDIDATES; }
 static inline bool franka_plan_substeps_ok(int substeps) { return substeps >= 1 && substeps <= 64; }
-static inline int franka_plan_options_check(const char *who, int T, const mpx_plan_options &opt) {
+static inline int franka_plan_T_check(const char *who, int T) {
   MPX_REQUIRE(franka_plan_T_ok(T), "%s: T = %d waypoints, need 2 .. %d (one lane each)", who, T, MPX_PLAN_MAX_T);
+  return 0;
+}
+static inline int franka_plan_options_check(const char *who, int T, const mpx_plan_options &opt) {
+  if (franka_plan_T_check(who, T)) return 1;
   MPX_REQUIRE(franka_plan_candidates_ok(opt.candidates), "%s: candidates = %d, need 1 .. %d (one wave each)", who,
               opt.candidates, MPX_PLAN_MAX_CANDIDATES);
   MPX_REQUIRE(opt.iterations >= 0, "%s: iterations = %d, need >= 0", who, opt.iterations);
@@ -43,6 +52,18 @@ static inline int franka_plan_options_check(const char *who, int T, const mpx_pl
   MPX_REQUIRE(franka_plan_substeps_ok(opt.substeps), "%s: substeps = %d, need 1 .. 64", who, opt.substeps);
   MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "%s: negative check_margin or max_jerk", who);
   MPX_REQUIRE(opt.clearance == opt.clearance && opt.spread == opt.spread, "%s: clearance or spread is NaN", who);
+  return 0;
+}
+static inline int franka_roadmap_options_check(const char *who, int T, const mpx_roadmap_options &opt) {
+  if (franka_plan_T_check(who, T)) return 1;
+  MPX_REQUIRE(opt.nodes >= 2 && opt.nodes <= MPX_ROADMAP_MAX_NODES, "%s: nodes = %d, need 2 .. %d (one thread each)", who,
+              opt.nodes, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
+  MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
+  MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
+  MPX_REQUIRE(opt.smooth_passes >= 0, "%s: smooth_passes = %d, need >= 0", who, opt.smooth_passes);
+  MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
   return 0;
 }
 

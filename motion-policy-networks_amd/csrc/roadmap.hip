@@ -255,11 +255,6 @@ __global__ void __launch_bounds__(ROADMAP_THREADS)
   }
 }
 
-static inline mpx_roadmap_options franka_roadmap_defaults() {
-  return {MPX_ROADMAP_DEFAULT_NODES, MPX_ROADMAP_DEFAULT_RESOLUTION, __builtin_inff(), MPX_ROADMAP_DEFAULT_MAX_ROUNDS,
-          MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
-}
-
 MPX_EXPORT int mpx_franka_roadmap(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
                                   const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
                                   const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
@@ -269,16 +264,8 @@ MPX_EXPORT int mpx_franka_roadmap(const float *q_start, const float *q_goal, int
   const char *who = "mpx_franka_roadmap";
   const mpx_roadmap_options opt = options ? *options : franka_roadmap_defaults();
   MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "%s: negative size", who);
-  MPX_REQUIRE(franka_plan_T_ok(T), "%s: T = %d waypoints, need 2 .. %d (one lane each)", who, T, MPX_PLAN_MAX_T);
-  MPX_REQUIRE(opt.nodes >= 2 && opt.nodes <= MPX_ROADMAP_MAX_NODES, "%s: nodes = %d, need 2 .. %d (one thread each)", who,
-              opt.nodes, MPX_ROADMAP_MAX_NODES);
-  MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
-  MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
-  MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
-  MPX_REQUIRE(opt.smooth_passes >= 0, "%s: smooth_passes = %d, need >= 0", who, opt.smooth_passes);
-  MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
-  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
-  if (franka_counts_check(who, S, M1, M2) || franka_env_offset_check(who, env_offset, B)) return 1;
+  if (franka_roadmap_options_check(who, T, opt) || franka_counts_check(who, S, M1, M2) || franka_env_offset_check(who, env_offset, B))
+    return 1;
   if (B == 0) return 0;
   MPX_REQUIRE(traj && status && path && hops, "%s: NULL output (traj, status, path, hops)", who);
   MPX_REQUIRE(q_start && q_goal && limits, "%s: NULL operand (q_start, q_goal, limits)", who);

@@ -1,6 +1,10 @@
-"""Operand rules of the robot-geometry wrappers (``robot``, ``capture``, ``field``), each stated once; C side: csrc/franka_host.h."""
+"""Operand rules of the robot-geometry wrappers (``robot``, ``solvers``, ``capture``, ``field``), each stated once: single
+operands (cloud, counts, limits, scratch), the argument blocks the Franka entries share (sphere table and primitives, cloud,
+options / seed / env_offset) and the merge of keyword options into a C options struct.  C side: csrc/franka_host.h."""
 from __future__ import annotations
 
+import ctypes
+from operator import itemgetter
 from typing import Dict, Optional
 
 import torch
@@ -9,6 +13,7 @@ from . import _lib
 from . import franka_tables as ft
 
 _scratch: Dict[Optional[int], torch.Tensor] = {}
+_sphere_tables: dict = {}
 
 
 def cloud_operand(who: str, cloud: torch.Tensor, B: Optional[int] = None, empty_batch_any_stride: bool = True):
@@ -51,3 +56,80 @@ def scratch_for(device: torch.device, nbytes: int) -> torch.Tensor:
     if buf is None or buf.numel() < nbytes:
         buf = _scratch[device.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
     return buf
+
+
+def sphere_table(device: torch.device, with_base_link: bool):
+    """The collision-sphere table of ``franka_tables`` on ``device`` -> (centres, radii, links), made once per device."""
+    key = (device, bool(with_base_link))
+    if key not in _sphere_tables:
+        c, r, l, _ = ft.collision_sphere_table(with_base_link)
+        _sphere_tables[key] = tuple(torch.from_numpy(a).to(device) for a in (c, r, l))
+    return _sphere_tables[key]
+
+
+# The blocks below return call ARGUMENTS (pointers as plain integers) and, second, the tensors behind those that may be
+# copies made here: the caller keeps that second value in a local until its ``_lib.call`` returns.
+
+
+def sphere_primitive_args(cuboids, cylinders, B: Optional[int] = None, device: Optional[torch.device] = None,
+                          with_base_link: bool = False, table=None):
+    """-> the eleven arguments ``sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames,
+    cyl_radii, cyl_heights, M2`` of an entry that tests spheres against ``geometry.TorchCuboids`` / ``TorchCylinders`` (batch
+    ``B`` where given, or None), and what to hold.  ``table``: a sampler's own (centres, radii, links), always passed;
+    without one the cached table of ``device`` is passed where there is a primitive to test, and S = 0 where there is none."""
+    cub, cyl, held = (None, None, 0), (None, None, None, 0), ()
+    if cuboids is not None:
+        assert B is None or cuboids.centers.size(0) == B
+        cf, cd = held = cuboids.inv_frames, _lib.f32c(cuboids.dims)
+        cub = cf.data_ptr(), cd.data_ptr(), cuboids.centers.size(1)
+    if cylinders is not None:
+        assert B is None or cylinders.centers.size(0) == B
+        yf, yr, yh = cylinders.inv_frames, _lib.f32c(cylinders.radii), _lib.f32c(cylinders.heights)
+        cyl, held = (yf.data_ptr(), yr.data_ptr(), yh.data_ptr(), cylinders.centers.size(1)), held + (yf, yr, yh)
+    if table is None:
+        if cub[2] + cyl[3] == 0:
+            return (None, None, None, 0) + cub + cyl, held
+        table = sphere_table(device, with_base_link)
+    c, r, l = table
+    return (c.data_ptr(), r.data_ptr(), l.data_ptr(), c.size(0)) + cub + cyl, (table, held)
+
+
+def cloud_args(who: str, cloud: torch.Tensor, counts: Optional[torch.Tensor], B: int, point_radius: float,
+               empty_batch_any_stride: bool = True, row: int = 0, null_without_points: bool = False):
+    """-> the six arguments ``cloud, cloud_batch_stride, cloud_point_stride, N, counts, point_radius`` of an entry that reads
+    one cloud per environment (``cloud_operand``'s and ``counts_operand``'s rules), from environment ``row`` on, and what to
+    hold.  ``null_without_points``: ``mpx_franka_ik_cloud`` is handed NULL for a cloud of no rows."""
+    N, bs, ps = cloud_operand(who, cloud, B, empty_batch_any_stride)
+    cn = counts_operand(counts, B)
+    return (None if null_without_points and N == 0 else cloud.data_ptr() + 4 * row * bs, bs, ps, N,
+            None if cn is None else cn.data_ptr() + 4 * row, float(point_radius)), cn
+
+
+def options_tail(copt: ctypes.Structure, seed: int, env_offset: int):
+    """-> the three arguments ``options, seed, env_offset`` of a solver entry (the seed as the uint64 the draws are keyed by)."""
+    return ctypes.byref(copt), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
+
+
+def _self_flag(v) -> int:
+    return int(bool(v))
+
+
+# struct -> (the values of its fields out of an options dict, the cast of each), in field order: the option names are the
+# struct's field names, but ``damping`` (C: ``lambda``)
+_OPTION_FIELDS = {
+    s: (itemgetter(*("damping" if n == "lambda_" else n for n, _ in s._fields_)),
+        tuple(_self_flag if n == "check_self" else float if t is ctypes.c_float else int for n, t in s._fields_))
+    for s in (_lib.IkOptions, _lib.PlanOptions, _lib.RoadmapOptions)}
+
+
+def merge_options(who: str, struct, defaults: dict, options: dict):
+    """Keyword ``options`` over ``defaults`` (one value per field of ``struct``, of the field's type; never written) -> the
+    filled ctypes struct and the merged dict, read-only: its values as the caller gave them, not yet float32.  Without
+    options that dict is ``defaults`` itself (most calls pass none: nothing to merge, nothing to cast)."""
+    values, casts = _OPTION_FIELDS[struct]
+    if not options:
+        return struct(*values(defaults)), defaults
+    if not options.keys() <= defaults.keys():
+        raise TypeError(f"{who}: unknown option(s) {sorted(options.keys() - defaults.keys())}")
+    o = dict(defaults, **options)
+    return struct(*[cast(v) for cast, v in zip(casts, values(o))]), o

@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from ._operands import cloud_operand, counts_operand, scratch_for
 from .robot import FrankaCollisionSampler
+from .solvers import franka_ik_cloud, franka_plan_cloud
 
 # planning_node.py:201-221: the task table and the mount table, rows of (lo x, lo y, lo z, hi x, hi y, hi z); a point is
 # inside when it is STRICTLY inside one of them
@@ -167,8 +168,6 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
     :returns: dict of ``q_goal`` [B,7] (NaN rows where ``ik_status`` != 0), ``ik_status`` int32 [B], ``trajectory``
         [B,T,7] (NaN rows where ``plan_status`` != 0), ``plan_status`` int32 [B] -- 2 for every row without a goal: the
         planner refuses a NaN endpoint -- and ``valid`` bool [B]: both statuses 0."""
-    from .robot import franka_ik_cloud, franka_plan_cloud
-
     q_goal, ik_status = franka_ik_cloud(target_poses, cloud, counts, point_radius, seed=seed, env_offset=env_offset,
                                         **(ik_options or {}))
     traj, plan_status = franka_plan_cloud(q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T,

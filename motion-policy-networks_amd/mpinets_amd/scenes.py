@@ -277,15 +277,13 @@ EXPERT_LENGTH = 50  # the reference's SEQUENCE_LENGTH (data_pipeline/gen_data.py
 def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
                          seed: int, env_offset: int, roadmap: bool = False) -> Dict[str, torch.Tensor]:
     from .geometry import TorchCuboids, TorchCylinders
-    from .robot import franka_plan
+    from .solvers import franka_plan, franka_plan_global
 
     cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
     cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
                          prims["cylinder_quats"])
     # (invalid rows have a NaN goal: the kernel reports status 2 and writes a NaN row for them)
     if roadmap:  # ``expert_from="roadmap"``: the same planner with the roadmap's path as one more candidate
-        from .robot import franka_plan_global
-
         traj, status, _ = franka_plan_global(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
     else:
         traj, status = franka_plan(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
@@ -298,8 +296,8 @@ EXPERT_CLOUD_POINT_RADIUS = 0.02  # [m] about half the spacing of 4096 points on
 def _expert_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
                                seed: int, env_offset: int, point_radius: float) -> Dict[str, torch.Tensor]:
     """``expert_from="cloud"``: the demonstration is planned against the batch's own scene cloud (a view of the slab),
-    with ``robot.franka_plan_cloud``; valid means free by ``FrankaCollisionSampler.check_cloud`` at ``point_radius``."""
-    from .robot import franka_plan_cloud
+    with ``solvers.franka_plan_cloud``; valid means free by ``FrankaCollisionSampler.check_cloud`` at ``point_radius``."""
+    from .solvers import franka_plan_cloud
 
     traj, status = franka_plan_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH, seed=seed,
                                      env_offset=env_offset)
@@ -349,7 +347,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     (a local optimiser standing in for the reference's AIT* + Geometric Fabrics; valid by this engine's sphere model):
     ``global_solutions`` [B,50,7] and ``expert_valid`` = ``valid`` & planned (bool [B]); the other rows are NaN.  The
     candidate draws are keyed by the global row, so shards agree.  ``expert_from="cloud"`` plans against the batch's own
-    scene cloud (the scene rows of ``xyz``) with ``robot.franka_plan_cloud`` at ``expert_point_radius`` instead of against
+    scene cloud (the scene rows of ``xyz``) with ``solvers.franka_plan_cloud`` at ``expert_point_radius`` instead of against
     the primitives: what a depth or captured cloud, which has no primitives, allows.  Valid then means free by
     ``FrankaCollisionSampler.check_cloud`` at that radius, which is not the primitive test.
     ``expert_from="roadmap"`` plans against the primitives with ``robot.franka_plan_global``: a lazy roadmap's path seeds one

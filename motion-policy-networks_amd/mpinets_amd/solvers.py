@@ -1,0 +1,288 @@
+"""The device solvers for the Franka: inverse kinematics, trajectory optimisation and the roadmap, against primitives or a
+point cloud (csrc/ik.hip, plan.hip, roadmap.hip, cloud_field.hip).  Each wrapper is its entry's argument list: the inputs
+(``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
+outputs, in the header's order.  ``robot`` re-exports every name here."""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import franka_tables as ft
+from ._operands import (cloud_args, limits_operand, merge_options, options_tail, scratch_for, sphere_primitive_args,
+                        sphere_table)
+from ._operands import sphere_table as _ik_sphere_table  # noqa: F401  (the name tests and tools reach it by)
+from .field import DEFAULT_VOXEL, CloudField
+
+IK_SEEDS = 64  # MPX_IK_SEEDS: starts per problem, one per lane
+IK_SOLVED, IK_IN_COLLISION, IK_NOT_CONVERGED = 0, 1, 2  # status values of ``franka_ik``
+IK_BIT_CONVERGED, IK_BIT_ENV_HIT, IK_BIT_SELF_HIT = 1, 2, 4  # per-start bits of ``return_all``
+IK_DEFAULTS = dict(iterations=64, damping=0.05, step_clip=0.5, pos_tol=1e-3, rot_tol=float(np.radians(0.5)),
+                   clearance=0.0)
+_IK_DEFAULTS_BY_SELF = {s: dict(IK_DEFAULTS, check_self=s) for s in (False, True)}  # (``check_self``: each entry's own default)
+
+PLAN_SOLVED, PLAN_NO_VALID_CANDIDATE, PLAN_BAD_ENDPOINT = 0, 1, 2  # status values of ``franka_plan``
+PLAN_BIT_ENV_HIT, PLAN_BIT_SELF_HIT, PLAN_BIT_JERK = 1, 2, 4  # per-candidate bits of ``return_all``
+# MPX_PLAN_DEFAULT_* (include/mpinets_hip.h; profiles/plan_timing.md holds the table behind iterations / step / smooth_weight)
+PLAN_DEFAULTS = dict(candidates=8, iterations=20, step=2e-4, smooth_weight=20.0, epsilon=0.05, spread=0.5, substeps=4,
+                     check_margin=1e-4, clearance=0.0, max_jerk=0.15, check_self=True)
+
+ROADMAP_FOUND, ROADMAP_NO_PATH, ROADMAP_BAD_ENDPOINT = 0, 1, 2  # status values of ``franka_roadmap``
+ROADMAP_EDGE_UNTESTED, ROADMAP_EDGE_FREE, ROADMAP_EDGE_BLOCKED = 0, 1, 2  # ``edge_state`` of ``return_graph``
+# MPX_ROADMAP_DEFAULT_* (include/mpinets_hip.h; profiles/roadmap_timing.md holds the runs behind them)
+ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.05, connect_radius=float("inf"), max_rounds=64, smooth_passes=8,
+                        check_margin=1e-4, clearance=0.0, check_self=True)
+
+PLAN_CLOUD_SCRATCH_BYTES = 256 << 20  # ``franka_plan_cloud`` runs a large batch in slabs of problems whose scratch stays below this
+
+
+def _ik_options(who: str, options: dict, check_self: bool) -> _lib.IkOptions:
+    """Keyword options of an IK entry over ``IK_DEFAULTS`` and its ``check_self`` default; ``lambda`` is ``damping``'s C name."""
+    if "lambda" in options:
+        options["damping"] = options.pop("lambda")
+    return merge_options(who, _lib.IkOptions, _IK_DEFAULTS_BY_SELF[bool(check_self)], options)[0]
+
+
+def _plan_options(who: str, options: dict):
+    """Keyword options of a planning entry over ``PLAN_DEFAULTS`` -> the ``_lib.PlanOptions`` and the merged dict."""
+    return merge_options(who, _lib.PlanOptions, PLAN_DEFAULTS, options)
+
+
+def _roadmap_options(who: str, options: dict):
+    """Keyword options of the roadmap over ``ROADMAP_DEFAULTS`` -> the ``_lib.RoadmapOptions`` and the merged dict."""
+    return merge_options(who, _lib.RoadmapOptions, ROADMAP_DEFAULTS, options)
+
+
+def _inputs(first: torch.Tensor, rows: tuple, second: Optional[torch.Tensor], limits, *others):
+    """What every solver starts from: ``first`` ``[B, *rows]`` (target poses, or ``q_start``), ``second`` ``[B,7]`` (``q_init``
+    or None, or ``q_goal``), ``limits`` and the other tensors of the call, all on the current GPU -> B, the device, the two
+    as contiguous float32 and the limits operand."""
+    _lib.require_cuda(first, second, *others)
+    assert first.ndim == 1 + len(rows) and first.shape[1:] == rows
+    B, dev = first.size(0), first.device
+    assert second is None or second.shape == (B, 7)
+    return B, dev, _lib.f32c(first), None if second is None else _lib.f32c(second), limits_operand(limits, dev)
+
+
+# The outputs of an entry, in its argument order: the call passes ``_ptrs`` of them, the caller gets them all or the first few.
+
+
+def _ik_outputs(B: int, dev: torch.device, return_all: bool):  # -> q, status, all_q, all_status (None without return_all)
+    return (torch.empty((B, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty((B, IK_SEEDS, 7), dtype=torch.float32, device=dev) if return_all else None,
+            torch.empty((B, IK_SEEDS), dtype=torch.int32, device=dev) if return_all else None)
+
+
+def _plan_outputs(B: int, K: int, T: int, dev: torch.device, return_all: bool):  # -> traj, status, choice, all_traj, all_status
+    return (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev) if return_all else None,
+            torch.empty((B, K, T, 7), dtype=torch.float32, device=dev) if return_all else None,
+            torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None)
+
+
+def _ptrs(tensors):
+    return [None if t is None else t.data_ptr() for t in tensors]
+
+
+def franka_ik(target_poses: torch.Tensor, cuboids=None, cylinders=None, q_init: Optional[torch.Tensor] = None,
+              limits=ft.JOINT_LIMITS_REAL, seed: int = 0, env_offset: int = 0, with_base_link: bool = False,
+              return_all: bool = False, finger: float = ft.FINGER_OPENING, **options):
+    """Batched collision-free inverse kinematics on the GPU (csrc/ik.hip: damped least squares, 64 starts per pose).
+
+    :param target_poses: [B,4,4] right_gripper poses
+    :param cuboids, cylinders: ``geometry.TorchCuboids`` / ``TorchCylinders`` (batch B) or None, as for
+        ``FrankaCollisionSampler.check``
+    :param limits: [7,2]; cast to float32 toward the inside of the interval, so every returned joint satisfies them as given
+    :param q_init: [B,7] first start of every problem (default: the neutral pose); the other 63 are uniform in ``limits``,
+        drawn from Philox keyed by (``seed``, ``env_offset`` + row, start)
+    :param options: ``iterations`` (64), ``damping`` (0.05; the C struct's ``lambda``), ``step_clip`` (0.5 rad), ``pos_tol``
+        (1e-3 m), ``rot_tol`` (radians; 0.5 degrees), ``clearance`` (0 m), ``check_self`` (default: on when primitives are
+        passed, off in free space)
+    :returns: ``q`` [B,7] (NaN rows where ``status`` != 0) and ``status`` int32 [B]: 0 solved, 1 every converged start
+        collides, 2 nothing converged; with ``return_all`` also ``all_q`` [B,64,7] and ``all_status`` int32 [B,64] (bit 0
+        converged, bit 1 environment hit, bit 2 self hit)."""
+    B, dev, tp, qi, lim = _inputs(target_poses, (4, 4), q_init, limits)
+    copt = _ik_options("franka_ik", options, check_self=cuboids is not None or cylinders is not None)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    out = _ik_outputs(B, dev, return_all)
+    _lib.call("mpx_franka_ik", tp.data_ptr(), B, float(finger), lim.data_ptr(), _lib.ptr(qi), *prims,
+              *options_tail(copt, seed, env_offset), *_ptrs(out))
+    return out if return_all else out[:2]
+
+
+def franka_ik_cloud(target_poses: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                    point_radius: float = 0.0, q_init: Optional[torch.Tensor] = None, limits=ft.JOINT_LIMITS_REAL,
+                    seed: int = 0, env_offset: int = 0, with_base_link: bool = False, return_all: bool = False,
+                    finger: float = ft.FINGER_OPENING, **options):
+    """``franka_ik`` against one POINT CLOUD per environment instead of primitives (``mpx_franka_ik_cloud``): the same 64
+    starts and iterations, and the result is the lowest start that converges, is free of the cloud by
+    ``FrankaCollisionSampler.check_cloud``'s test (``point_radius``, ``clearance`` from the options) and, with
+    ``check_self`` (default: on), of the robot itself.
+
+    :param cloud: [B,N,3] or [B,N,4] float32 on the GPU, any view whose last stride is 1 (``xyz[:, 2048:6144, :3]`` of the
+        slab is read in place); ``counts`` optional int [B] as for ``check_cloud``
+    :param point_radius: radius given to every point (>= 0)
+    :returns: what ``franka_ik`` returns; bit 1 of ``all_status`` is the cloud verdict of a converged start (0 on the
+        others, which are not tested)."""
+    copt = _ik_options("franka_ik_cloud", options, check_self=True)
+    B, dev, tp, qi, lim = _inputs(target_poses, (4, 4), q_init, limits, cloud, counts)
+    points, held = cloud_args("franka_ik_cloud", cloud, counts, B, point_radius, null_without_points=True)
+    sc, sr, sl = sphere_table(dev, with_base_link)
+    out = _ik_outputs(B, dev, return_all)
+    nbytes = int(_lib.load().mpx_franka_ik_cloud_scratch(B))
+    buf = scratch_for(dev, nbytes)
+    _lib.call("mpx_franka_ik_cloud", tp.data_ptr(), B, float(finger), lim.data_ptr(), _lib.ptr(qi), sc.data_ptr(),
+              sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), *points, *options_tail(copt, seed, env_offset), *_ptrs(out),
+              buf.data_ptr(), nbytes)
+    return out if return_all else out[:2]
+
+
+def franka_plan(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
+                env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                finger: float = ft.FINGER_OPENING, seeds: Optional[torch.Tensor] = None, **options):
+    """Batched collision-free trajectories from ``q_start`` to ``q_goal`` on the GPU (csrc/plan.hip): covariant gradient
+    descent on ``T`` waypoints from ``candidates`` starting trajectories per problem (the straight line, and the line bent
+    by Philox draws keyed by (``seed``, ``env_offset`` + row, candidate)), then a validity sweep of every candidate; the
+    result is the lowest valid one.  A LOCAL optimiser, not the reference's AIT*: it can fail where a sampling planner
+    succeeds, and "valid" means free by this engine's sphere model (``FrankaCollisionSampler`` / ``BatchedEvaluator``).
+
+    :param q_start, q_goal: [B,7], inside ``limits`` and collision free (e.g. from ``franka_ik``)
+    :param cuboids, cylinders: ``geometry.TorchCuboids`` / ``TorchCylinders`` (batch B) or None, as for ``franka_ik``
+    :param limits: [7,2]; cast to float32 toward the inside of the interval, as ``franka_ik`` does
+    :param seeds: None (``mpx_franka_plan``), or [B,Ks,T,7] caller-supplied starting trajectories (``mpx_franka_plan_seeded``,
+        e.g. ``franka_roadmap``'s): candidates ``candidates`` .. ``candidates`` + Ks - 1, behind the drawn ones, which stay
+        bit-equal; interior waypoints are clamped into ``limits``, the endpoints replaced, a seed with a non-finite entry
+        is not optimised (NaN rows, bits 7); ``candidates`` + Ks <= 16.  ``all_traj`` / ``all_status`` then have K + Ks rows.
+    :param options: the fields of ``mpx_plan_options``, see ``PLAN_DEFAULTS``
+    :returns: ``traj`` [B,T,7] (NaN rows where ``status`` != 0; waypoints 0 and T-1 are bit-equal to the inputs) and
+        ``status`` int32 [B]: 0 solved, 1 no valid candidate, 2 an endpoint is non-finite, outside the limits or in
+        collision.  "In collision" is the validity sweep's own test, which adds ``check_margin`` (1e-4 m) to the sphere
+        radii AND to the self-collision distances: an endpoint that ``FrankaCollisionSampler.check`` or
+        ``mpx_trajectory_metrics`` accepts by less than that margin is refused with status 2.  With ``return_all`` also ``choice`` int32 [B], ``all_traj`` [B,K,T,7] and ``all_status`` int32 [B,K] (bit 0
+        environment hit, bit 1 self hit, bit 2 jerk)."""
+    B, dev, qs, qg, lim = _inputs(q_start, (7,), q_goal, limits)
+    copt, o = _plan_options("franka_plan", options)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    entry, seeded, Ks = "mpx_franka_plan", (), 0
+    if seeds is not None:
+        _lib.require_cuda(seeds)
+        assert seeds.ndim == 4 and seeds.size(0) == B and tuple(seeds.shape[2:]) == (int(T), 7)
+        sd, Ks = _lib.f32c(seeds), seeds.size(1)
+        entry, seeded = "mpx_franka_plan_seeded", (sd.data_ptr() if Ks else None, Ks)
+    out = _plan_outputs(B, max(int(o["candidates"]), 0) + Ks, T, dev, return_all)
+    _lib.call(entry, qs.data_ptr(), _lib.ptr(qg), B, int(T), float(finger), lim.data_ptr(), *prims,
+              *options_tail(copt, seed, env_offset), *seeded, *_ptrs(out))
+    return out if return_all else out[:2]
+
+
+def franka_roadmap(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
+                   env_offset: int = 0, return_graph: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                   finger: float = ft.FINGER_OPENING, **options):
+    """A lazy probabilistic roadmap per problem on the GPU (csrc/roadmap.hip): ``nodes`` configurations (start, goal and
+    Philox draws inside ``limits`` keyed by (``seed``, ``env_offset`` + row, node)) judged by ``franka_plan``'s validity test,
+    the shortest start-goal path over the edges not known to be blocked, its untested edges tested every ``resolution`` rad,
+    searched again until a path survives.  The path, resampled to ``T`` waypoints and rounded by ``smooth_passes`` passes
+    of (1/4, 1/2, 1/4), is a seed for ``franka_plan(seeds=...)``: it is collision free as a polyline, not yet smooth enough.
+
+    :param q_start, q_goal, cuboids, cylinders, limits: as for ``franka_plan``
+    :param options: the fields of ``mpx_roadmap_options``, see ``ROADMAP_DEFAULTS``
+    :returns: ``traj`` [B,T,7] (NaN rows where ``status`` != 0; a one-edge path is ``franka_plan``'s straight line bit for
+        bit), ``status`` int32 [B] (0 path found, 1 none, 2 an endpoint is non-finite, outside the limits or in collision),
+        ``path`` int32 [B,V] (node indices from 0 = start to 1 = goal, then -1) and ``hops`` int32 [B]; with
+        ``return_graph`` also ``nodes`` [B,V,7], ``edge_state`` uint8 [B,V,V] (0 untested, 1 free, 2 blocked; the diagonal
+        1 for a valid node, 2 for an invalid one) and ``rounds`` int32 [B]."""
+    B, dev, qs, qg, lim = _inputs(q_start, (7,), q_goal, limits)
+    copt, o = _roadmap_options("franka_roadmap", options)
+    V = max(int(o["nodes"]), 0)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    out = (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
+           torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
+           torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)  # traj, status, path, hops, nodes, edge_state, rounds
+    _lib.call("mpx_franka_roadmap", qs.data_ptr(), _lib.ptr(qg), B, int(T), float(finger), lim.data_ptr(), *prims,
+              *options_tail(copt, seed, env_offset), *_ptrs(out))
+    return out if return_graph else out[:4]
+
+
+def franka_plan_global(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
+                       env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL,
+                       with_base_link: bool = False, finger: float = ft.FINGER_OPENING, roadmap: Optional[dict] = None,
+                       **options):
+    """``franka_roadmap``, then ``franka_plan`` with the roadmap's trajectory as one more candidate behind the drawn ones:
+    a row ``franka_plan`` solves comes back identical, a row whose straight line is blocked gets a start that already
+    goes round the obstacle.  Rows where the roadmap found nothing pass a NaN seed (bits 7).
+
+    :param roadmap: options of ``franka_roadmap`` (``ROADMAP_DEFAULTS``); ``check_margin``, ``clearance`` and ``check_self``
+        default to the planner's values in ``options``
+    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 <= 16
+    :returns: what ``franka_plan`` returns (``all_traj`` / ``all_status`` with ``candidates`` + 1 rows, the seed last), then
+        the roadmap's ``status`` int32 [B]."""
+    _, o = _plan_options("franka_plan_global", options)
+    shared = {k: o[k] for k in ("check_margin", "clearance", "check_self")}
+    seed_traj, rm_status, _, _ = franka_roadmap(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, False, limits,
+                                                with_base_link, finger, **dict(shared, **(roadmap or {})))
+    out = franka_plan(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, return_all, limits, with_base_link, finger,
+                      seeds=seed_traj[:, None], **options)
+    return tuple(out) + (rm_status,)
+
+
+def plan_cloud_truncation(point_radius: float = 0.0, clearance: float = 0.0, epsilon: float = PLAN_DEFAULTS["epsilon"],
+                          voxel: float = 0.03, with_base_link: bool = False) -> float:
+    """The truncation ``franka_plan_cloud`` builds its field with: the largest sphere radius + ``point_radius`` +
+    ``clearance`` + ``epsilon`` is the farthest a sphere centre can be from a point and still be repelled; two more cells
+    keep every corner of a cell inside that band below saturation."""
+    rmax = float(ft.collision_sphere_table(with_base_link)[1].max())
+    return rmax + float(point_radius) + max(float(clearance), 0.0) + float(epsilon) + 2.0 * float(voxel)
+
+
+def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                      field=None, point_radius: float = 0.0, T: int = 50, seed: int = 0, env_offset: int = 0,
+                      return_all: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                      finger: float = ft.FINGER_OPENING, **options):
+    """``franka_plan`` against one POINT CLOUD per environment instead of primitives (csrc/cloud_field.hip): the same
+    candidates, metric, jerk and self tests and lowest-valid-candidate rule.  The obstacle term of an iteration reads a
+    truncated distance field of the cloud (``field.CloudField``, built here when ``field`` is None); whether a candidate is
+    free is decided by ``FrankaCollisionSampler.check_cloud``'s kernel on its refined configurations, with this
+    ``point_radius`` and ``clearance + check_margin`` -- the field steers, the exact test judges.
+
+    :param cloud: [B,N,3] or [B,N,4] float32 on the GPU, any view whose last stride is 1 (``xyz[:, 2048:6144, :3]`` of the
+        slab is read in place); ``counts`` optional int [B] as for ``check_cloud``
+    :param field: a ``CloudField`` of this cloud (batch B), or None: one is built on the default grid with
+        ``plan_cloud_truncation(point_radius, clearance, epsilon, voxel)``
+    :param point_radius: radius given to every point (>= 0), in the cost and in the validity test
+    :returns: what ``franka_plan`` returns.  A batch whose scratch would exceed ``PLAN_CLOUD_SCRATCH_BYTES`` runs in slabs
+        of problems (the draws are keyed by the global row: the result does not depend on the slabbing)."""
+    B, dev, qs, qg, lim = _inputs(q_start, (7,), q_goal, limits, cloud, counts)
+    copt, o = _plan_options("franka_plan_cloud", options)
+    _, cn = cloud_args("franka_plan_cloud", cloud, counts, B, point_radius)  # (the refusals, and the counts for the field)
+    if field is None:
+        field = CloudField.build(cloud, cn, truncation=plan_cloud_truncation(point_radius, o["clearance"], o["epsilon"],
+                                                                            DEFAULT_VOXEL, with_base_link))
+    _lib.require_cuda(field.values)
+    if field.values.size(0) != B or not field.values.is_contiguous():
+        raise _lib.MpxError(f"franka_plan_cloud: the field holds {field.values.size(0)} environments, the batch {B}")
+    sc, sr, sl = sphere_table(dev, with_base_link)
+    K, sub = max(int(o["candidates"]), 0), int(o["substeps"])
+    out = _plan_outputs(B, K, T, dev, return_all)
+    lib = _lib.load()
+    per = int(lib.mpx_franka_plan_cloud_scratch(1, int(T), K, sub))
+    slab = max(B, 1) if per <= 0 else max(1, min(max(B, 1), PLAN_CLOUD_SCRATCH_BYTES // per))  # (per <= 0: the call refuses)
+    nodes = field.values[0].numel() if B else 0
+    for b0 in range(0, max(B, 1), slab):
+        n = min(slab, B - b0)
+        nbytes = max(int(lib.mpx_franka_plan_cloud_scratch(n, int(T), K, sub)), 0)
+        buf = scratch_for(dev, nbytes)  # (fetched per call: CloudField.build above, or another entry, may have regrown it)
+
+        def at(t, row):  # pointer to row b0 of a [B, ...] operand
+            return None if t is None else t.data_ptr() + b0 * row * t.element_size()
+
+        _lib.call("mpx_franka_plan_cloud", at(qs, 7), at(qg, 7), n, int(T), float(finger), lim.data_ptr(), sc.data_ptr(),
+                  sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), at(field.values, nodes), ctypes.byref(field.grid),
+                  *cloud_args("franka_plan_cloud", cloud, cn, B, point_radius, row=b0)[0],
+                  *options_tail(copt, seed, int(env_offset) + b0),
+                  *(at(t, row) for t, row in zip(out, (T * 7, 1, 1, K * T * 7, K))), buf.data_ptr(), nbytes)
+    return out if return_all else out[:2]

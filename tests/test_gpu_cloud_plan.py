@@ -283,7 +283,7 @@ def test_edges_sizes_and_guard_rows(B, T, K, substeps):
 
 
 def test_determinism_sharding_seeds_and_slabs(share, monkeypatch):
-    from mpinets_amd import robot
+    from mpinets_amd import robot, solvers
 
     scn, qs, qg, c, want = share
     a, b = up(qs), up(qg)
@@ -298,7 +298,7 @@ def test_determinism_sharding_seeds_and_slabs(share, monkeypatch):
         assert same(torch.cat([x, z]), w)
     # slabs of problems (scratch held below a small bound): the same rows
     per = int(robot._lib.load().mpx_franka_plan_cloud_scratch(1, 50, 8, 4))
-    monkeypatch.setattr(robot, "PLAN_CLOUD_SCRATCH_BYTES", 5 * per)
+    monkeypatch.setattr(solvers, "PLAN_CLOUD_SCRATCH_BYTES", 5 * per)  # (the module that owns it: ``robot`` re-exports a copy)
     slabbed = robot.franka_plan_cloud(a, b, c, **kw)
     for g, w in zip(slabbed, want):
         assert same(g, w)
