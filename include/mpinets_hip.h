@@ -522,6 +522,8 @@ int mpx_sa3_front_bf16x3(const float *x, int ldx, int B, int rows, const void *p
  * loss_sum[b] = sum_n max(0, margin - min(cuboid sdf, cylinder sdf)); the reference's mean is
  * sum_b loss_sum[b] / (B*N).  grad_points (optional, strided like points) receives
  * d(loss_sum[b]) / d(point): the autograd of geometry.py:256-288 / :478-507 restated analytically.
+ * A point with a NaN or infinite coordinate takes no part: it adds nothing to loss_sum[b] and its
+ * gradient row is +0 (the reference returns NaN there); the other rows are as without it.
  * frames / dims / radii / heights as for mpx_cuboid_sdf / mpx_cylinder_sdf.                          */
 int mpx_collision_hinge(const float *points, int64_t batch_stride, int point_stride, int B, int N,
                         const float *cub_frames, const float *cub_dims, int M1, const float *cyl_frames,

@@ -49,13 +49,18 @@ __global__ void __launch_bounds__(256)
   for (int j = threadIdx.x; j < N; j += 256) {
     const float *p = pts + (int64_t)b * pbs + (int64_t)j * pps;
     const float x = p[0], y = p[1], z = p[2];
-    float best = __builtin_inff();
+    // A row with a NaN or infinite coordinate takes no part: no loss, a zero gradient.  (fmaxf / fminf drop a NaN operand,
+    // so the distance forms would read a NaN row as a point ON a surface: sdf 0, a hinge of `margin`.)
+    const float inf = __builtin_inff();
+    const bool finite = __builtin_fabsf(x) < inf && __builtin_fabsf(y) < inf && __builtin_fabsf(z) < inf;
+    const int n1 = finite ? M1 : 0, n2 = finite ? M2 : 0;
+    float best = inf;
     int arg = -1;  // < M1: cuboid, else cylinder; the reference's torch.min / torch.minimum keep the first minimum
-    for (int m = 0; m < M1; ++m) {
+    for (int m = 0; m < n1; ++m) {
       float s = cuboid_sdf(cf + 16 * m, cd[3 * m], cd[3 * m + 1], cd[3 * m + 2], x, y, z);
       if (s < best) best = s, arg = m;
     }
-    for (int m = 0; m < M2; ++m) {
+    for (int m = 0; m < n2; ++m) {
       float s = cylinder_sdf(yf + 16 * m, yr[m], yh[m], x, y, z);
       if (s < best) best = s, arg = M1 + m;
     }

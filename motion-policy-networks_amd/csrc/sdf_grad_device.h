@@ -1,7 +1,7 @@
 // sdf_grad_device.h -- analytic gradients of the single-primitive signed distances of sdf_device.h: the derivative of the
 // function those forms EVALUATE (autograd of geometry.py:276-287 / :486-506), not of an ideal distance field.
-// sgn / box_grad serve the collision hinge (loss.hip, whose kernel text and code object are as before) and the trajectory
-// optimiser (plan.hip), which also uses the per-primitive forms below.
+// sgn / box_grad serve the collision hinge (loss.hip, which exposes this gradient per point: tests/test_gpu_loss_float64.py
+// holds it to float64 there) and the trajectory optimiser (plan.hip), which also uses the per-primitive forms below.
 #pragma once
 #include "sdf_device.h"
 
