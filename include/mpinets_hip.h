@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_roadmap,
+int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_follow,
+                          struct mpx_follow_options; 341 (unchanged, likewise): mpx_franka_roadmap,
                           struct mpx_roadmap_options, mpx_franka_plan_seeded;
                           341: the route queries mpx_fps_route, mpx_franka_collision_route, mpx_linear_route, mpx_linear_wgrad_route,
                           mpx_pool_wgrad_route, mpx_sa_mlp_route (additions only);
@@ -394,6 +395,102 @@ int mpx_franka_roadmap(const float *q_start, const float *q_goal, int B, int T, 
                        const float *cyl_radii, const float *cyl_heights, int M2, const mpx_roadmap_options *options,
                        uint64_t seed, int64_t env_offset, float *traj, int32_t *status, int32_t *path, int32_t *hops,
                        float *nodes, uint8_t *edge_state, int32_t *rounds, mpx_stream_t stream);
+
+/* A reactive follower of an end-effector path, its retiming and its verdict: where the reference's data generator runs
+ * Geometric Fabrics along the global plan, downsamples to 50 waypoints and filters with verify_trajectory
+ * (data_pipeline/gen_data.py:156-307, 433-528: the 'hybrid_solutions' key).  This is a STAND-IN, NOT Lula's fabric and claims
+ * no parity with it: a damped second-order joint-space system driven by mpx_franka_ik's damped-least-squares direction
+ * toward the current guide pose, mpx_franka_plan's obstacle gradient, a joint-limit barrier and viscous damping, under
+ * a joint speed limit.  One wave per problem, lane = collision sphere in the obstacle term; no randomness (no seed, no
+ * env_offset): row b depends on row b's inputs alone, and the obstacle sum is reduced across lanes in a fixed order.
+ *   q_start [B,7]; poses [B,W,4,4] row-major right_gripper guide poses, 1 <= W <= MPX_FOLLOW_MAX_POSES; limits [7,2], the
+ *   sphere table and the primitives exactly as for mpx_franka_ik (S <= 64, M1, M2 <= 64, zero-volume rows skipped);
+ *   2 <= T <= MPX_PLAN_MAX_T; v_init [B,7] (NULL: zeros); progress_init int32 [B,3] = {waypoint w, steps spent on it n_w,
+ *   finished flag} (NULL: {0, 0, 0}).
+ *   One step from (q, v, w, n_w), p_w / R_w the position / rotation of guide pose w:
+ *     1. FK of q: p, R the right_gripper frame; dist = |p_w - p|.
+ *     2. Switch: if w < W-1 and (dist <= switch_radius or n_w >= switch_steps): w <- w+1, n_w <- 0, dist recomputed for the
+ *        new w.  At most one advance per step.
+ *     3. Stop: if w was W-1 ON ENTRY to the step and (dist < final_radius or n_w >= final_steps): the row is FINISHED and
+ *        takes no step, now or later.
+ *     4. Attractor: e = [p_w - p ; rotvec(R_w R^T)], u = J^T (J J^T + lambda^2 I)^-1 e scaled so that max |u_j| <= step_clip:
+ *        mpx_franka_ik's dq, statement for statement.
+ *     5. Obstacle: g = mpx_franka_plan's g_t for this one configuration (the same c'(d), epsilon, clearance, arg-min tie
+ *        rule and upstream-joint mask); 0 without live primitives or with S = 0.
+ *     6. a_j = attract u_j - repel g_j + limit_gain (max(0, (lo_j + limit_band) - q_j) - max(0, q_j - (hi_j - limit_band)))
+ *              - damping v_j.
+ *     7. q'_j = q_j + dt v_j (position first, as gen_data.py:283-284); v'_j = clamp(v_j + dt a_j, -speed_limit, speed_limit);
+ *        q'_j is clamped into the limits, and where the clamp moved it v'_j = 0.  n_w <- n_w + 1.
+ *   At most options->max_steps steps are taken (no unbounded loop on the device: max_steps <= MPX_FOLLOW_MAX_STEPS is
+ *   checked on the host, the retiming search is a bisection of fixed length).
+ *   Dense path.  path[0] = q_start, path[i] = q after step i; arc[0] = 0, arc[i] = arc[i-1] + |path[i] - path[i-1]|_2
+ *   (sqrtf of the fma chain over j = 0..6, in float32); n = steps[b] <= max_steps.  path [B,max_steps+1,7] and arc
+ *   [B,max_steps+1] are caller-provided device buffers (required), written for 0..n only.
+ *   Retiming to T waypoints of constant arc-length spacing (gen_data.py's downsample): s_t = ((float)t / (float)(T-1)) arc[n];
+ *   i = the largest index with arc[i] <= s_t, capped at n-1; f = clamp((s_t - arc[i]) / (arc[i+1] - arc[i]), 0, 1), 0 for a
+ *   zero denominator; q_t = fma(f, path[i+1] - path[i], path[i]).  Waypoints 0 and T-1 are path[0] and path[n] bit for
+ *   bit; with n = 0 all T waypoints are q_start.
+ *   Verdict on the T waypoints, bits int32 [B]: bits 0-2 are mpx_franka_plan's validity tests unchanged (the refined sweep
+ *   with substeps, check_margin, clearance and check_self; third differences against max_jerk * MPX_PLAN_JERK_SHARE);
+ *   bit 3 (MPX_FOLLOW_BIT_MISS) is !(|p_{W-1} - p(q_{T-1})| <= miss_tol * MPX_FOLLOW_MISS_SHARE) (gen_data.py:420).  There
+ *   is no joint-limit bit: every waypoint is a convex combination of configurations clamped into the limits.
+ *   status int32 [B]: 0 valid (bits == 0); 1 followed but bits != 0; 2 bad input -- q_start not finite or outside the
+ *   limits, a guide pose with an entry of its first three rows not finite, with progress_init == NULL (a fresh rollout)
+ *   q_start itself failing mpx_franka_plan's configuration test, or (stated here, no other entry has them) v_init not
+ *   finite, progress_init with w outside 0 .. W-1 or n_w < 0 -- which takes no steps: steps 0, bits 15.  A CONTINUED
+ *   rollout (progress_init given) is not refused for a state in collision: the dense path may graze an obstacle, a
+ *   controller must be able to step on from any state it produced, and the verdict judges the trajectory.
+ *   steps int32 [B]; traj [B,T,7], NaN where status != 0; traj_any [B,T,7] (optional) holds the status-1 rows too (NaN
+ *   on status 2).  Optional q_end, v_end [B,7] and progress_end int32 [B,3]: the state after the last step (status 2: the
+ *   state as given).  Passing them back as q_start, v_init, progress_init CONTINUES the rollout: k calls of max_steps m
+ *   walk the dense path of one call of k m steps bit for bit -- the entry is a reactive controller that can be stepped.
+ *   A row that comes in finished takes no step (steps 0) and is judged on T copies of q_start.
+ *   No allocation, no scratch, no atomics; everything is enqueued on `stream` (capturable).  B == 0 launches nothing.    */
+#define MPX_FOLLOW_MAX_POSES 64
+#define MPX_FOLLOW_MAX_STEPS 4096
+#define MPX_FOLLOW_BIT_MISS 8
+#define MPX_FOLLOW_MISS_SHARE 0.9999f
+#define MPX_FOLLOW_DEFAULT_DT 0.005f            /* gen_data.py:268 */
+#define MPX_FOLLOW_DEFAULT_MAX_STEPS 1024
+#define MPX_FOLLOW_DEFAULT_ATTRACT 144.0f
+#define MPX_FOLLOW_DEFAULT_DAMPING 24.0f        /* critical for that stiffness */
+#define MPX_FOLLOW_DEFAULT_REPEL 40.0f
+#define MPX_FOLLOW_DEFAULT_LIMIT_GAIN 50.0f
+#define MPX_FOLLOW_DEFAULT_LIMIT_BAND 0.1f
+#define MPX_FOLLOW_DEFAULT_SPEED_LIMIT 1.6999f  /* the fabric config's cspace_speed_limit */
+#define MPX_FOLLOW_DEFAULT_SWITCH_RADIUS 0.15f
+#define MPX_FOLLOW_DEFAULT_SWITCH_STEPS 100     /* 0.5 s at dt */
+#define MPX_FOLLOW_DEFAULT_FINAL_RADIUS 0.005f
+#define MPX_FOLLOW_DEFAULT_FINAL_STEPS 800      /* 4 s at dt: gen_data.py:76, 278, 291-294 */
+#define MPX_FOLLOW_DEFAULT_MISS_TOL 0.05f       /* gen_data.py:420 */
+typedef struct mpx_follow_options { /* NULL options: the defaults above, lambda / step_clip the IK defaults, epsilon / substeps /
+                                       check_margin / max_jerk the planner's, clearance 0, check_self 1 */
+  float dt;                         /* > 0 [s]                                                          */
+  int max_steps;                    /* 1 .. MPX_FOLLOW_MAX_STEPS: steps of this call                     */
+  float attract, damping;           /* >= 0: gain on u, viscous damping                                  */
+  float lambda, step_clip;          /* > 0: as in mpx_ik_options                                         */
+  float repel;                      /* >= 0: gain on the obstacle gradient                               */
+  float epsilon;                    /* > 0 [m]: width of the band in which an obstacle repels            */
+  float clearance;                  /* [m], added to the radii in the obstacle term AND the verdict      */
+  float limit_gain, limit_band;     /* >= 0: the joint-limit barrier and its width [rad]                 */
+  float speed_limit;                /* > 0 [rad/s] per joint                                             */
+  float switch_radius;              /* >= 0 [m]: advance to the next guide pose inside it                */
+  int switch_steps;                 /* >= 1: ... or after this many steps on one pose                    */
+  float final_radius;               /* >= 0 [m]: finished inside it of the last pose                     */
+  int final_steps;                  /* >= 1: ... or after this many steps on the last pose               */
+  int substeps;                     /* 1 .. 64: pieces per segment in the validity sweep                 */
+  float check_margin;               /* >= 0 [m], as in mpx_plan_options                                  */
+  float max_jerk;                   /* >= 0: largest third difference [rad]                              */
+  int check_self;                   /* non-zero: self collisions invalidate                              */
+  float miss_tol;                   /* >= 0 [m]                                                          */
+} mpx_follow_options;
+int mpx_franka_follow(const float *q_start, const float *poses, int B, int W, int T, float finger, const float *limits,
+                      const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                      const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                      const float *cyl_radii, const float *cyl_heights, int M2, const float *v_init,
+                      const int32_t *progress_init, const mpx_follow_options *options, float *path, float *arc,
+                      int32_t *status, int32_t *bits, int32_t *steps, float *traj, float *traj_any, float *q_end,
+                      float *v_end, int32_t *progress_end, mpx_stream_t stream);
 
 /* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
  * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at

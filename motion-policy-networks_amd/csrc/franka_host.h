@@ -1,5 +1,5 @@
 // franka_host.h -- host-only (no __device__ code): the option defaults, the argument checks and the cloud launch table that
-// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
+// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, follow.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
 // env_offset and scratch size); a new entry takes its defaults and its checks from here, and states a refusal of its own only
 // where no other entry has it.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
 // returns 0 or 1 (field_grid_check's idiom).  Sizes and values are checked before an entry's "nothing to do" return, pointers after.
@@ -24,6 +24,14 @@ static inline mpx_plan_options franka_plan_defaults() {
 static inline mpx_roadmap_options franka_roadmap_defaults() {
   return {MPX_ROADMAP_DEFAULT_NODES, MPX_ROADMAP_DEFAULT_RESOLUTION, __builtin_inff(), MPX_ROADMAP_DEFAULT_MAX_ROUNDS,
           MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
+}
+static inline mpx_follow_options franka_follow_defaults() {
+  return {MPX_FOLLOW_DEFAULT_DT, MPX_FOLLOW_DEFAULT_MAX_STEPS, MPX_FOLLOW_DEFAULT_ATTRACT, MPX_FOLLOW_DEFAULT_DAMPING,
+          MPX_IK_DEFAULT_LAMBDA, MPX_IK_DEFAULT_STEP_CLIP, MPX_FOLLOW_DEFAULT_REPEL, MPX_PLAN_DEFAULT_EPSILON, 0.0f,
+          MPX_FOLLOW_DEFAULT_LIMIT_GAIN, MPX_FOLLOW_DEFAULT_LIMIT_BAND, MPX_FOLLOW_DEFAULT_SPEED_LIMIT,
+          MPX_FOLLOW_DEFAULT_SWITCH_RADIUS, MPX_FOLLOW_DEFAULT_SWITCH_STEPS, MPX_FOLLOW_DEFAULT_FINAL_RADIUS,
+          MPX_FOLLOW_DEFAULT_FINAL_STEPS, MPX_PLAN_DEFAULT_SUBSTEPS, MPX_PLAN_DEFAULT_CHECK_MARGIN, MPX_PLAN_DEFAULT_MAX_JERK, 1,
+          MPX_FOLLOW_DEFAULT_MISS_TOL};
 }
 static inline int franka_ik_options_check(const char *who, const mpx_ik_options &opt) {
   MPX_REQUIRE(opt.iterations >= 1, "%s: iterations = %d, need >= 1", who, opt.iterations);
@@ -52,6 +60,28 @@ static inline int franka_plan_options_check(const char *who, int T, const mpx_pl
   MPX_REQUIRE(franka_plan_substeps_ok(opt.substeps), "%s: substeps = %d, need 1 .. 64", who, opt.substeps);
   MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "%s: negative check_margin or max_jerk", who);
   MPX_REQUIRE(opt.clearance == opt.clearance && opt.spread == opt.spread, "%s: clearance or spread is NaN", who);
+  return 0;
+}
+// (every float is tested as `x >= 0` or `x > 0`: a NaN fails either)
+static inline int franka_follow_options_check(const char *who, int W, int T, const mpx_follow_options &opt) {
+  if (franka_plan_T_check(who, T)) return 1;
+  MPX_REQUIRE(W >= 1 && W <= MPX_FOLLOW_MAX_POSES, "%s: W = %d guide poses, need 1 .. %d", who, W, MPX_FOLLOW_MAX_POSES);
+  MPX_REQUIRE(opt.max_steps >= 1 && opt.max_steps <= MPX_FOLLOW_MAX_STEPS, "%s: max_steps = %d, need 1 .. %d (the time loop's bound)",
+              who, opt.max_steps, MPX_FOLLOW_MAX_STEPS);
+  MPX_REQUIRE(opt.dt > 0.0f && opt.dt < __builtin_inff(), "%s: dt must be > 0 and finite", who);
+  MPX_REQUIRE(opt.lambda > 0.0f, "%s: lambda must be > 0 (the 6x6 solve has no pivoting)", who);
+  MPX_REQUIRE(opt.step_clip > 0.0f, "%s: step_clip must be > 0", who);
+  MPX_REQUIRE(opt.attract >= 0.0f && opt.damping >= 0.0f && opt.repel >= 0.0f && opt.limit_gain >= 0.0f && opt.limit_band >= 0.0f,
+              "%s: negative (or NaN) attract, damping, repel, limit_gain or limit_band", who);
+  MPX_REQUIRE(opt.epsilon > 0.0f, "%s: epsilon must be > 0", who);
+  MPX_REQUIRE(opt.speed_limit > 0.0f, "%s: speed_limit must be > 0", who);
+  MPX_REQUIRE(opt.switch_radius >= 0.0f && opt.final_radius >= 0.0f && opt.miss_tol >= 0.0f,
+              "%s: negative (or NaN) switch_radius, final_radius or miss_tol", who);
+  MPX_REQUIRE(opt.switch_steps >= 1 && opt.final_steps >= 1, "%s: switch_steps = %d, final_steps = %d, need >= 1", who,
+              opt.switch_steps, opt.final_steps);
+  MPX_REQUIRE(franka_plan_substeps_ok(opt.substeps), "%s: substeps = %d, need 1 .. 64", who, opt.substeps);
+  MPX_REQUIRE(opt.check_margin >= 0.0f && opt.max_jerk >= 0.0f, "%s: negative check_margin or max_jerk", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
   return 0;
 }
 static inline int franka_roadmap_options_check(const char *who, int T, const mpx_roadmap_options &opt) {

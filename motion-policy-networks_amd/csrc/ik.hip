@@ -11,7 +11,7 @@
 // never diverge.  Per iteration: FK (franka_fk_visit, keeping the seven joint origins, their z axes and right_gripper),
 // e = [p_t - p ; rotvec(R_t R^T)], the geometric Jacobian J[:, j] = [z_j x (p - o_j) ; z_j],
 // dq = J^T (J J^T + lambda^2 I)^-1 e through an unrolled 6x6 Cholesky (positive definite for lambda > 0: no pivoting),
-// the step scaled so that max |dq_j| <= step_clip, q clamped into the limits.
+// the step scaled so that max |dq_j| <= step_clip (dls_direction.inc states these), q clamped into the limits.
 // A lane is ACCEPTED when one more FK of its final q -- the code mpx_franka_fk runs -- is within pos_tol / rot_tol of the
 // target.  Accepted lanes are then visited in lane order and the WAVE tests one candidate together: lane = collision
 // sphere against the problem's live primitives (compacted into LDS once, sdf_device.h forms, `sdf <= radius + clearance`
@@ -26,33 +26,12 @@
 #include "common.h"
 #include "franka_host.h"
 #include "franka_device.h"
+#include "dls_device.h"  // what the solver shares with follow.hip: the rotation vector (and dls_direction.inc)
 #include "sdf_device.h"
 #include "philox.h"
 
 enum { STREAM_IK = 13 };
 constexpr int IK_FRAME_FLOATS = MPX_NUM_FRAMES * 12;
-
-// rotvec of E = A B^T (row-major 3x3 each): w = sin(theta) axis from the antisymmetric part, theta = atan2(|w|, cos).
-// Returns theta.  (|w| -> 0 with cos < 0, a half turn about an unknown axis, yields a zero vector: such a lane moves on
-// its position error and leaves the half turn within a step.)
-__device__ __forceinline__ float ik_rotvec(const float *a, const float *b, float (&w)[3]) {
-  float E[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      E[3 * i + k] = mpx_fma(a[3 * i + 2], b[3 * k + 2], mpx_fma(a[3 * i + 1], b[3 * k + 1], a[3 * i] * b[3 * k]));
-  w[0] = 0.5f * (E[7] - E[5]);
-  w[1] = 0.5f * (E[2] - E[6]);
-  w[2] = 0.5f * (E[3] - E[1]);
-  const float c = 0.5f * ((E[0] + E[4] + E[8]) - 1.0f);
-  const float s = sqrtf(mpx_fma(w[2], w[2], mpx_fma(w[1], w[1], w[0] * w[0])));
-  const float theta = atan2f(s, c);
-  const float k = s > 1e-7f ? theta / s : 1.0f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) w[i] *= k;
-  return theta;
-}
 
 __global__ void __launch_bounds__(64)
     franka_ik_kernel(const float *__restrict__ targets, float finger, const float *__restrict__ limits,
@@ -100,74 +79,9 @@ __global__ void __launch_bounds__(64)
       }
       if constexpr (id == 14) eff = g;
     });
-    float e[6];
-    {
-      float w[3];
-      ik_rotvec(Rt, eff.r, w);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) e[i] = pt[i] - eff.t[i], e[3 + i] = w[i];
-    }
-    float J[6][7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float dx = eff.t[0] - o[j][0], dy = eff.t[1] - o[j][1], dz = eff.t[2] - o[j][2];
-      J[0][j] = mpx_fma(z[j][1], dz, -(z[j][2] * dy));
-      J[1][j] = mpx_fma(z[j][2], dx, -(z[j][0] * dz));
-      J[2][j] = mpx_fma(z[j][0], dy, -(z[j][1] * dx));
-      J[3][j] = z[j][0], J[4][j] = z[j][1], J[5][j] = z[j][2];
-    }
-    // A = J J^T + lambda^2 I = L L^T (lower triangle in place), then L y' = e, L^T y = y'
-    float L[6][6], inv[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int k = 0; k <= i; ++k) {
-        float acc = i == k ? lam2 : 0.0f;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) acc = mpx_fma(J[i][j], J[k][j], acc);
-        L[i][k] = acc;
-      }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      float d = L[k][k];
-#pragma unroll
-      for (int m = 0; m < k; ++m) d = mpx_fma(-L[k][m], L[k][m], d);
-      const float root = sqrtf(d);
-      inv[k] = 1.0f / root;
-      L[k][k] = root;
-#pragma unroll
-      for (int i = k + 1; i < 6; ++i) {
-        float v = L[i][k];
-#pragma unroll
-        for (int m = 0; m < k; ++m) v = mpx_fma(-L[i][m], L[k][m], v);
-        L[i][k] = v * inv[k];
-      }
-    }
-    float y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      float v = e[i];
-#pragma unroll
-      for (int m = 0; m < i; ++m) v = mpx_fma(-L[i][m], y[m], v);
-      y[i] = v * inv[i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-      float v = y[i];
-#pragma unroll
-      for (int m = i + 1; m < 6; ++m) v = mpx_fma(-L[m][i], y[m], v);
-      y[i] = v * inv[i];
-    }
-    float dq[7], big = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      float v = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) v = mpx_fma(J[i][j], y[i], v);
-      dq[j] = v;
-      big = fmaxf(big, __builtin_fabsf(v));
-    }
-    const float scale = big > opt.step_clip ? opt.step_clip / big : 1.0f;
+#define DLS_STEP_CLIP opt.step_clip
+#include "dls_direction.inc"
+#undef DLS_STEP_CLIP
 #pragma unroll
     for (int j = 0; j < 7; ++j) q[j] = fminf(fmaxf(q[j] + dq[j] * scale, lo[j]), hi[j]);
   }

@@ -43,6 +43,7 @@ PROTOTYPES = {
     "mpx_franka_plan": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P],
     "mpx_franka_plan_seeded": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, I, P, P, P, P, P, P],
     "mpx_franka_roadmap": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
+    "mpx_franka_follow": [P, P, I, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
     "mpx_franka_plan_cloud_scratch": [I, I, I, I],
@@ -151,6 +152,16 @@ class RoadmapOptions(ctypes.Structure):
     """``mpx_roadmap_options`` (include/mpinets_hip.h); the defaults are the header's MPX_ROADMAP_DEFAULT_*."""
     _fields_ = [("nodes", c_int), ("resolution", c_float), ("connect_radius", c_float), ("max_rounds", c_int),
                 ("smooth_passes", c_int), ("check_margin", c_float), ("clearance", c_float), ("check_self", c_int)]
+
+
+class FollowOptions(ctypes.Structure):
+    """``mpx_follow_options`` (include/mpinets_hip.h); the defaults are the header's MPX_FOLLOW_DEFAULT_* and, for the fields
+    it shares with them, the IK's and the planner's."""
+    _fields_ = [("dt", c_float), ("max_steps", c_int), ("attract", c_float), ("damping", c_float), ("lambda_", c_float),
+                ("step_clip", c_float), ("repel", c_float), ("epsilon", c_float), ("clearance", c_float),
+                ("limit_gain", c_float), ("limit_band", c_float), ("speed_limit", c_float), ("switch_radius", c_float),
+                ("switch_steps", c_int), ("final_radius", c_float), ("final_steps", c_int), ("substeps", c_int),
+                ("check_margin", c_float), ("max_jerk", c_float), ("check_self", c_int), ("miss_tol", c_float)]
 
 
 class FieldGrid(ctypes.Structure):

@@ -115,11 +115,12 @@ def _self_flag(v) -> int:
 
 
 # struct -> (the values of its fields out of an options dict, the cast of each), in field order: the option names are the
-# struct's field names, but ``damping`` (C: ``lambda``)
+# struct's field names, but ``damping`` (C: ``lambda``) where the struct has no ``damping`` of its own (the follower has:
+# its ``lambda_`` keeps its name)
 _OPTION_FIELDS = {
-    s: (itemgetter(*("damping" if n == "lambda_" else n for n, _ in s._fields_)),
+    s: (itemgetter(*("damping" if n == "lambda_" and "damping" not in dict(s._fields_) else n for n, _ in s._fields_)),
         tuple(_self_flag if n == "check_self" else float if t is ctypes.c_float else int for n, t in s._fields_))
-    for s in (_lib.IkOptions, _lib.PlanOptions, _lib.RoadmapOptions)}
+    for s in (_lib.IkOptions, _lib.PlanOptions, _lib.RoadmapOptions, _lib.FollowOptions)}
 
 
 def merge_options(who: str, struct, defaults: dict, options: dict):

@@ -304,20 +304,54 @@ def _expert_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor,
     return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
 
 
+HYBRID_GUIDE_POSES = 8  # guide poses handed to the follower: waypoints round(i * 49 / 8), i = 1..8, of the global plan
+
+
+def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, global_solutions: torch.Tensor,
+                         expert_valid: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """``hybrid=True``: the global plan steers, the follower produces.  ``solvers.franka_follow`` (a stand-in for the
+    reference's Geometric Fabrics expert, NOT Lula: gen_data.py:156-307) follows the right_gripper poses of eight waypoints
+    of ``global_solutions``, its dense path is retimed to 50 waypoints and judged; the target becomes the pose the
+    trajectory actually ends at (hindsight goal revision, gen_data.py:303-306).  Rows without a global solution hand NaN
+    poses to the follower and come back with status 2."""
+    from .geometry import TorchCuboids, TorchCylinders
+    from .robot import franka_fk, frames_to_matrix
+    from .solvers import franka_follow
+
+    cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
+    cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
+                         prims["cylinder_quats"])
+    B = q_start.size(0)
+    at = [int(round(i * (EXPERT_LENGTH - 1) / HYBRID_GUIDE_POSES)) for i in range(1, HYBRID_GUIDE_POSES + 1)]
+    gripper = ft.LINK_ID["right_gripper"]
+    guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
+    traj, status, _, _ = franka_follow(q_start, guide, cub, cyl, T=EXPERT_LENGTH)
+    return {"hybrid_solutions": traj, "hybrid_valid": expert_valid & (status == 0),
+            "hybrid_target_pose": frames_to_matrix(franka_fk(traj[:, -1].contiguous())[:, gripper])}
+
+
 _DATASET_KEYS = {"cuboid_dims": "cuboid_dims", "cuboid_centers": "cuboid_centers", "cuboid_quats": "cuboid_quaternions",
                  "cylinder_radii": "cylinder_radii", "cylinder_heights": "cylinder_heights",
                  "cylinder_centers": "cylinder_centers", "cylinder_quats": "cylinder_quaternions"}
 
 
-def problems_to_dataset(prob: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
+def problems_to_dataset(prob: Dict[str, torch.Tensor], trajectory_key: str = "global_solutions") -> Dict[str, np.ndarray]:
     """The ``expert_valid`` rows of ``make_problem_batch(collision_free=True, expert=True)`` under the HDF5 key names of
     the reference's dataset (``data.PointCloudTrajectoryDataset(mapping, "global_solutions", ...)`` reads them): float32
     numpy arrays ``cuboid_{dims,centers,quaternions}``, ``cylinder_{radii,heights,centers,quaternions}``,
-    ``global_solutions`` [N,50,7]."""
+    ``global_solutions`` [N,50,7].  ``trajectory_key="hybrid_solutions"`` (a batch made with ``hybrid=True``; the key the
+    reference's training job reads, jobconfig.yaml:28): the kept rows are ``hybrid_valid`` and both ``global_solutions``
+    and ``hybrid_solutions`` are written, as the reference's files hold both."""
+    if trajectory_key not in ("global_solutions", "hybrid_solutions"):
+        raise ValueError(f"trajectory_key must be 'global_solutions' or 'hybrid_solutions', got {trajectory_key!r}")
     assert "expert_valid" in prob, "problems_to_dataset needs make_problem_batch(collision_free=True, expert=True)"
-    keep = prob["expert_valid"]
+    hybrid = trajectory_key == "hybrid_solutions"
+    assert not hybrid or "hybrid_valid" in prob, "trajectory_key='hybrid_solutions' needs make_problem_batch(..., hybrid=True)"
+    keep = prob["hybrid_valid" if hybrid else "expert_valid"]
     out = {dst: prob[src][keep].detach().cpu().numpy().astype(np.float32) for src, dst in _DATASET_KEYS.items()}
     out["global_solutions"] = prob["global_solutions"][keep].detach().cpu().numpy().astype(np.float32)
+    if hybrid:
+        out["hybrid_solutions"] = prob["hybrid_solutions"][keep].detach().cpu().numpy().astype(np.float32)
     return out
 
 
@@ -325,7 +359,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        scene_pool: Optional[int] = None, device_clouds: bool = False, env_offset: int = 0,
                        total_envs: Optional[int] = None, collision_free: bool = False,
                        max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
-                       expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS) -> Dict[str, torch.Tensor]:
+                       expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False) -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -352,10 +386,22 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     ``FrankaCollisionSampler.check_cloud`` at that radius, which is not the primitive test.
     ``expert_from="roadmap"`` plans against the primitives with ``robot.franka_plan_global``: a lazy roadmap's path seeds one
     more candidate, so a problem whose straight line is blocked is not silently dropped; every row ``franka_plan`` solves
-    is returned as ``expert_from="primitives"`` returns it."""
+    is returned as ``expert_from="primitives"`` returns it.
+
+    ``hybrid`` (with ``expert``; default off, which leaves every key as it was): also ``hybrid_solutions`` [B,50,7], the
+    demonstration of ``solvers.franka_follow`` along eight right_gripper poses of ``global_solutions`` (a reactive follower
+    standing in for the reference's Geometric Fabrics expert, NOT Lula), retimed to constant speed and judged against the
+    primitives; ``hybrid_valid`` = ``expert_valid`` & followed and valid (bool [B]; the other rows are NaN); and
+    ``hybrid_target_pose`` [B,4,4], the pose the hybrid trajectory ends at (the reference's hindsight goal revision).
+    Refused with ``expert_from="cloud"``: the follower has no cloud form, and ``hybrid_valid`` would mix the cloud test of the
+    plan with the primitive test of the follower."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
+    assert expert or not hybrid, "hybrid trajectories follow the expert's: they need expert=True"
+    if hybrid and expert_from == "cloud":  # (the follower steers by and is judged against primitives: ``hybrid_valid`` would mix two tests)
+        raise ValueError("hybrid=True needs expert_from='primitives' or 'roadmap': the follower runs against the primitives, "
+                         "a plan judged against the point cloud is not what it would be judged by")
     if expert_from not in ("primitives", "cloud", "roadmap"):
         raise ValueError(f"expert_from must be 'primitives', 'cloud' or 'roadmap', got {expert_from!r}")
 
@@ -396,6 +442,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     target_pose = frames_to_matrix(franka_fk(q_target)[:, ft.LINK_ID["right_gripper"]])
     xyz[:, NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS:, :3] = sampler.sample_end_effector(target_pose, NUM_TARGET_POINTS)
     np.random.set_state(state)
+    if hybrid:
+        out.update(_hybrid_trajectories(out, q, out["global_solutions"], out["expert_valid"]))
     out.update(q=q, q_norm=(q - lim[:, 0]) / (lim[:, 1] - lim[:, 0]) * 2 - 1, xyz=xyz, target_pose=target_pose,
                target_position=target_pose[:, :3, 3].contiguous(), robot_subset=subset, env_offset=int(env_offset))
     return out

@@ -1,5 +1,5 @@
-"""The device solvers for the Franka: inverse kinematics, trajectory optimisation and the roadmap, against primitives or a
-point cloud (csrc/ik.hip, plan.hip, roadmap.hip, cloud_field.hip).  Each wrapper is its entry's argument list: the inputs
+"""The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap and the path follower, against
+primitives or a point cloud (csrc/ik.hip, plan.hip, roadmap.hip, follow.hip, cloud_field.hip).  Each wrapper is its entry's argument list: the inputs
 (``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
 outputs, in the header's order.  ``robot`` re-exports every name here."""
 from __future__ import annotations
@@ -36,6 +36,19 @@ ROADMAP_EDGE_UNTESTED, ROADMAP_EDGE_FREE, ROADMAP_EDGE_BLOCKED = 0, 1, 2  # ``ed
 ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.05, connect_radius=float("inf"), max_rounds=64, smooth_passes=8,
                         check_margin=1e-4, clearance=0.0, check_self=True)
 
+FOLLOW_VALID, FOLLOW_INVALID, FOLLOW_BAD_INPUT = 0, 1, 2  # status values of ``franka_follow``
+FOLLOW_BIT_MISS = 8  # MPX_FOLLOW_BIT_MISS, beside PLAN_BIT_ENV_HIT / PLAN_BIT_SELF_HIT / PLAN_BIT_JERK in ``bits``
+FOLLOW_MAX_STEPS = 4096  # MPX_FOLLOW_MAX_STEPS
+# MPX_FOLLOW_DEFAULT_* (include/mpinets_hip.h; profiles/follow_timing.md holds the runs behind them).  ``lambda_`` is the C
+# struct's ``lambda`` (``damping`` is the follower's viscous term, not the solve's)
+FOLLOW_DEFAULTS = dict(dt=0.005, max_steps=1024, attract=144.0, damping=24.0, lambda_=0.05, step_clip=0.5, repel=40.0,
+                       epsilon=0.05, clearance=0.0, limit_gain=50.0, limit_band=0.1, speed_limit=1.6999, switch_radius=0.15,
+                       switch_steps=100, final_radius=0.005, final_steps=800, substeps=4, check_margin=1e-4, max_jerk=0.15,
+                       check_self=True, miss_tol=0.05)
+
+# without ``return_path``, ``franka_follow`` runs a large batch in slabs of problems whose dense path and arc stay below this
+FOLLOW_PATH_BYTES = 512 << 20
+
 PLAN_CLOUD_SCRATCH_BYTES = 256 << 20  # ``franka_plan_cloud`` runs a large batch in slabs of problems whose scratch stays below this
 
 
@@ -54,6 +67,14 @@ def _plan_options(who: str, options: dict):
 def _roadmap_options(who: str, options: dict):
     """Keyword options of the roadmap over ``ROADMAP_DEFAULTS`` -> the ``_lib.RoadmapOptions`` and the merged dict."""
     return merge_options(who, _lib.RoadmapOptions, ROADMAP_DEFAULTS, options)
+
+
+def _follow_options(who: str, options: dict):
+    """Keyword options of the follower over ``FOLLOW_DEFAULTS`` -> the ``_lib.FollowOptions`` and the merged dict; ``lambda``
+    is accepted for ``lambda_``."""
+    if "lambda" in options:
+        options["lambda_"] = options.pop("lambda")
+    return merge_options(who, _lib.FollowOptions, FOLLOW_DEFAULTS, options)
 
 
 def _inputs(first: torch.Tensor, rows: tuple, second: Optional[torch.Tensor], limits, *others):
@@ -228,6 +249,76 @@ def franka_plan_global(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None
     out = franka_plan(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, return_all, limits, with_base_link, finger,
                       seeds=seed_traj[:, None], **options)
     return tuple(out) + (rm_status,)
+
+
+def franka_follow(q_start: torch.Tensor, poses: torch.Tensor, cuboids=None, cylinders=None, T: int = 50,
+                  v_init: Optional[torch.Tensor] = None, progress: Optional[torch.Tensor] = None, return_path: bool = False,
+                  return_state: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
+                  finger: float = ft.FINGER_OPENING, **options):
+    """Follow a path of end-effector poses with a reactive joint-space controller on the GPU, retime the dense path to ``T``
+    waypoints of constant arc-length spacing and judge them (csrc/follow.hip).  A STAND-IN for the Geometric Fabrics
+    expert of the reference's data generator (``gen_data.py:156-307``), NOT Lula and without any claim of parity with it:
+    a damped second-order system driven by ``franka_ik``'s damped-least-squares direction toward the current guide pose,
+    ``franka_plan``'s obstacle gradient, a joint-limit barrier and viscous damping under a joint speed limit.  No
+    randomness: row b depends on row b's inputs alone.
+
+    :param q_start: [B,7], inside ``limits`` and collision free.  A start that fails ``franka_plan``'s configuration test is
+        refused with status 2 ONLY when ``progress`` is None (a fresh rollout): whenever ``progress`` is given, an all-zero
+        one included, that test is skipped, because a continued rollout may stand where its dense path grazed an obstacle
+    :param poses: [B,W,4,4] right_gripper guide poses, 1 <= W <= 64, followed in order (switch inside ``switch_radius`` or
+        after ``switch_steps``; finished inside ``final_radius`` of the last or after ``final_steps`` on it)
+    :param cuboids, cylinders, limits: as for ``franka_plan``
+    :param v_init: [B,7] joint velocities (default: zeros); ``progress``: int32 [B,3] = (guide pose, steps spent on it,
+        finished flag) (default: zeros).  Pass the ``q_end``, ``v_end``, ``progress_end`` of ``return_state`` back in to
+        continue a rollout: the entry is then a controller stepped ``max_steps`` at a time.
+    :param options: the fields of ``mpx_follow_options``, see ``FOLLOW_DEFAULTS``
+    :returns: ``traj`` [B,T,7] (NaN rows where ``status`` != 0), ``status`` int32 [B] (0 valid, 1 followed but ``bits`` != 0,
+        2 bad input: no steps, bits 15), ``bits`` int32 [B] (``PLAN_BIT_ENV_HIT``, ``PLAN_BIT_SELF_HIT``, ``PLAN_BIT_JERK``,
+        ``FOLLOW_BIT_MISS``) and ``steps`` int32 [B]; with ``return_path`` also ``traj_any`` [B,T,7] (the status-1 rows
+        too), ``path`` [B,max_steps+1,7] and ``arc`` [B,max_steps+1] (rows 0 .. ``steps`` are written, the rest is not);
+        with ``return_state`` then ``q_end``, ``v_end`` [B,7] and ``progress_end`` int32 [B,3].  The entry writes the dense
+        path whether or not it is returned (32 (max_steps + 1) bytes a problem: 33 kB with the defaults).  With
+        ``return_path`` all of it is allocated, 269 MB at B = 8192; without, the batch runs in slabs of problems that
+        share one buffer of at most ``FOLLOW_PATH_BYTES`` (rows do not depend on one another: the result is the same)."""
+    _lib.require_cuda(poses, v_init, progress)
+    assert poses.ndim == 4 and tuple(poses.shape[2:]) == (4, 4) and poses.size(0) == q_start.size(0)
+    B, dev, qs, vi, lim = _inputs(q_start, (7,), v_init, limits)
+    copt, o = _follow_options("franka_follow", options)
+    W, rows = poses.size(1), min(max(int(o["max_steps"]), 0), FOLLOW_MAX_STEPS) + 1  # (out of range: the call refuses)
+    ps = _lib.f32c(poses)
+    pg = None
+    if progress is not None:
+        assert progress.shape == (B, 3)
+        pg = _lib.i32c(progress)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+
+    def f32(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    def i32(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+
+    slab = max(B, 1) if return_path else max(1, min(max(B, 1), FOLLOW_PATH_BYTES // (32 * rows)))
+    path, arc = f32(B if return_path else min(B, slab), rows, 7), f32(B if return_path else min(B, slab), rows)
+    traj, status, bits, steps = f32(B, T, 7), i32(B), i32(B), i32(B)
+    traj_any = f32(B, T, 7) if return_path else None
+    state = (f32(B, 7), f32(B, 7), i32(B, 3)) if return_state else (None, None, None)
+    M1, M2 = prims[6], prims[10]
+    prim_rows = (0, 0, 0, None, M1 * 16, M1 * 3, None, M2 * 16, M2, M2, None)  # floats per problem behind each pointer
+    for b0 in range(0, max(B, 1), slab):
+
+        def at(p, row):  # row b0 of a [B, ...] operand of 4-byte elements, by its address
+            return p if p is None or row is None else p + 4 * b0 * row
+
+        outs = zip(_ptrs((path, arc, status, bits, steps, traj, traj_any) + state),
+                   (rows * 7 if return_path else 0, rows if return_path else 0, 1, 1, 1, T * 7, T * 7, 7, 7, 3))
+        _lib.call("mpx_franka_follow", at(qs.data_ptr(), 7), at(ps.data_ptr(), W * 16), min(slab, B - b0), W, int(T), float(finger),
+                  lim.data_ptr(), *(at(p, row) for p, row in zip(prims, prim_rows)), at(_lib.ptr(vi), 7), at(_lib.ptr(pg), 3),
+                  ctypes.byref(copt), *(at(p, row) for p, row in outs))
+    out = (traj, status, bits, steps)
+    if return_path:
+        out += (traj_any, path, arc)
+    return out + state if return_state else out
 
 
 def plan_cloud_truncation(point_radius: float = 0.0, clearance: float = 0.0, epsilon: float = PLAN_DEFAULTS["epsilon"],
