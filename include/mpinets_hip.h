@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_follow,
+int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_gripper_roadmap,
+                          struct mpx_gripper_roadmap_options; 341 (unchanged, likewise): mpx_franka_follow,
                           struct mpx_follow_options; 341 (unchanged, likewise): mpx_franka_roadmap,
                           struct mpx_roadmap_options, mpx_franka_plan_seeded;
                           341: the route queries mpx_fps_route, mpx_franka_collision_route, mpx_linear_route, mpx_linear_wgrad_route,
@@ -491,6 +492,85 @@ int mpx_franka_follow(const float *q_start, const float *poses, int B, int W, in
                       const int32_t *progress_init, const mpx_follow_options *options, float *path, float *arc,
                       int32_t *status, int32_t *bits, int32_t *steps, float *traj, float *traj_any, float *q_end,
                       float *v_end, int32_t *progress_end, mpx_stream_t stream);
+
+/* A lazy probabilistic roadmap per problem for the FREE-FLYING GRIPPER in SE(3): where the reference's data generator plans
+ * the end effector through the scene before it hands the pose path to the fabric (data_pipeline/gen_data.py:156-189,
+ * plan_end_effector).  A STAND-IN for that OMPL planner, NOT a port of it and with no claim of parity with AIT*; "valid"
+ * means free by this engine's sphere model, not by PyBullet's meshes.  One workgroup per problem; the result depends on the
+ * inputs alone.  Its poses are an operand of mpx_franka_follow.
+ *   start_pose, goal_pose [B,4,4] row-major right_gripper poses (mpx_franka_ik's targets; rows 0-2 are read); bounds
+ *   [B,2,3] = lo, hi of the position box of each problem; the sphere table and the primitives exactly as for
+ *   mpx_franka_roadmap (S <= 64, M1, M2 <= 64, zero-volume rows skipped).
+ *   The gripper.  The rows of the sphere table with link id 9, 12 or 13 (panda_hand and the two fingertips; 20 of the standard
+ *   56), the others are ignored.  From a right_gripper pose (R, p) a sphere centre c of link 9 has the hand-frame point
+ *   h = c, of link 12 h = c + (0, finger, 0.0584f + 0.045f), of link 13 h = c + (0, -finger, 0.0584f + 0.045f); it sits at
+ *   R (-h_x, -h_y, h_z - 0.1f) + p, the product as fma(R_i2, g_z, fma(R_i1, g_y, R_i0 g_x)) + p_i (mpx_franka_fk's fixed
+ *   transforms from the hand to right_gripper, inverted).  R of a unit quaternion (x, y, z, w): R_00 = 1 - 2 (yy + zz),
+ *   R_01 = 2 (xy - wz), R_02 = 2 (xz + wy), R_10 = 2 (xy + wz), R_11 = 1 - 2 (xx + zz), R_12 = 2 (yz - wx),
+ *   R_20 = 2 (xz - wy), R_21 = 2 (yz + wx), R_22 = 1 - 2 (xx + yy), every product and sum rounded on its own.
+ *   A pose is VALID by the planner's clause: no gripper sphere with sdf <= r_s + clearance + check_margin (the minimum over
+ *   the live primitives; with S = 0 or no live primitive this test passes), and with check_self none of the origins of
+ *   frames 9, 12, 13 -- R (0, 0, -0.1f) + p and R (0, -+finger, (0.0584f + 0.045f) - 0.1f) + p -- inside
+ *   0.15 + 0.01 + check_margin of the base segment (mpx_franka_plan's self test on those frames).
+ *   Nodes.  V = options->nodes, 2 <= V <= MPX_ROADMAP_MAX_NODES; a node is (p, q): position and unit quaternion (x, y, z, w).
+ *   Node 0 is start_pose, node 1 goal_pose: p the last column, q by Shepperd's method -- with t = R_00 + R_11 + R_22 the
+ *   branch is the first of (t, R_00, R_11, R_22) that is >= the other three; branch t: s = 2 sqrtf(1 + t), w = s / 4,
+ *   x = (R_21 - R_12) / s, y = (R_02 - R_20) / s, z = (R_10 - R_01) / s; branch R_00: s = 2 sqrtf(1 + R_00 - R_11 - R_22),
+ *   x = s / 4, w = (R_21 - R_12) / s, y = (R_01 + R_10) / s, z = (R_02 + R_20) / s; R_11 and R_22 by cyclic exchange -- then
+ *   divided by its norm.  Node v >= 2: words 0-7 = Philox4x32-10(counter = {2v, GLOBAL problem id = env_offset + b,
+ *   stream 17, 0}, key = seed) followed by the block with counter word 0 = 2v + 1, u_i = u01 of word i;
+ *   p_k = fma(u_k, hi_k - lo_k, lo_k), k = 0..2; with sigma = +1 when dot(q_start, q_goal) >= 0, else -1,
+ *   m_k = fma(u_3, sigma q_goal,k - q_start,k, q_start,k), raw_k = fma(orient_spread, fma(2, u_{4+k}, -1), m_k),
+ *   q = raw / sqrtf(|raw|^2): orientations scatter about the start-goal arc (orient_spread = 0 puts them on it), they are
+ *   NOT uniform on SO(3).  A drawn node with |raw|^2 < 2^-20 is invalid.  Every 4-vector dot and squared norm is
+ *   fma(a_3, b_3, fma(a_2, b_2, fma(a_1, b_1, a_0 b_0))).
+ *   status int32 [B]: 2 an endpoint pose has a non-finite entry in rows 0-2, lies outside bounds (NaN bounds fail) or is
+ *   invalid (no search is done, rounds = 0); 0 a path was found; 1 none was.
+ *   Edge (a,b), a < b, sigma_ab the sign of dot(q_a, q_b) as above:
+ *   w = sqrtf(fma((2 rot_weight)^2, |q_b - sigma_ab q_a|^2, |p_b - p_a|^2)), each squared norm summed k ascending, the
+ *   first square rounded on its own and the others fused, (2 rot_weight)^2 = (2 rot_weight) (2 rot_weight) in float32 (the
+ *   same bits for (b,a)).  2 |q_a - sigma q_b| = 4 sin(theta / 4) ~ theta for a relative rotation theta: with rot_weight the
+ *   largest lever arm of a sphere centre about the gripper origin (0.1172 m; default 0.12), w bounds how far any centre
+ *   moves along the edge.  n = min(2^20, max(1, (int)ceilf(w / resolution))) pieces; interior pose i = 1 .. n-1 with
+ *   f = (float)i / (float)n: p = fma(f, p_b - p_a, p_a), q = raw / sqrtf(|raw|^2), raw_k = fma(f, sigma_ab q_b,k - q_a,k,
+ *   q_a,k) (nlerp).  The edge is BLOCKED exactly when an interior pose is invalid; an edge with w > connect_radius does not
+ *   exist.
+ *   Search: mpx_franka_roadmap's, statement for statement (Jacobi sweeps to a fixed point, u ascending with a strict "<",
+ *   the untested edges of the round's path tested in full, at most max_rounds rounds), and its outputs path int32 [B,V],
+ *   hops int32 [B], optional nodes [B,V,7] (p, then q), edge_state uint8 [B,V,V] (0 untested / 1 free / 2 blocked, the
+ *   diagonal 1 for a valid node and 2 for an invalid one), rounds int32 [B].
+ *   poses [B,W,4,4], 1 <= W <= MPX_FOLLOW_MAX_POSES: the start is not among them (the follower starts there).  With c_0 = 0,
+ *   c_{i+1} = c_i + w_i summed in path order in float32 and s_t = ((float)(t+1) / (float)W) c_hops, pose t < W-1 lies on
+ *   the last edge i with c_i <= s_t at f = min((s_t - c_i) / w_i, 1) (0 if w_i = 0), by the edge's nlerp taken in PATH
+ *   order (from path node i toward i+1); rows 0-2 are [R | p] of that (p, q), R as above.  Rows 0-2 of pose W-1 are
+ *   goal_pose's bit for bit.  Row 3 of every pose is (0, 0, 0, 1).  No smoothing: the follower switches poses inside its
+ *   switch radius.  Rows with status != 0 are NaN (all 16 entries).
+ *   No allocation, no scratch, no global atomics; everything is enqueued on `stream` (capturable).  B == 0 launches
+ *   nothing.                                                                                                            */
+#define MPX_GRIPPER_ROADMAP_DEFAULT_NODES 64
+#define MPX_GRIPPER_ROADMAP_DEFAULT_RESOLUTION 0.01f   /* the smallest gripper sphere has radius 0.0108 */
+#define MPX_GRIPPER_ROADMAP_DEFAULT_ROT_WEIGHT 0.12f   /* the lever arm 0.1172 m, rounded up            */
+#define MPX_GRIPPER_ROADMAP_DEFAULT_ORIENT_SPREAD 0.5f
+#define MPX_GRIPPER_ROADMAP_DEFAULT_MAX_ROUNDS 256     /* a round is cheap: 20 spheres per pose (profiles/gripper_roadmap_timing.md) */
+typedef struct mpx_gripper_roadmap_options { /* NULL options: the defaults above, connect_radius +inf, check_margin
+                                                MPX_PLAN_DEFAULT_CHECK_MARGIN, clearance 0, check_self 1 */
+  int nodes;                                 /* 2 .. MPX_ROADMAP_MAX_NODES, start and goal included       */
+  float resolution;                          /* > 0 [m]: the longest piece of an edge (the metric w)      */
+  float rot_weight;                          /* > 0 [m/rad]: what a radian of rotation counts in w        */
+  float orient_spread;                       /* >= 0: scatter of the drawn quaternions about the arc      */
+  float connect_radius;                      /* [m], longer edges do not exist; +inf: the complete graph  */
+  int max_rounds;                            /* >= 1: searches before giving up                           */
+  float check_margin;                        /* >= 0 [m], as in mpx_plan_options                          */
+  float clearance;                           /* [m], added to the radii                                   */
+  int check_self;                            /* non-zero: the body column invalidates a pose              */
+} mpx_gripper_roadmap_options;
+int mpx_gripper_roadmap(const float *start_pose, const float *goal_pose, int B, int W, const float *bounds, float finger,
+                        const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                        const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                        const float *cyl_radii, const float *cyl_heights, int M2,
+                        const mpx_gripper_roadmap_options *options, uint64_t seed, int64_t env_offset, float *poses,
+                        int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state, int32_t *rounds,
+                        mpx_stream_t stream);
 
 /* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
  * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at

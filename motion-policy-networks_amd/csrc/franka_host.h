@@ -1,5 +1,5 @@
 // franka_host.h -- host-only (no __device__ code): the option defaults, the argument checks and the cloud launch table that
-// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, follow.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
+// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, follow.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
 // env_offset and scratch size); a new entry takes its defaults and its checks from here, and states a refusal of its own only
 // where no other entry has it.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
 // returns 0 or 1 (field_grid_check's idiom).  Sizes and values are checked before an entry's "nothing to do" return, pointers after.
@@ -24,6 +24,11 @@ static inline mpx_plan_options franka_plan_defaults() {
 static inline mpx_roadmap_options franka_roadmap_defaults() {
   return {MPX_ROADMAP_DEFAULT_NODES, MPX_ROADMAP_DEFAULT_RESOLUTION, __builtin_inff(), MPX_ROADMAP_DEFAULT_MAX_ROUNDS,
           MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
+}
+static inline mpx_gripper_roadmap_options gripper_roadmap_defaults() {
+  return {MPX_GRIPPER_ROADMAP_DEFAULT_NODES, MPX_GRIPPER_ROADMAP_DEFAULT_RESOLUTION, MPX_GRIPPER_ROADMAP_DEFAULT_ROT_WEIGHT,
+          MPX_GRIPPER_ROADMAP_DEFAULT_ORIENT_SPREAD, __builtin_inff(), MPX_GRIPPER_ROADMAP_DEFAULT_MAX_ROUNDS,
+          MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
 }
 static inline mpx_follow_options franka_follow_defaults() {
   return {MPX_FOLLOW_DEFAULT_DT, MPX_FOLLOW_DEFAULT_MAX_STEPS, MPX_FOLLOW_DEFAULT_ATTRACT, MPX_FOLLOW_DEFAULT_DAMPING,
@@ -92,6 +97,21 @@ static inline int franka_roadmap_options_check(const char *who, int T, const mpx
   MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
   MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
   MPX_REQUIRE(opt.smooth_passes >= 0, "%s: smooth_passes = %d, need >= 0", who, opt.smooth_passes);
+  MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
+  return 0;
+}
+// (W: the guide poses it writes are mpx_franka_follow's operand, so its range is the follower's)
+static inline int gripper_roadmap_options_check(const char *who, int W, const mpx_gripper_roadmap_options &opt) {
+  MPX_REQUIRE(W >= 1 && W <= MPX_FOLLOW_MAX_POSES, "%s: W = %d guide poses, need 1 .. %d (one thread each)", who, W,
+              MPX_FOLLOW_MAX_POSES);
+  MPX_REQUIRE(opt.nodes >= 2 && opt.nodes <= MPX_ROADMAP_MAX_NODES, "%s: nodes = %d, need 2 .. %d (one thread each)", who,
+              opt.nodes, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
+  MPX_REQUIRE(opt.rot_weight > 0.0f && opt.rot_weight < __builtin_inff(), "%s: rot_weight must be > 0 and finite", who);
+  MPX_REQUIRE(opt.orient_spread >= 0.0f && opt.orient_spread < __builtin_inff(), "%s: orient_spread must be >= 0 and finite", who);
+  MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
+  MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
   MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
   MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
   return 0;

@@ -11,14 +11,13 @@
 // concatenated untested edges of the round's path (the planner's validity-sweep mapping, in passes of 256), thread = waypoint
 // (resampling and the corner filter: T <= 64).  The path walk and the prefix sums over its <= V - 1 edges are serial on
 // thread 0.  Every branch around a barrier is workgroup-uniform: it reads a value from LDS behind a barrier, or a barrier's
-// own reduction.
+// own reduction.  The search itself is roadmap_search.inc, shared with gripper_roadmap.hip (the gripper's roadmap in SE(3)).
 #include "common.h"
 #include "franka_host.h"
 #include "plan_prims_device.h"
+#include "roadmap_device.h"
 
 enum { STREAM_ROADMAP = 16 };
-enum { ROADMAP_THREADS = 256, ROADMAP_MAX_PIECES = 1 << 20 };
-enum { ROADMAP_UNTESTED = 0, ROADMAP_FREE = 1, ROADMAP_BLOCKED = 2 };
 
 // LDS, in 4-byte words: [128 primitive rows x 16 | nodes V x 7 | dist 2 x V (later: cumulative and edge lengths) |
 // two trajectories 64 x 7 | pred, path, rev, pieces, blocked, valid: V ints each | first V + 1 | hops | edge bits]
@@ -37,21 +36,6 @@ __device__ __forceinline__ float roadmap_length(const float *qa, const float *qb
     acc = j == 0 ? d * d : mpx_fma(d, d, acc);
   }
   return sqrtf(acc);
-}
-__device__ __forceinline__ int roadmap_pieces(float w, float resolution) {
-  const float n = ceilf(w / resolution);
-  return n >= (float)ROADMAP_MAX_PIECES ? ROADMAP_MAX_PIECES : n >= 1.0f ? (int)n : 1;
-}
-
-// 2 bits per pair, at bit 2 (lo V + hi) for lo < hi
-__device__ __forceinline__ int roadmap_edge_get(const unsigned *bits, int V, int a, int b) {
-  const int idx = (a < b ? a : b) * V + (a < b ? b : a);
-  return (int)((bits[idx >> 4] >> ((idx & 15) * 2)) & 3u);
-}
-// (from ROADMAP_UNTESTED only: an OR sets the state, whichever lanes share the word)
-__device__ __forceinline__ void roadmap_edge_set(unsigned *bits, int V, int a, int b, int state) {
-  const int idx = (a < b ? a : b) * V + (a < b ? b : a);
-  atomicOr(&bits[idx >> 4], (unsigned)state << ((idx & 15) * 2));
 }
 
 __global__ void __launch_bounds__(ROADMAP_THREADS)
@@ -113,79 +97,15 @@ __global__ void __launch_bounds__(ROADMAP_THREADS)
   __syncthreads();
 
   // ---- the lazy search -----------------------------------------------------------------------------------------------------------
-  int st = (valid[0] && valid[1]) ? 1 : 2, rounds = 0, hops = 0;
-  for (int round = 0; st == 1 && round < opt.max_rounds; ++round) {
-    rounds = round + 1;
-    if (tid < V) dist[tid] = tid == 0 ? 0.0f : inf, pred[tid] = -1;
-    __syncthreads();
-    int cur = 0;
-    for (int sweep = 0; sweep < V; ++sweep) {  // (Jacobi: a sweep reads dist[cur], writes the other half; V - 1 suffice)
-      const float *dp = dist + cur * V;
-      int changed = 0;
-      if (tid < V) {
-        float best = dp[tid];
-        int bp = pred[tid];
-        if (tid != 0 && valid[tid]) {
-          for (int u = 0; u < V; ++u) {
-            const float du = dp[u];
-            if (u == tid || !(du < inf) || roadmap_edge_get(ebits, V, u, tid) == ROADMAP_BLOCKED) continue;
-            const float w = roadmap_length(nodes + u * 7, mine);
-            if (w > opt.connect_radius) continue;
-            const float cand = du + w;
-            if (cand < best) best = cand, bp = u;
-          }
-        }
-        changed = best < dp[tid];
-        dist[(cur ^ 1) * V + tid] = best, pred[tid] = bp;
-      }
-      cur ^= 1;
-      if (!__syncthreads_or(changed)) break;
-    }
-    if (!(dist[cur * V + 1] < inf)) break;  // the goal cannot be reached over what is not blocked
-
-    // the path, and where each of its untested edges starts among this round's tests
-    if (tid == 0) {
-      int n = 0, v = 1;
-      for (; v > 0 && n < V; v = pred[v]) rev[n++] = v;
-      if (v != 0) n = 0;  // (a finite distance has a chain of predecessors down to node 0: never taken)
-      path[0] = 0;
-      first[0] = 0;
-      for (int i = 0; i < n; ++i) {
-        path[i + 1] = rev[n - 1 - i];
-        const int a = path[i] < path[i + 1] ? path[i] : path[i + 1], c = path[i] < path[i + 1] ? path[i + 1] : path[i];
-        pieces[i] = roadmap_pieces(roadmap_length(nodes + a * 7, nodes + c * 7), opt.resolution);
-        first[i + 1] = first[i] + (roadmap_edge_get(ebits, V, a, c) == ROADMAP_UNTESTED ? pieces[i] - 1 : 0);
-        blocked[i] = 0;
-      }
-      *hops_lds = n;
-    }
-    __syncthreads();
-    hops = *hops_lds;
-    if (hops == 0) break;
-    const int total = first[hops];
-    for (int c = tid; c < total; c += ROADMAP_THREADS) {  // thread = interior configuration
-      int i = 0, top = hops;                              // the last edge with first[i] <= c
-      while (top - i > 1) {
-        const int mid = (i + top) >> 1;
-        if (first[mid] <= c) i = mid; else top = mid;
-      }
-      const int a = path[i] < path[i + 1] ? path[i] : path[i + 1], e = path[i] < path[i + 1] ? path[i + 1] : path[i];
-      const float f = (float)(c - first[i] + 1) / (float)pieces[i];
-      float q[7];
-#pragma unroll
-      for (int j = 0; j < 7; ++j) q[j] = mpx_fma(f, nodes[e * 7 + j] - nodes[a * 7 + j], nodes[a * 7 + j]);
-      if (plan_config_bits(q, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin))
-        blocked[i] = 1;  // (every lane that stores, stores 1)
-    }
-    __syncthreads();
-    int hit = 0;
-    if (tid < hops && roadmap_edge_get(ebits, V, path[tid], path[tid + 1]) == ROADMAP_UNTESTED) {
-      hit = blocked[tid];
-      roadmap_edge_set(ebits, V, path[tid], path[tid + 1], hit ? ROADMAP_BLOCKED : ROADMAP_FREE);
-    }
-    if (!__syncthreads_or(hit)) st = 0;
-  }
-  if (st != 0) hops = 0;
+#define ROADMAP_SEARCH_LENGTH(a, b) roadmap_length(a, b)
+#define ROADMAP_SEARCH_POINT(a, e, f, q) \
+  _Pragma("unroll") for (int j = 0; j < 7; ++j) q[j] = mpx_fma(f, nodes[e * 7 + j] - nodes[a * 7 + j], nodes[a * 7 + j]);
+#define ROADMAP_SEARCH_HIT(q) \
+  plan_config_bits(q, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin)
+#include "roadmap_search.inc"
+#undef ROADMAP_SEARCH_LENGTH
+#undef ROADMAP_SEARCH_POINT
+#undef ROADMAP_SEARCH_HIT
 
   // ---- what the search found -----------------------------------------------------------------------------------------------------
   if (tid == 0) {

@@ -1,0 +1,23 @@
+// roadmap_device.h -- what the roadmap kernels share besides the search itself (roadmap_search.inc): the workgroup size, the
+// edge states and their 2-bit store in LDS, the pieces of an edge.  roadmap.hip (joint space) and gripper_roadmap.hip (SE(3)).
+#pragma once
+#include "common.h"
+
+enum { ROADMAP_THREADS = 256, ROADMAP_MAX_PIECES = 1 << 20 };
+enum { ROADMAP_UNTESTED = 0, ROADMAP_FREE = 1, ROADMAP_BLOCKED = 2 };
+
+__device__ __forceinline__ int roadmap_pieces(float w, float resolution) {
+  const float n = ceilf(w / resolution);
+  return n >= (float)ROADMAP_MAX_PIECES ? ROADMAP_MAX_PIECES : n >= 1.0f ? (int)n : 1;
+}
+
+// 2 bits per pair, at bit 2 (lo V + hi) for lo < hi
+__device__ __forceinline__ int roadmap_edge_get(const unsigned *bits, int V, int a, int b) {
+  const int idx = (a < b ? a : b) * V + (a < b ? b : a);
+  return (int)((bits[idx >> 4] >> ((idx & 15) * 2)) & 3u);
+}
+// (from ROADMAP_UNTESTED only: an OR sets the state, whichever lanes share the word)
+__device__ __forceinline__ void roadmap_edge_set(unsigned *bits, int V, int a, int b, int state) {
+  const int idx = (a < b ? a : b) * V + (a < b ? b : a);
+  atomicOr(&bits[idx >> 4], (unsigned)state << ((idx & 15) * 2));
+}

@@ -44,6 +44,7 @@ PROTOTYPES = {
     "mpx_franka_plan_seeded": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, I, P, P, P, P, P, P],
     "mpx_franka_roadmap": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_franka_follow": [P, P, I, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "mpx_gripper_roadmap": [P, P, I, I, P, F, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
     "mpx_franka_plan_cloud_scratch": [I, I, I, I],
@@ -152,6 +153,13 @@ class RoadmapOptions(ctypes.Structure):
     """``mpx_roadmap_options`` (include/mpinets_hip.h); the defaults are the header's MPX_ROADMAP_DEFAULT_*."""
     _fields_ = [("nodes", c_int), ("resolution", c_float), ("connect_radius", c_float), ("max_rounds", c_int),
                 ("smooth_passes", c_int), ("check_margin", c_float), ("clearance", c_float), ("check_self", c_int)]
+
+
+class GripperRoadmapOptions(ctypes.Structure):
+    """``mpx_gripper_roadmap_options`` (include/mpinets_hip.h); the defaults are the header's MPX_GRIPPER_ROADMAP_DEFAULT_*."""
+    _fields_ = [("nodes", c_int), ("resolution", c_float), ("rot_weight", c_float), ("orient_spread", c_float),
+                ("connect_radius", c_float), ("max_rounds", c_int), ("check_margin", c_float), ("clearance", c_float),
+                ("check_self", c_int)]
 
 
 class FollowOptions(ctypes.Structure):

@@ -308,15 +308,22 @@ HYBRID_GUIDE_POSES = 8  # guide poses handed to the follower: waypoints round(i 
 
 
 def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, global_solutions: torch.Tensor,
-                         expert_valid: torch.Tensor) -> Dict[str, torch.Tensor]:
+                         expert_valid: torch.Tensor, q_goal: Optional[torch.Tensor] = None, seed: int = 0,
+                         env_offset: int = 0, gripper_guide: bool = False) -> Dict[str, torch.Tensor]:
     """``hybrid=True``: the global plan steers, the follower produces.  ``solvers.franka_follow`` (a stand-in for the
     reference's Geometric Fabrics expert, NOT Lula: gen_data.py:156-307) follows the right_gripper poses of eight waypoints
     of ``global_solutions``, its dense path is retimed to 50 waypoints and judged; the target becomes the pose the
     trajectory actually ends at (hindsight goal revision, gen_data.py:303-306).  Rows without a global solution hand NaN
-    poses to the follower and come back with status 2."""
+    poses to the follower and come back with status 2.
+
+    ``gripper_guide`` (``hybrid_guide="gripper"``): the guide is not read off the global plan but planned for the free-flying
+    gripper through the same primitives by ``solvers.gripper_roadmap`` (a stand-in for the reference's OMPL end-effector
+    planner, gen_data.py:156-189, NOT a port of it), from the right_gripper pose of ``q_start`` to that of ``q_goal``, keyed
+    by the batch's ``seed`` / ``env_offset``.  There is no fall-back to the global guide: a row without a gripper path hands
+    NaN poses to the follower (the reference drops such rows too: "end effector path")."""
     from .geometry import TorchCuboids, TorchCylinders
     from .robot import franka_fk, frames_to_matrix
-    from .solvers import franka_follow
+    from .solvers import franka_follow, gripper_roadmap
 
     cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
     cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
@@ -324,10 +331,17 @@ def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
     B = q_start.size(0)
     at = [int(round(i * (EXPERT_LENGTH - 1) / HYBRID_GUIDE_POSES)) for i in range(1, HYBRID_GUIDE_POSES + 1)]
     gripper = ft.LINK_ID["right_gripper"]
-    guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
+    extra = {}
+    if gripper_guide:
+        ends = frames_to_matrix(franka_fk(torch.cat([q_start, q_goal]))[:, gripper])  # (an invalid row's NaN goal: status 2)
+        guide, guide_status = gripper_roadmap(ends[:B].contiguous(), ends[B:].contiguous(), cub, cyl, W=HYBRID_GUIDE_POSES,
+                                              seed=seed, env_offset=env_offset)
+        extra = {"hybrid_guide_poses": guide, "hybrid_guide_status": guide_status}
+    else:
+        guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
     traj, status, _, _ = franka_follow(q_start, guide, cub, cyl, T=EXPERT_LENGTH)
-    return {"hybrid_solutions": traj, "hybrid_valid": expert_valid & (status == 0),
-            "hybrid_target_pose": frames_to_matrix(franka_fk(traj[:, -1].contiguous())[:, gripper])}
+    return dict(extra, hybrid_solutions=traj, hybrid_valid=expert_valid & (status == 0),
+                hybrid_target_pose=frames_to_matrix(franka_fk(traj[:, -1].contiguous())[:, gripper]))
 
 
 _DATASET_KEYS = {"cuboid_dims": "cuboid_dims", "cuboid_centers": "cuboid_centers", "cuboid_quats": "cuboid_quaternions",
@@ -359,7 +373,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        scene_pool: Optional[int] = None, device_clouds: bool = False, env_offset: int = 0,
                        total_envs: Optional[int] = None, collision_free: bool = False,
                        max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
-                       expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False) -> Dict[str, torch.Tensor]:
+                       expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False,
+                       hybrid_guide: str = "global") -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -394,7 +409,16 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     primitives; ``hybrid_valid`` = ``expert_valid`` & followed and valid (bool [B]; the other rows are NaN); and
     ``hybrid_target_pose`` [B,4,4], the pose the hybrid trajectory ends at (the reference's hindsight goal revision).
     Refused with ``expert_from="cloud"``: the follower has no cloud form, and ``hybrid_valid`` would mix the cloud test of the
-    plan with the primitive test of the follower."""
+    plan with the primitive test of the follower.
+
+    ``hybrid_guide`` (with ``hybrid``; default "global", which leaves every key and every bit as it was): "gripper" takes the
+    follower's guide not from ``global_solutions`` but from ``solvers.gripper_roadmap``, a roadmap planner for the
+    free-flying gripper in SE(3) from the right_gripper pose of ``q`` to that of ``q_goal`` through the same primitives, at
+    eight poses, keyed by ``seed`` / ``env_offset`` so that shards agree -- the stage the reference runs before its fabric
+    (gen_data.py:156-189); a stand-in for that OMPL planner, not a port, valid by this engine's sphere model.  No fall-back
+    between the guides: a row without a gripper path is not ``hybrid_valid``, which still requires ``expert_valid`` as the
+    reference requires the global plan.  Also ``hybrid_guide_poses`` [B,8,4,4] (NaN rows without a path) and
+    ``hybrid_guide_status`` int32 [B] (``gripper_roadmap``'s)."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
@@ -402,6 +426,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if hybrid and expert_from == "cloud":  # (the follower steers by and is judged against primitives: ``hybrid_valid`` would mix two tests)
         raise ValueError("hybrid=True needs expert_from='primitives' or 'roadmap': the follower runs against the primitives, "
                          "a plan judged against the point cloud is not what it would be judged by")
+    if hybrid_guide not in ("global", "gripper"):
+        raise ValueError(f"hybrid_guide must be 'global' or 'gripper', got {hybrid_guide!r}")
     if expert_from not in ("primitives", "cloud", "roadmap"):
         raise ValueError(f"expert_from must be 'primitives', 'cloud' or 'roadmap', got {expert_from!r}")
 
@@ -443,7 +469,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     xyz[:, NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS:, :3] = sampler.sample_end_effector(target_pose, NUM_TARGET_POINTS)
     np.random.set_state(state)
     if hybrid:
-        out.update(_hybrid_trajectories(out, q, out["global_solutions"], out["expert_valid"]))
+        out.update(_hybrid_trajectories(out, q, out["global_solutions"], out["expert_valid"], q_goal, seed, env_offset,
+                                        gripper_guide=hybrid_guide == "gripper"))
     out.update(q=q, q_norm=(q - lim[:, 0]) / (lim[:, 1] - lim[:, 0]) * 2 - 1, xyz=xyz, target_pose=target_pose,
                target_position=target_pose[:, :3, 3].contiguous(), robot_subset=subset, env_offset=int(env_offset))
     return out

@@ -1,5 +1,6 @@
-"""The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap and the path follower, against
-primitives or a point cloud (csrc/ik.hip, plan.hip, roadmap.hip, follow.hip, cloud_field.hip).  Each wrapper is its entry's argument list: the inputs
+"""The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap, the gripper's SE(3) roadmap and
+the path follower, against primitives or a point cloud (csrc/ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, follow.hip,
+cloud_field.hip).  Each wrapper is its entry's argument list: the inputs
 (``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
 outputs, in the header's order.  ``robot`` re-exports every name here."""
 from __future__ import annotations
@@ -36,6 +37,12 @@ ROADMAP_EDGE_UNTESTED, ROADMAP_EDGE_FREE, ROADMAP_EDGE_BLOCKED = 0, 1, 2  # ``ed
 ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.05, connect_radius=float("inf"), max_rounds=64, smooth_passes=8,
                         check_margin=1e-4, clearance=0.0, check_self=True)
 
+# MPX_GRIPPER_ROADMAP_DEFAULT_* (include/mpinets_hip.h; profiles/gripper_roadmap_timing.md holds the runs behind them); the
+# status and ``edge_state`` values are the roadmap's (``ROADMAP_FOUND`` ...)
+GRIPPER_ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.01, rot_weight=0.12, orient_spread=0.5, connect_radius=float("inf"),
+                                max_rounds=256, check_margin=1e-4, clearance=0.0, check_self=True)
+GRIPPER_ROADMAP_BOUNDS_PAD = 0.3  # [m] ``bounds=None``: the box hull of the two positions, grown by this much per side
+
 FOLLOW_VALID, FOLLOW_INVALID, FOLLOW_BAD_INPUT = 0, 1, 2  # status values of ``franka_follow``
 FOLLOW_BIT_MISS = 8  # MPX_FOLLOW_BIT_MISS, beside PLAN_BIT_ENV_HIT / PLAN_BIT_SELF_HIT / PLAN_BIT_JERK in ``bits``
 FOLLOW_MAX_STEPS = 4096  # MPX_FOLLOW_MAX_STEPS
@@ -67,6 +74,12 @@ def _plan_options(who: str, options: dict):
 def _roadmap_options(who: str, options: dict):
     """Keyword options of the roadmap over ``ROADMAP_DEFAULTS`` -> the ``_lib.RoadmapOptions`` and the merged dict."""
     return merge_options(who, _lib.RoadmapOptions, ROADMAP_DEFAULTS, options)
+
+
+def _gripper_roadmap_options(who: str, options: dict):
+    """Keyword options of the gripper roadmap over ``GRIPPER_ROADMAP_DEFAULTS`` -> the ``_lib.GripperRoadmapOptions`` and the
+    merged dict."""
+    return merge_options(who, _lib.GripperRoadmapOptions, GRIPPER_ROADMAP_DEFAULTS, options)
 
 
 def _follow_options(who: str, options: dict):
@@ -249,6 +262,54 @@ def franka_plan_global(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None
     out = franka_plan(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, return_all, limits, with_base_link, finger,
                       seeds=seed_traj[:, None], **options)
     return tuple(out) + (rm_status,)
+
+
+def gripper_roadmap(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=None, cylinders=None, W: int = 8, bounds=None,
+                    seed: int = 0, env_offset: int = 0, return_graph: bool = False, with_base_link: bool = False,
+                    finger: float = ft.FINGER_OPENING, **options):
+    """A lazy probabilistic roadmap per problem for the free-flying gripper in SE(3) on the GPU (csrc/gripper_roadmap.hip):
+    the pose path ``franka_follow`` is handed, planned through the scene for the gripper alone instead of being read off a
+    joint-space plan.  A STAND-IN for the reference's OMPL end-effector planner (``gen_data.py:156-189``), NOT a port of it
+    and without any claim of parity with AIT*; valid means free by this engine's sphere model (the hand and fingertip
+    spheres of the table), not by PyBullet's meshes.  ``nodes`` poses (start, goal and Philox draws keyed by (``seed``,
+    ``env_offset`` + row, node): positions in ``bounds``, orientations scattered by ``orient_spread`` about the start-goal
+    arc, not uniform on SO(3)) are judged by ``franka_plan``'s clause; the search is ``franka_roadmap``'s over the metric
+    sqrt(|dp|^2 + (``rot_weight`` x angle)^2), edges tested every ``resolution`` m.
+
+    :param start_pose, goal_pose: [B,4,4] right_gripper poses, as ``franka_ik`` takes its targets
+    :param cuboids, cylinders: as for ``franka_plan``
+    :param W: guide poses per problem, 1 .. 64
+    :param bounds: None (per problem the box hull of the two positions, grown by ``GRIPPER_ROADMAP_BOUNDS_PAD`` per side),
+        [2,3] (lo, hi for every problem) or [B,2,3]
+    :param options: the fields of ``mpx_gripper_roadmap_options``, see ``GRIPPER_ROADMAP_DEFAULTS``
+    :returns: ``poses`` [B,W,4,4] (at equal steps of the path's metric length, the start not among them, the last one
+        ``goal_pose``; NaN rows where ``status`` != 0) and ``status`` int32 [B] (0 path found, 1 none, 2 an endpoint pose is
+        non-finite, outside ``bounds`` or invalid); with ``return_graph`` also ``path`` int32 [B,V], ``hops`` int32 [B],
+        ``nodes`` [B,V,7] (position, quaternion x y z w), ``edge_state`` uint8 [B,V,V] and ``rounds`` int32 [B], as
+        ``franka_roadmap`` returns them."""
+    _lib.require_cuda(start_pose, goal_pose)
+    assert start_pose.ndim == 3 and tuple(start_pose.shape[1:]) == (4, 4) and goal_pose.shape == start_pose.shape
+    B, dev = start_pose.size(0), start_pose.device
+    sp, gp = _lib.f32c(start_pose), _lib.f32c(goal_pose)
+    copt, o = _gripper_roadmap_options("gripper_roadmap", options)
+    V, W = max(int(o["nodes"]), 0), int(W)
+    if bounds is None:
+        ends = torch.stack((sp[:, :3, 3], gp[:, :3, 3]), 1)
+        box = torch.stack((ends.amin(1) - GRIPPER_ROADMAP_BOUNDS_PAD, ends.amax(1) + GRIPPER_ROADMAP_BOUNDS_PAD), 1)
+    else:
+        box = torch.as_tensor(bounds, dtype=torch.float32, device=dev)
+        assert tuple(box.shape) in ((2, 3), (B, 2, 3))
+        box = box.expand(B, 2, 3)
+    box = _lib.f32c(box)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    out = (torch.empty((B, max(W, 0), 4, 4), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
+           torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
+           torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)  # poses, status, path, hops, nodes, edge_state, rounds
+    _lib.call("mpx_gripper_roadmap", sp.data_ptr(), gp.data_ptr(), B, W, box.data_ptr(), float(finger), *prims,
+              *options_tail(copt, seed, env_offset), *_ptrs(out))
+    return out if return_graph else out[:2]
 
 
 def franka_follow(q_start: torch.Tensor, poses: torch.Tensor, cuboids=None, cylinders=None, T: int = 50,
