@@ -839,6 +839,8 @@ int mpx_gather_rows(const float *src, const int64_t *idx, int B, int row_floats,
  * image W x H.  depth [B, H*W] = distance along the pixel's ray to the nearest cuboid / cylinder, or -1 when
  * nothing is hit within far_clip or one of the robot's spheres (sph_centers [B,S,3] from mpx_franka_spheres,
  * sph_radii [S]; S = 0: no robot) is in front -- the reference removes the robot's pixels.
+ * A primitive or robot sphere that CONTAINS the camera origin is invisible (the rasteriser this stands in for culls
+ * back faces): only an entry into a primitive counts as a hit, never the exit through a wall or a cap.
  * Replaces PyBullet's rasteriser + depth buffer (robofin Bullet.get_pointcloud_from_camera).       */
 int mpx_depth_render(const float *cam_poses, float fx, float fy, float cx, float cy, int W, int H, int B,
                      const float *cub_frames, const float *cub_dims, int M1, const float *cyl_frames,
@@ -847,7 +849,8 @@ int mpx_depth_render(const float *cam_poses, float fx, float fy, float cx, float
 /* np.random.choice(len(cloud), n_out, replace=False) of run_inference.py:78-85 on the device: every valid
  * pixel gets a Philox4x32-10 key (seed, env_offset + environment, pixel); the n_out smallest keys are written as world
  * points in key order to out (strides in floats).  count [B] = valid pixels; an environment with fewer than
- * n_out of them is left untouched (the caller raises like numpy).  n_out <= 4096.                    */
+ * n_out of them is left untouched (the caller raises like numpy).  n_out <= 4096.  A pixel is valid when its depth
+ * is >= 0 (so -0.0 is valid; -1 and NaN are not).                                                     */
 int mpx_depth_select(const float *depth, const float *cam_poses, float fx, float fy, float cx, float cy,
                      int W, int H, int B, int n_out, uint64_t seed, int64_t env_offset, float *out,
                      int64_t out_batch_stride, int out_point_stride, int32_t *count, mpx_stream_t stream);

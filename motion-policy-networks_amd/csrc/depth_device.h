@@ -65,6 +65,7 @@ __host__ __device__ __forceinline__ float ray_cylinder(const float *f, float r, 
   if (__builtin_fabsf(ez) > MPX_RAY_EPS) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
+      if (k ? !(lz < -hh) : !(lz > hh)) continue;  // a cap is an entry only for an origin beyond it, on its own side
       const float s = ((k ? -hh : hh) - lz) / ez;
       const float px = mpx_fma(s, ex, lx), py = mpx_fma(s, ey, ly);
       if (s > 0.0f && s < best && mpx_fma(py, py, px * px) <= r * r) best = s;

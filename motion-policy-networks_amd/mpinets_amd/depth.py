@@ -61,7 +61,8 @@ class DepthCamera:
     @torch.no_grad()
     def render(self, cam_poses: torch.Tensor, cuboids: TorchCuboids, cylinders: TorchCylinders,
                q: Optional[torch.Tensor] = None, collision_sampler: Optional[FrankaCollisionSampler] = None) -> torch.Tensor:
-        """-> depth [B, H, W] (metres along the ray; -1 = nothing / robot).  ``q`` [B,7]: robot pixels are removed."""
+        """-> depth [B, H, W] (metres along the ray; -1 = nothing / robot).  ``q`` [B,7]: robot pixels are removed.
+        A primitive or robot sphere that contains the camera origin is invisible (back faces are culled)."""
         _lib.require_cuda(cam_poses)
         cam = _lib.f32c(cam_poses)
         B = cam.size(0)

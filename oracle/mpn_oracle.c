@@ -817,6 +817,7 @@ static float orc_ray_cylinder(const float *f, float r, float hh, const float *o,
   }
   if (fabsf(e[2]) > 1e-12f) {
     for (int k = 0; k < 2; ++k) {
+      if (k ? !(l[2] < -hh) : !(l[2] > hh)) continue; /* a cap is an entry only for an origin beyond it, on its own side */
       float s = ((k ? -hh : hh) - l[2]) / e[2];
       float px = fmaf(s, e[0], l[0]), py = fmaf(s, e[1], l[1]);
       if (s > 0.0f && s < best && fmaf(py, py, px * px) <= r * r) best = s;
@@ -879,7 +880,7 @@ ORC_API void orc_depth_select(const float *depth, const float *cam, float fx, fl
     const float *dp = depth + (size_t)b * W * H, *P = cam + 16 * (size_t)b;
     int n = 0;
     for (int pix = 0; pix < W * H; ++pix) {
-      if (dp[pix] < 0.0f) continue;
+      if (!(dp[pix] >= 0.0f)) continue; /* valid = depth >= 0: -0.0 counts, NaN does not (as the kernel) */
       uint32_t r[4];
       orc_philox((uint32_t)(pix >> 2), env0 + (uint32_t)b, 9u, 0u, k0, k1, r); /* one block keys four consecutive pixels */
       keys[n++] = ((uint64_t)r[pix & 3] << 32) | (uint32_t)pix;

@@ -157,3 +157,64 @@ def test_oracle_subset_draw_is_a_uniform_draw_without_replacement(oracle):
     assert hits.min() > 60 and hits.max() < 140, hits
     first = np.bincount([oracle.draw_subset(64, 16, 9, d)[0] for d in range(400)], minlength=64)
     assert first.max() < 25  # (uniform ORDER too: no row is favoured as the first pick)
+
+
+def test_oracle_points_are_uniform_over_each_surface(oracle):
+    """Where the sampler puts its points (the device kernel is held to this oracle bit for bit): on a cuboid with three
+    distinct dims and a cylinder with h != r, the share of points per face is area / total, the free coordinates of every
+    face are uniform (mean and second moment) and a cap's rho^2 is uniform on [0, r^2] (the sqrt(u) of the radius).  Every
+    bound is 5 standard errors of the statistic, computed from the counts: one fixed seed, about 2e4 points per primitive."""
+    dims, r, h = np.array([0.3, 0.5, 0.7]), 0.2, 0.7
+    cc, yc = np.array([0.4, -0.1, 0.3], np.float32), np.array([-0.3, 0.2, 0.5], np.float32)
+    R, N = 10, 4096
+    scn = {"cuboid_centers": np.tile(cc, (R, 1, 1)), "cuboid_dims": np.tile(dims.astype(np.float32), (R, 1, 1)),
+           "cuboid_quats": np.tile(np.float32([1, 0, 0, 0]), (R, 1, 1)), "cylinder_centers": np.tile(yc, (R, 1, 1)),
+           "cylinder_radii": np.full((R, 1, 1), r, np.float32), "cylinder_heights": np.full((R, 1, 1), h, np.float32),
+           "cylinder_quats": np.tile(np.float32([1, 0, 0, 0]), (R, 1, 1))}
+    pts, assign, _, nobs = oracle.scene_cloud(scn, N, 97)
+    assert (nobs == 2).all() and set(np.unique(assign)) == {0, 1}
+    on = 1e-5  # a point is on a face when it is this close to its plane (float32 points: |sdf| < 2e-6)
+
+    def share(n, total, p):
+        assert abs(n / total - p) <= 5 * np.sqrt(p * (1 - p) / total), (n, total, p)
+
+    def uniform(x, half):  # x uniform on [-half, half]: mean 0 (variance half^2 / 3), E x^2 = half^2 / 3 (variance 4 half^4 / 45)
+        assert abs(x.mean()) <= 5 * half / np.sqrt(3 * len(x)), (x.mean(), half, len(x))
+        assert abs((x * x).mean() - half * half / 3) <= 5 * half * half * np.sqrt(4 / 45 / len(x)), ((x * x).mean(), half)
+
+    p = pts[assign == 0].astype(np.float64) - cc
+    assert len(p) > 15000
+    area = np.array([dims[1] * dims[2], dims[0] * dims[2], dims[0] * dims[1]])
+    seen, covered = 0, np.zeros(len(p), bool)
+    for a in range(3):
+        for sign in (-1, 1):
+            face = np.abs(p[:, a] - sign * dims[a] / 2) < on
+            seen, covered = seen + face.sum(), covered | face
+            share(face.sum(), len(p), area[a] / (2 * area.sum()))
+            for j in range(3):
+                if j != a:
+                    assert np.abs(p[face, j]).max() <= dims[j] / 2 + on
+                    uniform(p[face, j], dims[j] / 2)
+    assert covered.all() and seen - len(p) <= 10  # every point on a face (a few within 1e-5 of an edge count twice)
+
+    p = pts[assign == 1].astype(np.float64) - yc
+    assert len(p) > 15000
+    rho2 = p[:, 0] ** 2 + p[:, 1] ** 2
+    caps = [np.abs(p[:, 2] - sign * h / 2) < on for sign in (-1, 1)]
+    side = ~caps[0] & ~caps[1]
+    assert (np.abs(np.sqrt(rho2[side]) - r) < on).all() and (np.abs(p[side, 2]) <= h / 2 + on).all()
+    share(side.sum(), len(p), h / (h + r))  # 2 pi r h of 2 pi r h + 2 pi r^2
+    uniform(p[side, 2], h / 2)
+    n = side.sum()
+    for c in (p[side, 0] / r, p[side, 1] / r):  # the angle is uniform: E cos = 0 (variance 1/2), E cos^2 = 1/2 (variance 1/8)
+        assert abs(c.mean()) <= 5 * np.sqrt(0.5 / n) and abs((c * c).mean() - 0.5) <= 5 * np.sqrt(0.125 / n)
+    for cap in caps:
+        n = cap.sum()
+        share(n, len(p), r / (2 * (h + r)))
+        assert rho2[cap].max() <= (r + on) ** 2
+        # uniform over the disc: rho^2 uniform on [0, r^2] (mean r^2 / 2, variance r^4 / 12); E x = 0 (variance r^2 / 4);
+        # E x^2 = r^2 / 4 (variance r^4 / 16)
+        assert abs(rho2[cap].mean() - r * r / 2) <= 5 * r * r / np.sqrt(12 * n)
+        for x in (p[cap, 0], p[cap, 1]):
+            assert abs(x.mean()) <= 5 * r / (2 * np.sqrt(n))
+            assert abs((x * x).mean() - r * r / 4) <= 5 * r * r / (4 * np.sqrt(n))
