@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_gripper_roadmap,
+int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_roadmap_cloud,
+                          mpx_franka_plan_cloud_seeded, MPX_FRANKA_MAX_SPHERE_RADIUS; 341 (unchanged, likewise): mpx_gripper_roadmap,
                           struct mpx_gripper_roadmap_options; 341 (unchanged, likewise): mpx_franka_follow,
                           struct mpx_follow_options; 341 (unchanged, likewise): mpx_franka_roadmap,
                           struct mpx_roadmap_options, mpx_franka_plan_seeded;
@@ -648,6 +649,60 @@ int mpx_franka_plan_cloud(const float *q_start, const float *q_goal, int B, int 
                           const mpx_plan_options *options, uint64_t seed, int64_t env_offset, float *traj, int32_t *status,
                           int32_t *choice, float *all_traj, int32_t *all_status, void *scratch, int64_t scratch_bytes,
                           mpx_stream_t stream);
+
+/* mpx_franka_plan_cloud with caller-supplied candidates, on the terms of mpx_franka_plan_seeded: seeds [B,Ks,T,7], Ks >= 0,
+ * candidates + Ks <= MPX_PLAN_MAX_CANDIDATES.  Candidates 0 .. K-1 (K = options->candidates) are drawn and optimised exactly
+ * as by mpx_franka_plan_cloud; candidate K + i starts from seeds[b,i]: its interior waypoints clamped into the limits,
+ * waypoints 0 and T-1 replaced by q_start / q_goal; L stays the straight line for every candidate.  A seed with an entry
+ * that is not finite is not a candidate: its all_traj rows are NaN and its all_status is 7 (its wave runs from the line,
+ * so every scratch row the flag calls read is finite).  Iterations, the flag calls (K + Ks + 1 of them), the bits, "the
+ * LOWEST valid candidate" and status 2 are mpx_franka_plan_cloud's; all_traj is [B,K+Ks,T,7], all_status [B,K+Ks], choice
+ * counts over K + Ks.  Hence: with Ks = 0 (or seeds == NULL and Ks = 0) every output is bit-equal to
+ * mpx_franka_plan_cloud's (it is that launch); with any Ks candidates 0 .. K-1 are bit-equal, and a row
+ * mpx_franka_plan_cloud solves comes back identical.  scratch: at least mpx_franka_plan_cloud_scratch(B, T, candidates + Ks,
+ * substeps) bytes.  Ks > 0 with seeds == NULL is refused.                                                               */
+int mpx_franka_plan_cloud_seeded(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                                 const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                                 const float *field, const mpx_field_grid *grid, const float *cloud,
+                                 int64_t cloud_batch_stride, int cloud_point_stride, int N, const int32_t *counts,
+                                 float point_radius, const mpx_plan_options *options, uint64_t seed, int64_t env_offset,
+                                 const float *seeds, int Ks, float *traj, int32_t *status, int32_t *choice, float *all_traj,
+                                 int32_t *all_status, void *scratch, int64_t scratch_bytes, mpx_stream_t stream);
+
+/* mpx_franka_roadmap against a POINT CLOUD, read through its distance field: the global half in front of
+ * mpx_franka_plan_cloud_seeded.  Every clause of mpx_franka_roadmap's contract holds unchanged -- the nodes (Philox stream
+ * 16 keyed by (seed, GLOBAL problem id, node): the same seed gives the same nodes as mpx_franka_roadmap), the edge pieces,
+ * the Jacobi sweeps, the rounds, the statuses, path / hops / nodes / edge_state / rounds, the one-edge path that is the
+ * planner's line bit for bit, resampling and the (1/4, 1/2, 1/4) passes, NaN rows where status != 0 -- except what makes a
+ * configuration INVALID:
+ *   with check_self, mpx_franka_plan's self test with check_margin fails; or
+ *   some collision sphere s is BLOCKED.  Its centre c is that of mpx_franka_fk's chain in float32; (inside, D) =
+ *   mpx_cloud_field_sample's INSIDE and dist of `field` [B,nz,ny,nx] (environment b of THIS call, built by
+ *   mpx_cloud_field_build on `grid`) at c.  Blocked: c is inside the grid AND D < trunc AND
+ *       d <= check_margin + field_slack,   d = ((D - point_radius) - r_s) - clearance
+ *   (d is mpx_franka_plan_cloud's own expression, in that order, in float32; the right-hand side is summed once on the host
+ *   in float32).  A centre outside the grid, or where the field is saturated, counts as FREE: the field knows nothing
+ *   there, which is mpx_franka_plan_cloud's rule for its cost.  field == NULL: no environment test (grid is not read).
+ * Nodes 0 and 1 are nodes like the others: status 2 is mpx_franka_roadmap's rule read with this validity test.
+ * The field is an APPROXIMATION.  Distance is 1-Lipschitz, so the trilinear interpolant of exact nodal distances is within
+ * (sqrt(3)/2) h of the true distance: a row may get status 2 or 1 where the exact swept-sphere test would not, and a path
+ * found here may graze the cloud.  The roadmap therefore only SEEDS: mpx_franka_plan_cloud_seeded judges what it returns
+ * by the exact test, and a row without a seed is simply planned without one.  field_slack >= 0 [m] widens the threshold:
+ * 0 uses the field as it is (unbiased: it steers, as in the planner); 0.866 h makes the roadmap conservative.
+ * Refused before any launch: what mpx_franka_roadmap refuses (T, the options, S > 64, env_offset), a bad grid (with a
+ * field), point_radius or field_slack negative or not finite, a field with S == 0, and a field whose
+ *   trunc <= MPX_FRANKA_MAX_SPHERE_RADIUS + point_radius + max(clearance, 0) + (check_margin + field_slack)
+ * (an obstacle between trunc and the threshold would be missed silently).  The largest radius is NOT read from sph_radii
+ * (device memory): it is bounded by MPX_FRANKA_MAX_SPHERE_RADIUS, the largest radius of the library's own sphere table
+ * (the base link's); a caller with larger spheres leaves that room in trunc itself.
+ * No allocation, no scratch, no global atomics; one kernel on `stream` (capturable).  B == 0 launches nothing.         */
+#define MPX_FRANKA_MAX_SPHERE_RADIUS 0.08f
+int mpx_franka_roadmap_cloud(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,
+                             const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                             const float *field, const mpx_field_grid *grid, float point_radius, float field_slack,
+                             const mpx_roadmap_options *options, uint64_t seed, int64_t env_offset, float *traj,
+                             int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state,
+                             int32_t *rounds, mpx_stream_t stream);
 
 /* ---- split-bf16 ("bf16x3") dense layers: the opt-in fast mode of mpx_linear / mpx_linear_rowmax ------
  * Every fp32 product is evaluated as x_hi*w_hi + x_hi*w_lo + x_lo*w_hi on the bf16 matrix cores (fp32

@@ -115,3 +115,17 @@ __device__ __forceinline__ void plan_refined(const float *buf, int r, int subste
     for (int j = 0; j < 7; ++j) qq[j] = mpx_fma(f, buf[(seg + 1) * 7 + j] - buf[seg * 7 + j], buf[seg * 7 + j]);
   }
 }
+
+// PLAN_BIT_SELF of one configuration (the frames of the self model are all the FK the compiler keeps).  (Its own walk: through
+// plan.hip's plan_config_bits without an environment cloud_field.hip's planner was 0.6 - 1.3 % slower,
+// profiles/franka_device_timing.md)
+__device__ __forceinline__ int plan_self_bits(const float *q, float finger, float self_margin) {
+  int bits = 0;
+  franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
+    constexpr int id = decltype(ID)::value;
+    if constexpr (franka_self_sphere(id) >= 0) {
+      if (franka_self_hit<id>(g, self_margin)) bits |= PLAN_BIT_SELF;
+    }
+  });
+  return bits;
+}

@@ -11,31 +11,18 @@
 // concatenated untested edges of the round's path (the planner's validity-sweep mapping, in passes of 256), thread = waypoint
 // (resampling and the corner filter: T <= 64).  The path walk and the prefix sums over its <= V - 1 edges are serial on
 // thread 0.  Every branch around a barrier is workgroup-uniform: it reads a value from LDS behind a barrier, or a barrier's
-// own reduction.  The search itself is roadmap_search.inc, shared with gripper_roadmap.hip (the gripper's roadmap in SE(3)).
+// own reduction.  The search itself is roadmap_search.inc, shared with gripper_roadmap.hip (the gripper's roadmap in SE(3)) and
+// roadmap_cloud.hip (this roadmap against a point cloud's distance field), which also shares what follows it, roadmap_tail.inc.
 #include "common.h"
 #include "franka_host.h"
 #include "plan_prims_device.h"
 #include "roadmap_device.h"
-
-enum { STREAM_ROADMAP = 16 };
 
 // LDS, in 4-byte words: [128 primitive rows x 16 | nodes V x 7 | dist 2 x V (later: cumulative and edge lengths) |
 // two trajectories 64 x 7 | pred, path, rev, pieces, blocked, valid: V ints each | first V + 1 | hops | edge bits]
 __host__ __device__ static inline size_t roadmap_lds_words(int V) {
   return (size_t)128 * 16 + (size_t)V * 7 + 2 * (size_t)V + 2 * 64 * 7 + 6 * (size_t)V + (size_t)V + 1 + 1 +
          ((size_t)V * V + 15) / 16;
-}
-
-// |q_b - q_a|: j ascending, the first square rounded on its own, the others fused.  (x - y)^2 is (y - x)^2 bit for bit, so
-// the length of an edge does not depend on the order of its ends.
-__device__ __forceinline__ float roadmap_length(const float *qa, const float *qb) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    const float d = qb[j] - qa[j];
-    acc = j == 0 ? d * d : mpx_fma(d, d, acc);
-  }
-  return sqrtf(acc);
 }
 
 __global__ void __launch_bounds__(ROADMAP_THREADS)
@@ -107,72 +94,7 @@ __global__ void __launch_bounds__(ROADMAP_THREADS)
 #undef ROADMAP_SEARCH_POINT
 #undef ROADMAP_SEARCH_HIT
 
-  // ---- what the search found -----------------------------------------------------------------------------------------------------
-  if (tid == 0) {
-    status[b] = st, hops_out[b] = hops;
-    if (rounds_out) rounds_out[b] = rounds;
-  }
-  if (tid < V) path_out[(size_t)b * V + tid] = (st == 0 && tid <= hops) ? path[tid] : -1;
-  if (edge_out)
-    for (int i = tid; i < V * V; i += ROADMAP_THREADS) {
-      const int a = i / V, c = i - a * V;
-      edge_out[(size_t)b * V * V + i] =
-          (uint8_t)(a == c ? (valid[a] ? ROADMAP_FREE : ROADMAP_BLOCKED) : roadmap_edge_get(ebits, V, a, c));
-    }
-
-  // ---- the seed trajectory: thread = waypoint ------------------------------------------------------------------------------------
-  float *out = traj + (size_t)b * T * 7;
-  if (st != 0) {
-    for (int i = tid; i < T * 7; i += ROADMAP_THREADS) out[i] = nan;
-    return;
-  }
-  const bool end = tid == 0 || tid == T - 1;
-  if (hops == 1) {  // the planner's line itself
-    if (tid < T) {
-      const float s = (float)tid / (float)(T - 1);
-#pragma unroll
-      for (int j = 0; j < 7; ++j)
-        out[tid * 7 + j] = tid == 0 ? qs[j] : tid == T - 1 ? qg[j] : mpx_fma(s, qg[j] - qs[j], qs[j]);
-    }
-    return;
-  }
-  float *cum = dist, *len = dist + V;  // (the search is over: cum[i] = arc length at path node i, len[i] = |edge i|)
-  __syncthreads();
-  if (tid == 0) {
-    cum[0] = 0.0f;
-    for (int i = 0; i < hops; ++i) {
-      len[i] = roadmap_length(nodes + path[i] * 7, nodes + path[i + 1] * 7);
-      cum[i + 1] = cum[i] + len[i];
-    }
-  }
-  __syncthreads();
-  if (tid < T) {
-    const float s = ((float)tid / (float)(T - 1)) * cum[hops];
-    int i = 0;
-    for (int e = 1; e < hops; ++e)
-      if (cum[e] <= s) i = e;
-    const float f = len[i] > 0.0f ? fminf((s - cum[i]) / len[i], 1.0f) : 0.0f;
-    const float *pa = nodes + path[i] * 7, *pb = nodes + path[i + 1] * 7;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) tbuf[tid * 7 + j] = tid == 0 ? qs[j] : tid == T - 1 ? qg[j] : mpx_fma(f, pb[j] - pa[j], pa[j]);
-  }
-  __syncthreads();
-  float *src = tbuf, *dst = tbuf + 64 * 7;
-  for (int pass = 0; pass < opt.smooth_passes; ++pass) {  // (1/4, 1/2, 1/4) on the interior, each pass from the previous one
-    if (tid < T) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j)
-        dst[tid * 7 + j] = end ? src[tid * 7 + j]
-                               : mpx_fma(0.25f, src[(tid - 1) * 7 + j] + src[(tid + 1) * 7 + j], 0.5f * src[tid * 7 + j]);
-    }
-    __syncthreads();
-    float *swap = src;
-    src = dst, dst = swap;
-  }
-  if (tid < T) {
-#pragma unroll
-    for (int j = 0; j < 7; ++j) out[tid * 7 + j] = src[tid * 7 + j];
-  }
+#include "roadmap_tail.inc"
 }
 
 MPX_EXPORT int mpx_franka_roadmap(const float *q_start, const float *q_goal, int B, int T, float finger, const float *limits,

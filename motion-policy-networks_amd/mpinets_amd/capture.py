@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._operands import cloud_operand, counts_operand, scratch_for
 from .robot import FrankaCollisionSampler
-from .solvers import franka_ik_cloud, franka_plan_cloud
+from .solvers import franka_ik_cloud, franka_plan_cloud, franka_plan_global_cloud
 
 # planning_node.py:201-221: the task table and the mount table, rows of (lo x, lo y, lo z, hi x, hi y, hi z); a point is
 # inside when it is STRICTLY inside one of them
@@ -155,7 +155,8 @@ def clean_point_cloud(xyz: np.ndarray, rgba: np.ndarray, **kw) -> Tuple[np.ndarr
 def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torch.Tensor, *,
                   counts: Optional[torch.Tensor] = None, point_radius: float = 0.0, T: int = 50, seed: int = 0,
                   env_offset: int = 0, field=None, ik_options: Optional[dict] = None,
-                  plan_options: Optional[dict] = None) -> dict:
+                  plan_options: Optional[dict] = None, global_plan: bool = False,
+                  roadmap_options: Optional[dict] = None) -> dict:
     """From a cloud and a target pose to a checked trajectory: ``robot.franka_ik_cloud`` for the goal configuration, then
     ``robot.franka_plan_cloud`` from ``q_start`` to it, both against the same ``cloud`` (``counts``, ``point_radius``).  The
     optimiser-based counterpart of the reference demo's ``Planner.plan(q0, target_pose, obstacle_pc)``
@@ -165,12 +166,22 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
     :param q_start: [B,7];  :param target_poses: [B,4,4] right_gripper poses
     :param field: a ``CloudField`` of the cloud for the planner, or None (built there)
     :param ik_options, plan_options: keyword options of the two calls (``franka_ik_cloud`` / ``franka_plan_cloud``)
+    :param global_plan: False (every key and bit as before), or True: the trajectory comes from
+        ``robot.franka_plan_global_cloud`` -- a lazy roadmap through the cloud's distance field seeds one more candidate, so a
+        target behind an obstacle is not lost to a blocked straight line; ``roadmap_options`` are that roadmap's
     :returns: dict of ``q_goal`` [B,7] (NaN rows where ``ik_status`` != 0), ``ik_status`` int32 [B], ``trajectory``
         [B,T,7] (NaN rows where ``plan_status`` != 0), ``plan_status`` int32 [B] -- 2 for every row without a goal: the
-        planner refuses a NaN endpoint -- and ``valid`` bool [B]: both statuses 0."""
+        planner refuses a NaN endpoint -- and ``valid`` bool [B]: both statuses 0; with ``global_plan`` also ``roadmap_status``
+        int32 [B] (``franka_roadmap_cloud``'s)."""
     q_goal, ik_status = franka_ik_cloud(target_poses, cloud, counts, point_radius, seed=seed, env_offset=env_offset,
                                         **(ik_options or {}))
-    traj, plan_status = franka_plan_cloud(q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T,
-                                          seed=seed, env_offset=env_offset, **(plan_options or {}))
-    return {"q_goal": q_goal, "ik_status": ik_status, "trajectory": traj, "plan_status": plan_status,
-            "valid": (ik_status == 0) & (plan_status == 0)}
+    extra = {}
+    if global_plan:
+        traj, plan_status, extra["roadmap_status"] = franka_plan_global_cloud(
+            q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T, seed=seed, env_offset=env_offset,
+            roadmap=roadmap_options, **(plan_options or {}))
+    else:
+        traj, plan_status = franka_plan_cloud(q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T,
+                                              seed=seed, env_offset=env_offset, **(plan_options or {}))
+    return dict({"q_goal": q_goal, "ik_status": ik_status, "trajectory": traj, "plan_status": plan_status,
+                 "valid": (ik_status == 0) & (plan_status == 0)}, **extra)

@@ -33,7 +33,8 @@ from .solvers import (IK_BIT_CONVERGED, IK_BIT_ENV_HIT, IK_BIT_SELF_HIT, IK_DEFA
                       ROADMAP_BAD_ENDPOINT, ROADMAP_DEFAULTS, ROADMAP_EDGE_BLOCKED, ROADMAP_EDGE_FREE, ROADMAP_EDGE_UNTESTED,
                       ROADMAP_FOUND, ROADMAP_NO_PATH, _ik_options, _ik_outputs, _ik_sphere_table, _plan_options,
                       _plan_outputs, _roadmap_options, franka_ik, franka_ik_cloud, franka_plan, franka_plan_cloud,
-                      franka_plan_global, franka_roadmap, plan_cloud_truncation)
+                      franka_plan_global, franka_plan_global_cloud, franka_roadmap, franka_roadmap_cloud,
+                      plan_cloud_truncation)
 
 
 class _SE3Lite:

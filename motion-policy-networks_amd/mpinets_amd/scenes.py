@@ -294,13 +294,20 @@ EXPERT_CLOUD_POINT_RADIUS = 0.02  # [m] about half the spacing of 4096 points on
 
 
 def _expert_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
-                               seed: int, env_offset: int, point_radius: float) -> Dict[str, torch.Tensor]:
+                               seed: int, env_offset: int, point_radius: float,
+                               roadmap: bool = False) -> Dict[str, torch.Tensor]:
     """``expert_from="cloud"``: the demonstration is planned against the batch's own scene cloud (a view of the slab),
-    with ``solvers.franka_plan_cloud``; valid means free by ``FrankaCollisionSampler.check_cloud`` at ``point_radius``."""
-    from .solvers import franka_plan_cloud
+    with ``solvers.franka_plan_cloud``; valid means free by ``FrankaCollisionSampler.check_cloud`` at ``point_radius``.
+    ``roadmap`` (``expert_from="cloud_roadmap"``): with ``solvers.franka_plan_global_cloud``, the same planner with a lazy
+    roadmap's path as one more candidate."""
+    from .solvers import franka_plan_cloud, franka_plan_global_cloud
 
-    traj, status = franka_plan_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH, seed=seed,
-                                     env_offset=env_offset)
+    if roadmap:
+        traj, status, _ = franka_plan_global_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH,
+                                                   seed=seed, env_offset=env_offset)
+    else:
+        traj, status = franka_plan_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH, seed=seed,
+                                         env_offset=env_offset)
     return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
 
 
@@ -401,14 +408,16 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     ``FrankaCollisionSampler.check_cloud`` at that radius, which is not the primitive test.
     ``expert_from="roadmap"`` plans against the primitives with ``robot.franka_plan_global``: a lazy roadmap's path seeds one
     more candidate, so a problem whose straight line is blocked is not silently dropped; every row ``franka_plan`` solves
-    is returned as ``expert_from="primitives"`` returns it.
+    is returned as ``expert_from="primitives"`` returns it.  ``expert_from="cloud_roadmap"`` is the ``"cloud"`` branch with
+    ``robot.franka_plan_global_cloud``: the roadmap reads the cloud's distance field, the exact cloud test still judges, and
+    every row ``"cloud"`` solves is returned as ``"cloud"`` returns it.
 
     ``hybrid`` (with ``expert``; default off, which leaves every key as it was): also ``hybrid_solutions`` [B,50,7], the
     demonstration of ``solvers.franka_follow`` along eight right_gripper poses of ``global_solutions`` (a reactive follower
     standing in for the reference's Geometric Fabrics expert, NOT Lula), retimed to constant speed and judged against the
     primitives; ``hybrid_valid`` = ``expert_valid`` & followed and valid (bool [B]; the other rows are NaN); and
     ``hybrid_target_pose`` [B,4,4], the pose the hybrid trajectory ends at (the reference's hindsight goal revision).
-    Refused with ``expert_from="cloud"``: the follower has no cloud form, and ``hybrid_valid`` would mix the cloud test of the
+    Refused with ``expert_from="cloud"`` and ``"cloud_roadmap"``: the follower has no cloud form, and ``hybrid_valid`` would mix the cloud test of the
     plan with the primitive test of the follower.
 
     ``hybrid_guide`` (with ``hybrid``; default "global", which leaves every key and every bit as it was): "gripper" takes the
@@ -423,13 +432,13 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
     assert expert or not hybrid, "hybrid trajectories follow the expert's: they need expert=True"
-    if hybrid and expert_from == "cloud":  # (the follower steers by and is judged against primitives: ``hybrid_valid`` would mix two tests)
+    if hybrid and expert_from in ("cloud", "cloud_roadmap"):  # (the follower steers by and is judged against primitives: ``hybrid_valid`` would mix two tests)
         raise ValueError("hybrid=True needs expert_from='primitives' or 'roadmap': the follower runs against the primitives, "
                          "a plan judged against the point cloud is not what it would be judged by")
     if hybrid_guide not in ("global", "gripper"):
         raise ValueError(f"hybrid_guide must be 'global' or 'gripper', got {hybrid_guide!r}")
-    if expert_from not in ("primitives", "cloud", "roadmap"):
-        raise ValueError(f"expert_from must be 'primitives', 'cloud' or 'roadmap', got {expert_from!r}")
+    if expert_from not in ("primitives", "cloud", "roadmap", "cloud_roadmap"):
+        raise ValueError(f"expert_from must be 'primitives', 'cloud', 'roadmap' or 'cloud_roadmap', got {expert_from!r}")
 
     dev = torch.device(device)
     total = env_offset + B if total_envs is None else int(total_envs)
@@ -462,9 +471,10 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                             env_offset=env_offset)
     else:
         xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3] = torch.from_numpy(cloud[sid]).to(dev)
-    if expert and expert_from == "cloud":
+    if expert and expert_from in ("cloud", "cloud_roadmap"):
         scene_cloud = xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3]
-        out.update(_expert_trajectories_cloud(scene_cloud, q, q_goal, valid, seed, env_offset, expert_point_radius))
+        out.update(_expert_trajectories_cloud(scene_cloud, q, q_goal, valid, seed, env_offset, expert_point_radius,
+                                              roadmap=expert_from == "cloud_roadmap"))
     target_pose = frames_to_matrix(franka_fk(q_target)[:, ft.LINK_ID["right_gripper"]])
     xyz[:, NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS:, :3] = sampler.sample_end_effector(target_pose, NUM_TARGET_POINTS)
     np.random.set_state(state)

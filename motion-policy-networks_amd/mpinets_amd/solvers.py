@@ -1,6 +1,6 @@
 """The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap, the gripper's SE(3) roadmap and
 the path follower, against primitives or a point cloud (csrc/ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, follow.hip,
-cloud_field.hip).  Each wrapper is its entry's argument list: the inputs
+cloud_field.hip, roadmap_cloud.hip).  Each wrapper is its entry's argument list: the inputs
 (``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
 outputs, in the header's order.  ``robot`` re-exports every name here."""
 from __future__ import annotations
@@ -391,10 +391,23 @@ def plan_cloud_truncation(point_radius: float = 0.0, clearance: float = 0.0, eps
     return rmax + float(point_radius) + max(float(clearance), 0.0) + float(epsilon) + 2.0 * float(voxel)
 
 
+def _plan_cloud_field(who: str, cloud, cn, field, B: int, point_radius: float, clearance: float, epsilon: float,
+                      with_base_link: bool):
+    """The ``CloudField`` a cloud entry reads: ``field`` checked against the batch, or (None) one built on the default grid
+    with ``plan_cloud_truncation(point_radius, clearance, epsilon, voxel)``."""
+    if field is None:
+        field = CloudField.build(cloud, cn, truncation=plan_cloud_truncation(point_radius, clearance, epsilon, DEFAULT_VOXEL,
+                                                                            with_base_link))
+    _lib.require_cuda(field.values)
+    if field.values.size(0) != B or not field.values.is_contiguous():
+        raise _lib.MpxError(f"{who}: the field holds {field.values.size(0)} environments, the batch {B}")
+    return field
+
+
 def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
                       field=None, point_radius: float = 0.0, T: int = 50, seed: int = 0, env_offset: int = 0,
                       return_all: bool = False, limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False,
-                      finger: float = ft.FINGER_OPENING, **options):
+                      finger: float = ft.FINGER_OPENING, seeds: Optional[torch.Tensor] = None, **options):
     """``franka_plan`` against one POINT CLOUD per environment instead of primitives (csrc/cloud_field.hip): the same
     candidates, metric, jerk and self tests and lowest-valid-candidate rule.  The obstacle term of an iteration reads a
     truncated distance field of the cloud (``field.CloudField``, built here when ``field`` is None); whether a candidate is
@@ -406,19 +419,23 @@ def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.
     :param field: a ``CloudField`` of this cloud (batch B), or None: one is built on the default grid with
         ``plan_cloud_truncation(point_radius, clearance, epsilon, voxel)``
     :param point_radius: radius given to every point (>= 0), in the cost and in the validity test
+    :param seeds: None (``mpx_franka_plan_cloud``), or [B,Ks,T,7] caller-supplied starting trajectories
+        (``mpx_franka_plan_cloud_seeded``, e.g. ``franka_roadmap_cloud``'s), on ``franka_plan``'s terms: candidates
+        ``candidates`` .. ``candidates`` + Ks - 1, behind the drawn ones, which stay bit-equal; a seed with a non-finite entry
+        is not optimised (NaN rows, bits 7); ``candidates`` + Ks <= 16.  ``all_traj`` / ``all_status`` then have K + Ks rows.
     :returns: what ``franka_plan`` returns.  A batch whose scratch would exceed ``PLAN_CLOUD_SCRATCH_BYTES`` runs in slabs
         of problems (the draws are keyed by the global row: the result does not depend on the slabbing)."""
     B, dev, qs, qg, lim = _inputs(q_start, (7,), q_goal, limits, cloud, counts)
     copt, o = _plan_options("franka_plan_cloud", options)
     _, cn = cloud_args("franka_plan_cloud", cloud, counts, B, point_radius)  # (the refusals, and the counts for the field)
-    if field is None:
-        field = CloudField.build(cloud, cn, truncation=plan_cloud_truncation(point_radius, o["clearance"], o["epsilon"],
-                                                                            DEFAULT_VOXEL, with_base_link))
-    _lib.require_cuda(field.values)
-    if field.values.size(0) != B or not field.values.is_contiguous():
-        raise _lib.MpxError(f"franka_plan_cloud: the field holds {field.values.size(0)} environments, the batch {B}")
+    field = _plan_cloud_field("franka_plan_cloud", cloud, cn, field, B, point_radius, o["clearance"], o["epsilon"], with_base_link)
     sc, sr, sl = sphere_table(dev, with_base_link)
-    K, sub = max(int(o["candidates"]), 0), int(o["substeps"])
+    entry, sd, Ks = "mpx_franka_plan_cloud", None, 0
+    if seeds is not None:
+        _lib.require_cuda(seeds)
+        assert seeds.ndim == 4 and seeds.size(0) == B and tuple(seeds.shape[2:]) == (int(T), 7)
+        entry, sd, Ks = "mpx_franka_plan_cloud_seeded", _lib.f32c(seeds), seeds.size(1)
+    K, sub = max(int(o["candidates"]), 0) + Ks, int(o["substeps"])
     out = _plan_outputs(B, K, T, dev, return_all)
     lib = _lib.load()
     per = int(lib.mpx_franka_plan_cloud_scratch(1, int(T), K, sub))
@@ -432,9 +449,82 @@ def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.
         def at(t, row):  # pointer to row b0 of a [B, ...] operand
             return None if t is None else t.data_ptr() + b0 * row * t.element_size()
 
-        _lib.call("mpx_franka_plan_cloud", at(qs, 7), at(qg, 7), n, int(T), float(finger), lim.data_ptr(), sc.data_ptr(),
+        seeded = () if seeds is None else (at(sd, Ks * T * 7) if Ks else None, Ks)
+        _lib.call(entry, at(qs, 7), at(qg, 7), n, int(T), float(finger), lim.data_ptr(), sc.data_ptr(),
                   sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), at(field.values, nodes), ctypes.byref(field.grid),
                   *cloud_args("franka_plan_cloud", cloud, cn, B, point_radius, row=b0)[0],
-                  *options_tail(copt, seed, int(env_offset) + b0),
+                  *options_tail(copt, seed, int(env_offset) + b0), *seeded,
                   *(at(t, row) for t, row in zip(out, (T * 7, 1, 1, K * T * 7, K))), buf.data_ptr(), nbytes)
     return out if return_all else out[:2]
+
+
+def franka_roadmap_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: Optional[torch.Tensor],
+                         counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, field_slack: float = 0.0,
+                         T: int = 50, seed: int = 0, env_offset: int = 0, return_graph: bool = False,
+                         limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False, finger: float = ft.FINGER_OPENING,
+                         **options):
+    """``franka_roadmap`` against one POINT CLOUD per environment (csrc/roadmap_cloud.hip): the same nodes (the same seed
+    draws the same nodes), edges, search, statuses and seed trajectory, with the cloud's truncated distance field as the
+    validity test.  A collision sphere blocks a configuration when its centre is inside the grid, the field is not
+    saturated there and ``((D - point_radius) - r) - clearance <= check_margin + field_slack``; outside the grid and where
+    the field is saturated it counts as free.  The field is an APPROXIMATION: the trilinear interpolant is within
+    (sqrt(3)/2) x voxel of the true distance, so a row may get status 2 or 1 where ``check_cloud`` would not object, and a
+    path found here may graze the cloud.  The roadmap only seeds ``franka_plan_cloud(seeds=...)``, which judges by the exact
+    test; ``franka_plan_global_cloud`` runs the two.
+
+    :param cloud: as for ``franka_plan_cloud``; only used to build the field.  None with ``field`` None: no environment
+        (every edge that passes the self test is free)
+    :param field: a ``CloudField`` of the cloud (batch B), or None: one is built on the default grid with
+        ``plan_cloud_truncation(point_radius, clearance)``
+    :param field_slack: >= 0 [m], added to the threshold: 0 uses the field as it is (unbiased), ``0.866 * voxel`` makes the
+        roadmap conservative
+    :param options: the fields of ``mpx_roadmap_options``, see ``ROADMAP_DEFAULTS``
+    :returns: what ``franka_roadmap`` returns."""
+    B, dev, qs, qg, lim = _inputs(q_start, (7,), q_goal, limits, cloud, counts)
+    copt, o = _roadmap_options("franka_roadmap_cloud", options)
+    V = max(int(o["nodes"]), 0)
+    if cloud is not None or field is not None:
+        cn = None if cloud is None else cloud_args("franka_roadmap_cloud", cloud, counts, B, point_radius)[1]
+        field = _plan_cloud_field("franka_roadmap_cloud", cloud, cn, field, B, point_radius, o["clearance"],
+                                  PLAN_DEFAULTS["epsilon"], with_base_link)
+    sc, sr, sl = sphere_table(dev, with_base_link)
+    out = (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+           torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
+           torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
+           torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)  # traj, status, path, hops, nodes, edge_state, rounds
+    _lib.call("mpx_franka_roadmap_cloud", qs.data_ptr(), _lib.ptr(qg), B, int(T), float(finger), lim.data_ptr(), sc.data_ptr(),
+              sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), None if field is None else field.values.data_ptr(),
+              None if field is None else ctypes.byref(field.grid), float(point_radius), float(field_slack),
+              *options_tail(copt, seed, env_offset), *_ptrs(out))
+    return out if return_graph else out[:4]
+
+
+def franka_plan_global_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.Tensor,
+                             counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, T: int = 50,
+                             seed: int = 0, env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL,
+                             with_base_link: bool = False, finger: float = ft.FINGER_OPENING, field_slack: float = 0.0,
+                             roadmap: Optional[dict] = None, **options):
+    """``franka_roadmap_cloud``, then ``franka_plan_cloud`` with the roadmap's trajectory as one more candidate behind the
+    drawn ones, both reading ONE field of the cloud (built here when ``field`` is None): a row ``franka_plan_cloud`` solves
+    comes back identical, a row whose straight line is blocked gets a start that already goes round the obstacle.  Rows
+    where the roadmap found nothing pass a NaN seed (bits 7).  Valid is still decided by the exact cloud test alone.
+
+    :param roadmap: options of ``franka_roadmap_cloud`` (``ROADMAP_DEFAULTS``); ``check_margin``, ``clearance`` and
+        ``check_self`` default to the planner's values in ``options``
+    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 <= 16
+    :returns: what ``franka_plan_cloud`` returns (``all_traj`` / ``all_status`` with ``candidates`` + 1 rows, the seed last),
+        then the roadmap's ``status`` int32 [B]."""
+    _, o = _plan_options("franka_plan_global_cloud", options)
+    B = q_start.size(0)
+    _lib.require_cuda(q_start, cloud, counts)
+    _, cn = cloud_args("franka_plan_global_cloud", cloud, counts, B, point_radius)
+    field = _plan_cloud_field("franka_plan_global_cloud", cloud, cn, field, B, point_radius, o["clearance"], o["epsilon"],
+                              with_base_link)
+    shared = {k: o[k] for k in ("check_margin", "clearance", "check_self")}
+    seed_traj, rm_status, _, _ = franka_roadmap_cloud(q_start, q_goal, cloud, counts, field, point_radius, field_slack, T, seed,
+                                                      env_offset, False, limits, with_base_link, finger,
+                                                      **dict(shared, **(roadmap or {})))
+    out = franka_plan_cloud(q_start, q_goal, cloud, counts, field, point_radius, T, seed, env_offset, return_all, limits,
+                            with_base_link, finger, seeds=seed_traj[:, None], **options)
+    return tuple(out) + (rm_status,)
