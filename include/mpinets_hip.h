@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_roadmap_cloud,
+int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_follow_cloud,
+                          mpx_franka_follow_cloud_scratch; 341 (unchanged, likewise): mpx_franka_roadmap_cloud,
                           mpx_franka_plan_cloud_seeded, MPX_FRANKA_MAX_SPHERE_RADIUS; 341 (unchanged, likewise): mpx_gripper_roadmap,
                           struct mpx_gripper_roadmap_options; 341 (unchanged, likewise): mpx_franka_follow,
                           struct mpx_follow_options; 341 (unchanged, likewise): mpx_franka_roadmap,
@@ -703,6 +704,41 @@ int mpx_franka_roadmap_cloud(const float *q_start, const float *q_goal, int B, i
                              const mpx_roadmap_options *options, uint64_t seed, int64_t env_offset, float *traj,
                              int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state,
                              int32_t *rounds, mpx_stream_t stream);
+
+/* mpx_franka_follow against a POINT CLOUD: the same follower -- still the STAND-IN for the reference's Geometric Fabrics
+ * expert, NOT Lula's fabric, no parity claimed.  Every clause of mpx_franka_follow's contract holds unchanged -- the state,
+ * the switch and the stop, the attractor, the barrier, the damping, the clamp, the dense path and arc, the retiming, the
+ * jerk, self and miss bits, status 0 / 1 / 2, NaN rows, continuing a rollout from q_end / v_end / progress_end, one wave per
+ * problem, lane = collision sphere, the fixed-order reduction, no randomness -- with two substitutions:
+ *   Obstacle term of one step (clause 5).  (inside, D, n) = mpx_cloud_field_sample's INSIDE, dist and grad of `field`
+ *   [B,nz,ny,nx] (environment b of THIS call, built by mpx_cloud_field_build on `grid`) at the sphere centre x_s;
+ *   d_s = ((D - point_radius) - r_s) - clearance (mpx_franka_plan_cloud's expression, in that order, in float32); the sphere
+ *   is active only where D < trunc and d_s < epsilon: c'(d) = -1 for d < 0, else (d - epsilon) / epsilon; its term is
+ *   c'(d_s) n (n as sampled, not normalised) through the joints upstream of its link, as in mpx_franka_plan_cloud.  A centre
+ *   outside the grid or in the saturated band contributes nothing.  field == NULL: no obstacle term (grid is not read).
+ *   Environment verdict (bit 0 of bits).  A row carries it exactly when mpx_franka_cloud_collision flags its refined
+ *   configurations [B,R,7], R = (T-1) substeps + 1 (r = t substeps + i, mpx_franka_plan's fma), against environment b's
+ *   cloud (cloud, strides, N, counts: as there) with this point_radius and clearance = options->clearance +
+ *   options->check_margin summed in float32: that entry itself is called, flags only.  The field steers and never judges.
+ *   cloud == NULL, N == 0, S == 0 or counts[b] == 0: no environment test for that row.
+ *   status 2: mpx_franka_follow's rule, the configuration test of a FRESH rollout's q_start (progress_init == NULL) being
+ *   that call on q_start as [B,1,7] and, with check_self, the planner's self test; with progress_init given neither is made.
+ * Hence: with field == NULL and no cloud every output is bit-equal to mpx_franka_follow's without primitives.
+ * scratch: device memory, 16-byte aligned, at least mpx_franka_follow_cloud_scratch(B, T, substeps) bytes (-1 for sizes the
+ * entry refuses), owned by the caller, free when the stream has passed the call.  No allocation, no host synchronisation;
+ * every step is enqueued on `stream` (a memset of the flags, for a fresh rollout the flags call on q_start, the rollout
+ * kernel, the flags call on the refined configurations, a finish kernel that writes status, bits, traj and traj_any).
+ * Refused before any launch: what mpx_franka_follow refuses (W, T, the options, S > 64, NULL outputs or operands), a bad
+ * grid (with a field), point_radius negative, a cloud with N > 0 and a point stride below 3, a field or a cloud with S == 0,
+ * a scratch that is too small, NULL or not 16-byte aligned.  B == 0 launches nothing.                                   */
+int64_t mpx_franka_follow_cloud_scratch(int B, int T, int substeps);
+int mpx_franka_follow_cloud(const float *q_start, const float *poses, int B, int W, int T, float finger, const float *limits,
+                            const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                            const float *field, const mpx_field_grid *grid, const float *cloud, int64_t cloud_batch_stride,
+                            int cloud_point_stride, int N, const int32_t *counts, float point_radius, const float *v_init,
+                            const int32_t *progress_init, const mpx_follow_options *options, float *path, float *arc,
+                            int32_t *status, int32_t *bits, int32_t *steps, float *traj, float *traj_any, float *q_end,
+                            float *v_end, int32_t *progress_end, void *scratch, int64_t scratch_bytes, mpx_stream_t stream);
 
 /* ---- split-bf16 ("bf16x3") dense layers: the opt-in fast mode of mpx_linear / mpx_linear_rowmax ------
  * Every fp32 product is evaluated as x_hi*w_hi + x_hi*w_lo + x_lo*w_hi on the bf16 matrix cores (fp32

@@ -44,6 +44,8 @@ PROTOTYPES = {
     "mpx_franka_plan_seeded": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, I, P, P, P, P, P, P],
     "mpx_franka_roadmap": [P, P, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_franka_follow": [P, P, I, I, I, F, P, P, P, P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "mpx_franka_follow_cloud_scratch": [I, I, I],
+    "mpx_franka_follow_cloud": [P, P, I, I, I, F, P, P, P, P, I, P, P, P, L, I, I, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, P],
     "mpx_gripper_roadmap": [P, P, I, I, P, F, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
@@ -134,7 +136,7 @@ PROTOTYPES = {
     "mpx_rollout_step": [P, P, P, I, P, P, I, P, P, P, L, P],
     "mpx_rollout": [P, P, P, P, I, P, P, I, P, P, P, L, P],
 }
-RESTYPES = {"mpx_last_error": c_char_p, "mpx_franka_ik_cloud_scratch": c_int64, "mpx_franka_plan_cloud_scratch": c_int64, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
+RESTYPES = {"mpx_last_error": c_char_p, "mpx_franka_ik_cloud_scratch": c_int64, "mpx_franka_plan_cloud_scratch": c_int64, "mpx_franka_follow_cloud_scratch": c_int64, "mpx_cloud_clean_scratch": c_int64,"mpx_sa_pack_size": c_int64, "mpx_sa3_front_bf16x3_pack_size": c_int64, "mpx_sa_pack_bf16x3_size": c_int64,
             "mpx_linear_wgrad_scratch": c_int64, "mpx_pool_wgrad_scratch": c_int64, "mpx_linear_workspace": c_int64, "mpx_policy_workspace": c_int64, "mpx_rollout_workspace": c_int64}
 
 

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._operands import cloud_operand, counts_operand, scratch_for
 from .robot import FrankaCollisionSampler
-from .solvers import franka_ik_cloud, franka_plan_cloud, franka_plan_global_cloud
+from .solvers import franka_follow_cloud, franka_ik_cloud, franka_plan_cloud, franka_plan_global_cloud
 
 # planning_node.py:201-221: the task table and the mount table, rows of (lo x, lo y, lo z, hi x, hi y, hi z); a point is
 # inside when it is STRICTLY inside one of them
@@ -156,7 +156,8 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
                   counts: Optional[torch.Tensor] = None, point_radius: float = 0.0, T: int = 50, seed: int = 0,
                   env_offset: int = 0, field=None, ik_options: Optional[dict] = None,
                   plan_options: Optional[dict] = None, global_plan: bool = False,
-                  roadmap_options: Optional[dict] = None) -> dict:
+                  roadmap_options: Optional[dict] = None, follow: bool = False, follow_poses: int = 8,
+                  follow_options: Optional[dict] = None) -> dict:
     """From a cloud and a target pose to a checked trajectory: ``robot.franka_ik_cloud`` for the goal configuration, then
     ``robot.franka_plan_cloud`` from ``q_start`` to it, both against the same ``cloud`` (``counts``, ``point_radius``).  The
     optimiser-based counterpart of the reference demo's ``Planner.plan(q0, target_pose, obstacle_pc)``
@@ -172,7 +173,24 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
     :returns: dict of ``q_goal`` [B,7] (NaN rows where ``ik_status`` != 0), ``ik_status`` int32 [B], ``trajectory``
         [B,T,7] (NaN rows where ``plan_status`` != 0), ``plan_status`` int32 [B] -- 2 for every row without a goal: the
         planner refuses a NaN endpoint -- and ``valid`` bool [B]: both statuses 0; with ``global_plan`` also ``roadmap_status``
-        int32 [B] (``franka_roadmap_cloud``'s)."""
+        int32 [B] (``franka_roadmap_cloud``'s).
+    :param follow: False (what is returned is what it was), or True: the plan's right_gripper poses at ``follow_poses``
+        waypoints (round(i (T-1) / W), i = 1..W) are also followed from ``q_start`` by ``robot.franka_follow_cloud`` -- the
+        stand-in reactive controller, NOT Geometric Fabrics -- against the same cloud, counts, ``point_radius`` and ONE field
+        (built here when ``field`` is None and shared with the planner); ``follow_options`` are its keyword options.  Adds
+        ``followed_trajectory`` [B,T,7] (NaN rows where ``follow_status`` != 0), ``follow_status`` int32 [B] (2 for every row
+        without a plan: its guide is NaN), ``follow_bits`` and ``follow_steps`` int32 [B].  The same call with
+        ``max_steps`` and the returned state of ``franka_follow_cloud`` is the controller stepped against that cloud."""
+    if follow and field is None:  # (one field for the planner and the follower)
+        from ._operands import cloud_args
+        from .field import DEFAULT_VOXEL, CloudField
+        from .solvers import FOLLOW_DEFAULTS, PLAN_DEFAULTS, plan_cloud_truncation
+
+        eps = max(float((plan_options or {}).get("epsilon", PLAN_DEFAULTS["epsilon"])),
+                  float((follow_options or {}).get("epsilon", FOLLOW_DEFAULTS["epsilon"])))
+        clr = max(float((plan_options or {}).get("clearance", 0.0)), float((follow_options or {}).get("clearance", 0.0)))
+        _, cn = cloud_args("plan_to_poses", cloud, counts, q_start.size(0), point_radius)
+        field = CloudField.build(cloud, cn, truncation=plan_cloud_truncation(point_radius, clr, eps, DEFAULT_VOXEL))
     q_goal, ik_status = franka_ik_cloud(target_poses, cloud, counts, point_radius, seed=seed, env_offset=env_offset,
                                         **(ik_options or {}))
     extra = {}
@@ -183,5 +201,14 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
     else:
         traj, plan_status = franka_plan_cloud(q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T,
                                               seed=seed, env_offset=env_offset, **(plan_options or {}))
+    if follow:
+        from . import franka_tables as ft
+        from .robot import franka_fk, frames_to_matrix
+
+        B, W = q_start.size(0), int(follow_poses)
+        at = [int(round(i * (int(T) - 1) / W)) for i in range(1, W + 1)]
+        guide = frames_to_matrix(franka_fk(traj[:, at].reshape(-1, 7))[:, ft.LINK_ID["right_gripper"]]).reshape(B, W, 4, 4)
+        extra["followed_trajectory"], extra["follow_status"], extra["follow_bits"], extra["follow_steps"] = franka_follow_cloud(
+            q_start, guide, cloud, counts, field=field, point_radius=point_radius, T=T, **(follow_options or {}))
     return dict({"q_goal": q_goal, "ik_status": ik_status, "trajectory": traj, "plan_status": plan_status,
                  "valid": (ik_status == 0) & (plan_status == 0)}, **extra)

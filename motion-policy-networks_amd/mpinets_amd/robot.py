@@ -24,7 +24,7 @@ from . import _lib
 from . import franka_tables as ft
 from ._operands import cloud_args, sphere_primitive_args
 from .solvers import (FOLLOW_BAD_INPUT, FOLLOW_BIT_MISS, FOLLOW_DEFAULTS, FOLLOW_INVALID, FOLLOW_MAX_STEPS,  # noqa: F401
-                      FOLLOW_PATH_BYTES, FOLLOW_VALID, _follow_options, franka_follow)
+                      FOLLOW_PATH_BYTES, FOLLOW_VALID, _follow_options, franka_follow, franka_follow_cloud)
 from .solvers import (GRIPPER_ROADMAP_BOUNDS_PAD, GRIPPER_ROADMAP_DEFAULTS, _gripper_roadmap_options,  # noqa: F401
                       gripper_roadmap)
 from .solvers import (IK_BIT_CONVERGED, IK_BIT_ENV_HIT, IK_BIT_SELF_HIT, IK_DEFAULTS, IK_IN_COLLISION,  # noqa: F401

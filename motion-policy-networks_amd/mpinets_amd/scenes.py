@@ -351,6 +351,28 @@ def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
                 hybrid_target_pose=frames_to_matrix(franka_fk(traj[:, -1].contiguous())[:, gripper]))
 
 
+def _hybrid_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, global_solutions: torch.Tensor,
+                               expert_valid: torch.Tensor, point_radius: float) -> Dict[str, torch.Tensor]:
+    """``hybrid_against="cloud"``: ``_hybrid_trajectories`` with ``solvers.franka_follow_cloud`` (still the stand-in for the
+    reference's Geometric Fabrics expert, NOT Lula) following the same eight right_gripper poses of the cloud plan against
+    the batch's own scene cloud, at the expert's ``point_radius``: the cloud's distance field steers, ``check_cloud``'s test
+    judges, so ``hybrid_valid`` and ``expert_valid`` mean free by one and the same test.  One field is built here and
+    handed to the follower."""
+    from .field import DEFAULT_VOXEL, CloudField
+    from .robot import franka_fk, frames_to_matrix
+    from .solvers import FOLLOW_DEFAULTS, franka_follow_cloud, plan_cloud_truncation
+
+    B = q_start.size(0)
+    at = [int(round(i * (EXPERT_LENGTH - 1) / HYBRID_GUIDE_POSES)) for i in range(1, HYBRID_GUIDE_POSES + 1)]
+    gripper = ft.LINK_ID["right_gripper"]
+    guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
+    field = CloudField.build(scene_cloud, None, truncation=plan_cloud_truncation(
+        point_radius, FOLLOW_DEFAULTS["clearance"], FOLLOW_DEFAULTS["epsilon"], DEFAULT_VOXEL))
+    traj, status, _, _ = franka_follow_cloud(q_start, guide, scene_cloud, field=field, point_radius=point_radius, T=EXPERT_LENGTH)
+    return dict(hybrid_solutions=traj, hybrid_valid=expert_valid & (status == 0),
+                hybrid_target_pose=frames_to_matrix(franka_fk(traj[:, -1].contiguous())[:, gripper]))
+
+
 _DATASET_KEYS = {"cuboid_dims": "cuboid_dims", "cuboid_centers": "cuboid_centers", "cuboid_quats": "cuboid_quaternions",
                  "cylinder_radii": "cylinder_radii", "cylinder_heights": "cylinder_heights",
                  "cylinder_centers": "cylinder_centers", "cylinder_quats": "cylinder_quaternions"}
@@ -381,7 +403,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        total_envs: Optional[int] = None, collision_free: bool = False,
                        max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
                        expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False,
-                       hybrid_guide: str = "global") -> Dict[str, torch.Tensor]:
+                       hybrid_guide: str = "global", hybrid_against: str = "primitives") -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -417,8 +439,15 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     standing in for the reference's Geometric Fabrics expert, NOT Lula), retimed to constant speed and judged against the
     primitives; ``hybrid_valid`` = ``expert_valid`` & followed and valid (bool [B]; the other rows are NaN); and
     ``hybrid_target_pose`` [B,4,4], the pose the hybrid trajectory ends at (the reference's hindsight goal revision).
-    Refused with ``expert_from="cloud"`` and ``"cloud_roadmap"``: the follower has no cloud form, and ``hybrid_valid`` would mix the cloud test of the
-    plan with the primitive test of the follower.
+    Refused with ``expert_from="cloud"`` and ``"cloud_roadmap"`` unless ``hybrid_against="cloud"``: ``hybrid_valid`` would mix the
+    cloud test of the plan with the primitive test of the follower.
+
+    ``hybrid_against`` (with ``hybrid``; default "primitives", which leaves every key and every bit as it was): "cloud" needs
+    ``expert_from`` "cloud" or "cloud_roadmap" and ``hybrid_guide="global"`` (the gripper roadmap has no cloud form).  The
+    follower is then ``solvers.franka_follow_cloud`` (the same stand-in controller) along the same eight poses of the cloud
+    plan, against the same scene cloud at ``expert_point_radius`` through one shared distance field; ``hybrid_valid`` =
+    ``expert_valid`` & followed and free by ``check_cloud``'s test, the test the plan was judged by.  The keys are the same
+    three, and ``problems_to_dataset(prob, "hybrid_solutions")`` reads them unchanged.
 
     ``hybrid_guide`` (with ``hybrid``; default "global", which leaves every key and every bit as it was): "gripper" takes the
     follower's guide not from ``global_solutions`` but from ``solvers.gripper_roadmap``, a roadmap planner for the
@@ -432,9 +461,19 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
     assert expert or not hybrid, "hybrid trajectories follow the expert's: they need expert=True"
-    if hybrid and expert_from in ("cloud", "cloud_roadmap"):  # (the follower steers by and is judged against primitives: ``hybrid_valid`` would mix two tests)
+    if hybrid_against not in ("primitives", "cloud"):
+        raise ValueError(f"hybrid_against must be 'primitives' or 'cloud', got {hybrid_against!r}")
+    if hybrid_against == "cloud":
+        assert hybrid, "hybrid_against='cloud' chooses the follower's environment: it needs hybrid=True"
+        if expert_from not in ("cloud", "cloud_roadmap"):
+            raise ValueError("hybrid_against='cloud' needs expert_from='cloud' or 'cloud_roadmap': a plan judged against the "
+                             f"primitives is not what the cloud follower would be judged by, got {expert_from!r}")
+        if hybrid_guide != "global":
+            raise ValueError("hybrid_against='cloud' needs hybrid_guide='global': the gripper roadmap has no cloud form")
+    elif hybrid and expert_from in ("cloud", "cloud_roadmap"):  # (``hybrid_valid`` would mix two tests)
         raise ValueError("hybrid=True needs expert_from='primitives' or 'roadmap': the follower runs against the primitives, "
-                         "a plan judged against the point cloud is not what it would be judged by")
+                         "a plan judged against the point cloud is not what it would be judged by "
+                         "(hybrid_against='cloud' follows against the cloud instead)")
     if hybrid_guide not in ("global", "gripper"):
         raise ValueError(f"hybrid_guide must be 'global' or 'gripper', got {hybrid_guide!r}")
     if expert_from not in ("primitives", "cloud", "roadmap", "cloud_roadmap"):
@@ -478,7 +517,10 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     target_pose = frames_to_matrix(franka_fk(q_target)[:, ft.LINK_ID["right_gripper"]])
     xyz[:, NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS:, :3] = sampler.sample_end_effector(target_pose, NUM_TARGET_POINTS)
     np.random.set_state(state)
-    if hybrid:
+    if hybrid and hybrid_against == "cloud":
+        out.update(_hybrid_trajectories_cloud(xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3], q,
+                                              out["global_solutions"], out["expert_valid"], expert_point_radius))
+    elif hybrid:
         out.update(_hybrid_trajectories(out, q, out["global_solutions"], out["expert_valid"], q_goal, seed, env_offset,
                                         gripper_guide=hybrid_guide == "gripper"))
     out.update(q=q, q_norm=(q - lim[:, 0]) / (lim[:, 1] - lim[:, 0]) * 2 - 1, xyz=xyz, target_pose=target_pose,

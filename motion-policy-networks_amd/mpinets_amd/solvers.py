@@ -1,6 +1,6 @@
 """The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap, the gripper's SE(3) roadmap and
 the path follower, against primitives or a point cloud (csrc/ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, follow.hip,
-cloud_field.hip, roadmap_cloud.hip).  Each wrapper is its entry's argument list: the inputs
+cloud_field.hip, roadmap_cloud.hip, follow_cloud.hip).  Each wrapper is its entry's argument list: the inputs
 (``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
 outputs, in the header's order.  ``robot`` re-exports every name here."""
 from __future__ import annotations
@@ -456,6 +456,82 @@ def franka_plan_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.
                   *options_tail(copt, seed, int(env_offset) + b0), *seeded,
                   *(at(t, row) for t, row in zip(out, (T * 7, 1, 1, K * T * 7, K))), buf.data_ptr(), nbytes)
     return out if return_all else out[:2]
+
+
+def franka_follow_cloud(q_start: torch.Tensor, poses: torch.Tensor, cloud: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                        field=None, point_radius: float = 0.0, T: int = 50, v_init: Optional[torch.Tensor] = None,
+                        progress: Optional[torch.Tensor] = None, return_path: bool = False, return_state: bool = False,
+                        limits=ft.JOINT_LIMITS_REAL, with_base_link: bool = False, finger: float = ft.FINGER_OPENING,
+                        **options):
+    """``franka_follow`` against one POINT CLOUD per environment instead of primitives (csrc/follow_cloud.hip): the same
+    stand-in controller (NOT Lula's Geometric Fabrics, no parity claimed), steps, retiming, jerk, self and miss tests.  The
+    obstacle term of a step reads a truncated distance field of the cloud (``field.CloudField``, built here when ``field`` is
+    None); whether the retimed trajectory is free is decided by ``FrankaCollisionSampler.check_cloud``'s kernel on its
+    refined configurations, with this ``point_radius`` and ``clearance + check_margin`` -- the field steers, the exact test
+    judges, as in ``franka_plan_cloud``.  A fresh rollout's ``q_start`` is judged by that test too (status 2); with
+    ``progress`` given it is not, as for ``franka_follow``.
+
+    :param cloud: [B,N,3] or [B,N,4] float32 on the GPU, any view whose last stride is 1 (``xyz[:, 2048:6144, :3]`` of the
+        slab is read in place); ``counts`` optional int [B] as for ``check_cloud`` (a row with count 0 has no environment test)
+    :param field: a ``CloudField`` of this cloud (batch B), or None: one is built on the default grid with
+        ``plan_cloud_truncation(point_radius, clearance, epsilon, voxel)``
+    :param point_radius: radius given to every point (>= 0), in the obstacle term and in the verdict
+    :param options: the fields of ``mpx_follow_options``, see ``FOLLOW_DEFAULTS``
+    :returns: what ``franka_follow`` returns.  Without ``return_path`` the batch runs in slabs of problems whose dense path
+        stays below ``FOLLOW_PATH_BYTES`` and whose scratch stays below ``PLAN_CLOUD_SCRATCH_BYTES`` (rows do not depend on
+        one another: the result is the same)."""
+    _lib.require_cuda(poses, v_init, progress)
+    assert poses.ndim == 4 and tuple(poses.shape[2:]) == (4, 4) and poses.size(0) == q_start.size(0)
+    B, dev, qs, vi, lim = _inputs(q_start, (7,), v_init, limits, cloud, counts)
+    copt, o = _follow_options("franka_follow_cloud", options)
+    W, rows = poses.size(1), min(max(int(o["max_steps"]), 0), FOLLOW_MAX_STEPS) + 1  # (out of range: the call refuses)
+    ps = _lib.f32c(poses)
+    pg = None
+    if progress is not None:
+        assert progress.shape == (B, 3)
+        pg = _lib.i32c(progress)
+    _, cn = cloud_args("franka_follow_cloud", cloud, counts, B, point_radius)  # (the refusals, and the counts for the field)
+    field = _plan_cloud_field("franka_follow_cloud", cloud, cn, field, B, point_radius, o["clearance"], o["epsilon"], with_base_link)
+    sc, sr, sl = sphere_table(dev, with_base_link)
+
+    def f32(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    def i32(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+
+    lib = _lib.load()
+    sub = int(o["substeps"])
+    per = int(lib.mpx_franka_follow_cloud_scratch(1, int(T), sub))
+    slab = max(B, 1)
+    if not return_path:
+        slab = max(1, min(slab, FOLLOW_PATH_BYTES // (32 * rows)))
+        if per > 0:  # (per <= 0: the call refuses)
+            slab = max(1, min(slab, PLAN_CLOUD_SCRATCH_BYTES // per))
+    path, arc = f32(B if return_path else min(B, slab), rows, 7), f32(B if return_path else min(B, slab), rows)
+    traj, status, bits, steps = f32(B, T, 7), i32(B), i32(B), i32(B)
+    traj_any = f32(B, T, 7) if return_path else None
+    state = (f32(B, 7), f32(B, 7), i32(B, 3)) if return_state else (None, None, None)
+    nodes = field.values[0].numel() if B else 0
+    for b0 in range(0, max(B, 1), slab):
+        n = min(slab, B - b0)
+        nbytes = max(int(lib.mpx_franka_follow_cloud_scratch(n, int(T), sub)), 0)
+        buf = scratch_for(dev, nbytes)  # (fetched per call: CloudField.build above, or another entry, may have regrown it)
+
+        def at(p, row):  # row b0 of a [B, ...] operand of 4-byte elements, by its address
+            return p if p is None or row is None else p + 4 * b0 * row
+
+        outs = zip(_ptrs((path, arc, status, bits, steps, traj, traj_any) + state),
+                   (rows * 7 if return_path else 0, rows if return_path else 0, 1, 1, 1, T * 7, T * 7, 7, 7, 3))
+        _lib.call("mpx_franka_follow_cloud", at(qs.data_ptr(), 7), at(ps.data_ptr(), W * 16), n, W, int(T), float(finger),
+                  lim.data_ptr(), sc.data_ptr(), sr.data_ptr(), sl.data_ptr(), int(sc.size(0)),
+                  at(field.values.data_ptr(), nodes), ctypes.byref(field.grid),
+                  *cloud_args("franka_follow_cloud", cloud, cn, B, point_radius, row=b0)[0], at(_lib.ptr(vi), 7),
+                  at(_lib.ptr(pg), 3), ctypes.byref(copt), *(at(p, row) for p, row in outs), buf.data_ptr(), nbytes)
+    out = (traj, status, bits, steps)
+    if return_path:
+        out += (traj_any, path, arc)
+    return out + state if return_state else out
 
 
 def franka_roadmap_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: Optional[torch.Tensor],
