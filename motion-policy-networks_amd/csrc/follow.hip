@@ -16,6 +16,11 @@
 // opt.max_steps (host-checked) iterations; the dense path and its arc lengths go to the caller's global buffers (28 bytes
 // a step: LDS is better spent on occupancy in a latency-bound loop).  Retiming: lane = output waypoint, a bisection of
 // fixed length over arc[].  Verdict: plan_jerk_bits, plan_refined and plan_config_bits with lane = refined configuration.
+//
+// Everything but the obstacle term, the test of a fresh start, the bad-input return and the verdict is stated once for
+// this kernel and follow_cloud.hip's: follow_device.h and the statement blocks follow_state.inc, follow_step_head.inc,
+// follow_step_tail.inc, follow_retime.inc and follow_miss.inc (profiles/follow_shared_isa.md: the instruction streams did
+// not move).
 #include "common.h"
 #include "franka_host.h"
 #include "franka_device.h"
@@ -23,20 +28,7 @@
 #include "sdf_grad_device.h"
 #include "plan_device.h"        // ... with plan.hip: the joint terms of a sphere's gradient, the jerk test, the refined sweep
 #include "plan_prims_device.h"  // ... and the validity test of one configuration
-
-constexpr int FOLLOW_BISECT_ROUNDS = 13;  // 2^13 > MPX_FOLLOW_MAX_STEPS: the search interval is one index wide after them
-static_assert((1 << FOLLOW_BISECT_ROUNDS) > MPX_FOLLOW_MAX_STEPS, "the retiming search");
-static_assert(MPX_FOLLOW_MAX_POSES <= 64 && MPX_PLAN_MAX_T <= 64, "one lane per guide pose / per waypoint");
-
-__device__ __forceinline__ void follow_load_pose(const float *__restrict__ tg, float (&Rt)[9], float (&pt)[3]) {
-  Rt[0] = tg[0], Rt[1] = tg[1], Rt[2] = tg[2], Rt[3] = tg[4], Rt[4] = tg[5], Rt[5] = tg[6], Rt[6] = tg[8], Rt[7] = tg[9],
-  Rt[8] = tg[10];
-  pt[0] = tg[3], pt[1] = tg[7], pt[2] = tg[11];
-}
-__device__ __forceinline__ float follow_distance(const float (&pt)[3], const Rigid &eff) {
-  const float dx = pt[0] - eff.t[0], dy = pt[1] - eff.t[1], dz = pt[2] - eff.t[2];
-  return sqrtf(mpx_fma(dz, dz, mpx_fma(dy, dy, dx * dx)));
-}
+#include "follow_device.h"      // ... with follow_cloud.hip: all but the obstacle term and the verdict
 
 __global__ void __launch_bounds__(64)
     franka_follow_kernel(const float *__restrict__ q_start, const float *__restrict__ poses, int W, int T, float finger,
@@ -58,27 +50,7 @@ __global__ void __launch_bounds__(64)
   const float *my_poses = poses + (size_t)b * W * 16;
 
   // ---- the state as given, and what makes it bad input --------------------------------------------------------------------
-  float lo[7], hi[7], q[7], v[7];
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
-    q[j] = q_start[(size_t)b * 7 + j];
-    v[j] = v_init ? v_init[(size_t)b * 7 + j] : 0.0f;
-    bad |= !((q[j] >= lo[j]) & (q[j] <= hi[j])) | !(__builtin_fabsf(v[j]) < __builtin_inff());  // (NaN fails)
-  }
-  int w = progress_init ? progress_init[(size_t)b * 3 + 0] : 0;
-  int nw = progress_init ? progress_init[(size_t)b * 3 + 1] : 0;
-  int fin = progress_init ? (progress_init[(size_t)b * 3 + 2] != 0) : 0;
-  bad |= (w < 0) | (w >= W) | (nw < 0);
-  {
-    bool pose_bad = false;
-    if (lane < W) {  // lane = guide pose: its first three rows
-#pragma unroll
-      for (int i = 0; i < 12; ++i) pose_bad |= !(__builtin_fabsf(my_poses[16 * lane + i]) < __builtin_inff());
-    }
-    bad |= __any(pose_bad) != 0;
-  }
+#include "follow_state.inc"
 
   // ---- the problem's live primitives, compacted into LDS (every lane of the one wave stores) -------------------------------
 #define FRANKA_LIVE_ROWS_STORE true
@@ -103,14 +75,8 @@ __global__ void __launch_bounds__(64)
       if (traj_any) traj_any[(size_t)b * T * 7 + i] = nan;
     }
     if (lane == 0) {
-      status[b] = 2, bits_out[b] = PLAN_BIT_ENV | PLAN_BIT_SELF | PLAN_BIT_JERK | MPX_FOLLOW_BIT_MISS, steps_out[b] = 0;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        if (q_end) q_end[(size_t)b * 7 + j] = q[j];
-        if (v_end) v_end[(size_t)b * 7 + j] = v[j];
-      }
-      if (progress_end)
-        progress_end[(size_t)b * 3 + 0] = w, progress_end[(size_t)b * 3 + 1] = nw, progress_end[(size_t)b * 3 + 2] = fin;
+      status[b] = 2, bits_out[b] = FOLLOW_BAD_BITS, steps_out[b] = 0;
+      follow_store_state(b, q, v, w, nw, fin, q_end, v_end, progress_end);
     }
     return;
   }
@@ -129,39 +95,8 @@ __global__ void __launch_bounds__(64)
   int n = 0;
   for (int i = 1; i <= opt.max_steps; ++i) {
     if (fin) break;
-    // 1. FK: the joint origins and axes, right_gripper, and this lane's sphere centre from the frame of its link
-    float o[7][3], z[7][3], sx = 0.0f, sy = 0.0f, sz = 0.0f;  // (sx, sy, sz: the sphere centre)
-    Rigid eff;
-    franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
-      constexpr int id = decltype(ID)::value;
-      if constexpr (id >= 1 && id <= 7) {
-        o[id - 1][0] = g.t[0], o[id - 1][1] = g.t[1], o[id - 1][2] = g.t[2];
-        z[id - 1][0] = g.r[2], z[id - 1][1] = g.r[5], z[id - 1][2] = g.r[8];
-      }
-      if constexpr (id == 14) eff = g;
-      if constexpr (id >= 1) {
-        if (link == id) rigid_apply(g, cx, cy, cz, sx, sy, sz);
-      }
-    });
-    float dist = follow_distance(pt, eff);
-    // 2. switch (at most one advance), 3. stop (only where the last pose was the target on entry)
-    const bool last_on_entry = w == W - 1;
-    if (!last_on_entry && (dist <= opt.switch_radius || nw >= opt.switch_steps)) {
-      ++w, nw = 0;
-      follow_load_pose(my_poses + 16 * w, Rt, pt);
-      dist = follow_distance(pt, eff);
-    }
-    if (last_on_entry && (dist < opt.final_radius || nw >= opt.final_steps)) {
-      fin = 1;
-      break;
-    }
-    // 4. the attractor: mpx_franka_ik's dq
-#define DLS_STEP_CLIP opt.step_clip
-#include "dls_direction.inc"
-#undef DLS_STEP_CLIP
-    float u[7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) u[j] = dq[j] * scale;
+    // 1. FK, 2. switch, 3. stop (leaves the loop), 4. the attractor u
+#include "follow_step_head.inc"
     // 5. the obstacle gradient: lane = sphere, then the seven sums over lanes in a fixed order
     float g[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (test_env) {
@@ -191,62 +126,14 @@ __global__ void __launch_bounds__(64)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) g[j] += __shfl_xor(g[j], off);
     }
-    // 6. the acceleration, 7. position first, then the velocity; the clamp into the limits stops a joint
-    float ss = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float barrier = fmaxf(0.0f, (lo[j] + opt.limit_band) - q[j]) - fmaxf(0.0f, q[j] - (hi[j] - opt.limit_band));
-      const float a = ((opt.attract * u[j] - opt.repel * g[j]) + opt.limit_gain * barrier) - opt.damping * v[j];
-      const float moved = q[j] + opt.dt * v[j];
-      float vn = fminf(fmaxf(v[j] + opt.dt * a, -opt.speed_limit), opt.speed_limit);
-      const float qn = fminf(fmaxf(moved, lo[j]), hi[j]);
-      if (qn != moved) vn = 0.0f;
-      const float dj = qn - q[j];
-      ss = j == 0 ? dj * dj : mpx_fma(dj, dj, ss);
-      q[j] = qn, v[j] = vn;
-    }
-    total += sqrtf(ss);
-    ++nw;
-    n = i;
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j) P[(size_t)i * 7 + j] = q[j];
-      A[i] = total;
-    }
+    // 6. the acceleration, 7. the integration and the clamp, the arc length, the dense path
+#include "follow_step_tail.inc"
   }
   __threadfence_block();
   __syncthreads();  // (lane 0's path and arc are read by every lane below)
 
   // ---- retiming: lane = output waypoint -------------------------------------------------------------------------------------
-  const int t = lane < T ? lane : T - 1;  // (lanes past the trajectory repeat the last waypoint and never store)
-  float qt[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) qt[j] = q[j];  // waypoint T-1 is path[n], the state itself; with n = 0 every waypoint is
-  if (n > 0 && t < T - 1) {
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j) qt[j] = P[j];
-    } else {
-      const float st = ((float)t / (float)(T - 1)) * total;
-      int i0 = 0, i1 = n - 1;  // arc[i0] <= st (arc[0] = 0); the answer lies in i0 .. i1
-      for (int r = 0; r < FOLLOW_BISECT_ROUNDS; ++r) {
-        if (i0 < i1) {
-          const int mid = (i0 + i1 + 1) >> 1;
-          if (A[mid] <= st)
-            i0 = mid;
-          else
-            i1 = mid - 1;
-        }
-      }
-      const float a0 = A[i0], den = A[i0 + 1] - a0;
-      const float f = den > 0.0f ? fminf(fmaxf((st - a0) / den, 0.0f), 1.0f) : 0.0f;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const float p0 = P[(size_t)i0 * 7 + j];
-        qt[j] = mpx_fma(f, P[(size_t)(i0 + 1) * 7 + j] - p0, p0);
-      }
-    }
-  }
+#include "follow_retime.inc"
 
   // ---- the verdict: the planner's tests on the T waypoints, and the miss of the last guide pose ----------------------------
 #pragma unroll
@@ -264,15 +151,7 @@ __global__ void __launch_bounds__(64)
       }
     }
   }
-  {
-    Rigid eff;
-    franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
-      if constexpr (decltype(ID)::value == 14) eff = g;
-    });
-    float Rl[9], pl[3];
-    follow_load_pose(my_poses + 16 * (W - 1), Rl, pl);
-    if (!(follow_distance(pl, eff) <= opt.miss_tol * MPX_FOLLOW_MISS_SHARE)) bits |= MPX_FOLLOW_BIT_MISS;
-  }
+#include "follow_miss.inc"
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) bits |= __shfl_xor(bits, off);
 
@@ -286,13 +165,7 @@ __global__ void __launch_bounds__(64)
   }
   if (lane == 0) {
     status[b] = bits ? 1 : 0, bits_out[b] = bits, steps_out[b] = n;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      if (q_end) q_end[(size_t)b * 7 + j] = q[j];
-      if (v_end) v_end[(size_t)b * 7 + j] = v[j];
-    }
-    if (progress_end)
-      progress_end[(size_t)b * 3 + 0] = w, progress_end[(size_t)b * 3 + 1] = nw, progress_end[(size_t)b * 3 + 2] = fin;
+    follow_store_state(b, q, v, w, nw, fin, q_end, v_end, progress_end);
   }
 }
 

@@ -6,9 +6,12 @@
 // One wave per problem, as in follow.hip: the state, the joint origins and axes and the 6x6 solve are wave-uniform; in the
 // obstacle term the lane is the collision sphere (S <= 64), its centre is sampled with field_sample<true> (8 loads, issued
 // together), and the seven sums over spheres are follow.hip's butterfly of __shfl_xor in a fixed order.  There are no
-// primitive rows: the only LDS is the 64 x 7 waypoint buffer.  The time loop is this kernel's OWN COPY of follow.hip's
-// (as plan_cloud_kernel.inc is of the planner's): franka_follow_kernel keeps its instruction stream
-// (profiles/follow_cloud_timing.md has the comparison).
+// primitive rows: the only LDS is the 64 x 7 waypoint buffer.  What this file states is what differs from follow.hip: the
+// obstacle term, the test of a fresh start, the bad-input return and the verdict.  The state load, steps 1 to 4 and 6 to 7
+// of the time loop, the retiming and the miss test are the statement blocks both kernels include (follow_state.inc,
+// follow_step_head.inc, follow_step_tail.inc, follow_retime.inc, follow_miss.inc), the pose helpers and the state write-out
+// are follow_device.h's; both kernels have the instruction streams they had with a copy each
+// (profiles/follow_shared_isa.md).
 //
 // The entry enqueues, on the caller's stream and without a host synchronisation: a memset of the two flag rows, for a fresh
 // rollout a flags call on q_start as [B,1,7], the rollout kernel (steps, retiming, the jerk / self / miss bits, the T
@@ -20,11 +23,7 @@
 #include "dls_device.h"
 #include "field_device.h"
 #include "plan_device.h"
-
-constexpr int FOLLOW_CLOUD_BISECT_ROUNDS = 13;  // 2^13 > MPX_FOLLOW_MAX_STEPS, as in follow.hip
-static_assert((1 << FOLLOW_CLOUD_BISECT_ROUNDS) > MPX_FOLLOW_MAX_STEPS, "the retiming search");
-static_assert(MPX_FOLLOW_MAX_POSES <= 64 && MPX_PLAN_MAX_T <= 64, "one lane per guide pose / per waypoint");
-constexpr int FOLLOW_CLOUD_BAD_BITS = PLAN_BIT_ENV | PLAN_BIT_SELF | PLAN_BIT_JERK | MPX_FOLLOW_BIT_MISS;
+#include "follow_device.h"
 
 struct FollowCloudScratch {  // all in 4-byte words, from the start of `scratch`
   size_t refined;            // float [B, R, 7]: what the one flags call over the trajectories reads
@@ -49,16 +48,6 @@ static FollowCloudScratch follow_cloud_layout(int B, int T, int substeps) {
   return L;
 }
 
-__device__ __forceinline__ void follow_cloud_load_pose(const float *__restrict__ tg, float (&Rt)[9], float (&pt)[3]) {
-  Rt[0] = tg[0], Rt[1] = tg[1], Rt[2] = tg[2], Rt[3] = tg[4], Rt[4] = tg[5], Rt[5] = tg[6], Rt[6] = tg[8], Rt[7] = tg[9],
-  Rt[8] = tg[10];
-  pt[0] = tg[3], pt[1] = tg[7], pt[2] = tg[11];
-}
-__device__ __forceinline__ float follow_cloud_distance(const float (&pt)[3], const Rigid &eff) {
-  const float dx = pt[0] - eff.t[0], dy = pt[1] - eff.t[1], dz = pt[2] - eff.t[2];
-  return sqrtf(mpx_fma(dz, dz, mpx_fma(dy, dy, dx * dx)));
-}
-
 __global__ void __launch_bounds__(64)
     franka_follow_cloud_kernel(const float *__restrict__ q_start, const float *__restrict__ poses, int W, int T, float finger,
                                const float *__restrict__ limits, const float *__restrict__ sc, const float *__restrict__ sr,
@@ -79,27 +68,7 @@ __global__ void __launch_bounds__(64)
   float *ref = refined + (size_t)b * (size_t)R * 7;
 
   // ---- the state as given, and what makes it bad input --------------------------------------------------------------------
-  float lo[7], hi[7], q[7], v[7];
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    lo[j] = limits[2 * j], hi[j] = limits[2 * j + 1];
-    q[j] = q_start[(size_t)b * 7 + j];
-    v[j] = v_init ? v_init[(size_t)b * 7 + j] : 0.0f;
-    bad |= !((q[j] >= lo[j]) & (q[j] <= hi[j])) | !(__builtin_fabsf(v[j]) < __builtin_inff());  // (NaN fails)
-  }
-  int w = progress_init ? progress_init[(size_t)b * 3 + 0] : 0;
-  int nw = progress_init ? progress_init[(size_t)b * 3 + 1] : 0;
-  int fin = progress_init ? (progress_init[(size_t)b * 3 + 2] != 0) : 0;
-  bad |= (w < 0) | (w >= W) | (nw < 0);
-  {
-    bool pose_bad = false;
-    if (lane < W) {  // lane = guide pose: its first three rows
-#pragma unroll
-      for (int i = 0; i < 12; ++i) pose_bad |= !(__builtin_fabsf(my_poses[16 * lane + i]) < __builtin_inff());
-    }
-    bad |= __any(pose_bad) != 0;
-  }
+#include "follow_state.inc"
 
   const bool test_env = field != nullptr && S > 0, test_self = opt.check_self != 0;
   if (!bad && !progress_init) {  // (wave-uniform) the start of a FRESH rollout: the entry's flags call on q_start, the self test
@@ -116,14 +85,8 @@ __global__ void __launch_bounds__(64)
     // (the flags call over `refined` reads every row: a bad row's are zeros, and the finish kernel discards its flag)
     for (int i = lane; i < R * 7; i += 64) ref[i] = 0.0f;
     if (lane == 0) {
-      bad_out[b] = 1, pre_bits[b] = FOLLOW_CLOUD_BAD_BITS, steps_out[b] = 0;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        if (q_end) q_end[(size_t)b * 7 + j] = q[j];
-        if (v_end) v_end[(size_t)b * 7 + j] = v[j];
-      }
-      if (progress_end)
-        progress_end[(size_t)b * 3 + 0] = w, progress_end[(size_t)b * 3 + 1] = nw, progress_end[(size_t)b * 3 + 2] = fin;
+      bad_out[b] = 1, pre_bits[b] = FOLLOW_BAD_BITS, steps_out[b] = 0;
+      follow_store_state(b, q, v, w, nw, fin, q_end, v_end, progress_end);
     }
     return;
   }
@@ -139,43 +102,12 @@ __global__ void __launch_bounds__(64)
   // ---- the time loop: at most opt.max_steps steps ---------------------------------------------------------------------------
   const float lam2 = opt.lambda * opt.lambda, inv_eps = 1.0f / opt.epsilon;
   float Rt[9], pt[3], total = 0.0f;
-  follow_cloud_load_pose(my_poses + 16 * w, Rt, pt);
+  follow_load_pose(my_poses + 16 * w, Rt, pt);
   int n = 0;
   for (int i = 1; i <= opt.max_steps; ++i) {
     if (fin) break;
-    // 1. FK: the joint origins and axes, right_gripper, and this lane's sphere centre from the frame of its link
-    float o[7][3], z[7][3], sx = 0.0f, sy = 0.0f, sz = 0.0f;  // (sx, sy, sz: the sphere centre)
-    Rigid eff;
-    franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
-      constexpr int id = decltype(ID)::value;
-      if constexpr (id >= 1 && id <= 7) {
-        o[id - 1][0] = g.t[0], o[id - 1][1] = g.t[1], o[id - 1][2] = g.t[2];
-        z[id - 1][0] = g.r[2], z[id - 1][1] = g.r[5], z[id - 1][2] = g.r[8];
-      }
-      if constexpr (id == 14) eff = g;
-      if constexpr (id >= 1) {
-        if (link == id) rigid_apply(g, cx, cy, cz, sx, sy, sz);
-      }
-    });
-    float dist = follow_cloud_distance(pt, eff);
-    // 2. switch (at most one advance), 3. stop (only where the last pose was the target on entry)
-    const bool last_on_entry = w == W - 1;
-    if (!last_on_entry && (dist <= opt.switch_radius || nw >= opt.switch_steps)) {
-      ++w, nw = 0;
-      follow_cloud_load_pose(my_poses + 16 * w, Rt, pt);
-      dist = follow_cloud_distance(pt, eff);
-    }
-    if (last_on_entry && (dist < opt.final_radius || nw >= opt.final_steps)) {
-      fin = 1;
-      break;
-    }
-    // 4. the attractor: mpx_franka_ik's dq
-#define DLS_STEP_CLIP opt.step_clip
-#include "dls_direction.inc"
-#undef DLS_STEP_CLIP
-    float u[7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) u[j] = dq[j] * scale;
+    // 1. FK, 2. switch, 3. stop (leaves the loop), 4. the attractor u
+#include "follow_step_head.inc"
     // 5. the obstacle gradient: lane = sphere reads the field, then the seven sums over lanes in a fixed order
     float g[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (test_env) {
@@ -197,62 +129,14 @@ __global__ void __launch_bounds__(64)
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) g[j] += __shfl_xor(g[j], off);
     }
-    // 6. the acceleration, 7. position first, then the velocity; the clamp into the limits stops a joint
-    float ss = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const float barrier = fmaxf(0.0f, (lo[j] + opt.limit_band) - q[j]) - fmaxf(0.0f, q[j] - (hi[j] - opt.limit_band));
-      const float a = ((opt.attract * u[j] - opt.repel * g[j]) + opt.limit_gain * barrier) - opt.damping * v[j];
-      const float moved = q[j] + opt.dt * v[j];
-      float vn = fminf(fmaxf(v[j] + opt.dt * a, -opt.speed_limit), opt.speed_limit);
-      const float qn = fminf(fmaxf(moved, lo[j]), hi[j]);
-      if (qn != moved) vn = 0.0f;
-      const float dj = qn - q[j];
-      ss = j == 0 ? dj * dj : mpx_fma(dj, dj, ss);
-      q[j] = qn, v[j] = vn;
-    }
-    total += sqrtf(ss);
-    ++nw;
-    n = i;
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j) P[(size_t)i * 7 + j] = q[j];
-      A[i] = total;
-    }
+    // 6. the acceleration, 7. the integration and the clamp, the arc length, the dense path
+#include "follow_step_tail.inc"
   }
   __threadfence_block();
   __syncthreads();  // (lane 0's path and arc are read by every lane below)
 
   // ---- retiming: lane = output waypoint -------------------------------------------------------------------------------------
-  const int t = lane < T ? lane : T - 1;  // (lanes past the trajectory repeat the last waypoint and never store)
-  float qt[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) qt[j] = q[j];  // waypoint T-1 is path[n], the state itself; with n = 0 every waypoint is
-  if (n > 0 && t < T - 1) {
-    if (t == 0) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j) qt[j] = P[j];
-    } else {
-      const float st = ((float)t / (float)(T - 1)) * total;
-      int i0 = 0, i1 = n - 1;  // arc[i0] <= st (arc[0] = 0); the answer lies in i0 .. i1
-      for (int r = 0; r < FOLLOW_CLOUD_BISECT_ROUNDS; ++r) {
-        if (i0 < i1) {
-          const int mid = (i0 + i1 + 1) >> 1;
-          if (A[mid] <= st)
-            i0 = mid;
-          else
-            i1 = mid - 1;
-        }
-      }
-      const float a0 = A[i0], den = A[i0 + 1] - a0;
-      const float fr = den > 0.0f ? fminf(fmaxf((st - a0) / den, 0.0f), 1.0f) : 0.0f;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const float p0 = P[(size_t)i0 * 7 + j];
-        qt[j] = mpx_fma(fr, P[(size_t)(i0 + 1) * 7 + j] - p0, p0);
-      }
-    }
-  }
+#include "follow_retime.inc"
 
   // ---- the jerk, self and miss bits; the refined configurations go to scratch for the entry's flags call -------------------
 #pragma unroll
@@ -269,15 +153,7 @@ __global__ void __launch_bounds__(64)
       if (test_self) bits |= plan_self_bits(qq, finger, opt.check_margin);
     }
   }
-  {
-    Rigid eff;
-    franka_fk_visit(q, finger, [&](auto ID, const Rigid &g) __attribute__((always_inline)) {
-      if constexpr (decltype(ID)::value == 14) eff = g;
-    });
-    float Rl[9], pl[3];
-    follow_cloud_load_pose(my_poses + 16 * (W - 1), Rl, pl);
-    if (!(follow_cloud_distance(pl, eff) <= opt.miss_tol * MPX_FOLLOW_MISS_SHARE)) bits |= MPX_FOLLOW_BIT_MISS;
-  }
+#include "follow_miss.inc"
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) bits |= __shfl_xor(bits, off);
 
@@ -288,13 +164,7 @@ __global__ void __launch_bounds__(64)
   }
   if (lane == 0) {
     bad_out[b] = 0, pre_bits[b] = bits, steps_out[b] = n;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      if (q_end) q_end[(size_t)b * 7 + j] = q[j];
-      if (v_end) v_end[(size_t)b * 7 + j] = v[j];
-    }
-    if (progress_end)
-      progress_end[(size_t)b * 3 + 0] = w, progress_end[(size_t)b * 3 + 1] = nw, progress_end[(size_t)b * 3 + 2] = fin;
+    follow_store_state(b, q, v, w, nw, fin, q_end, v_end, progress_end);
   }
 }
 
@@ -306,7 +176,7 @@ __global__ void __launch_bounds__(64)
                                       float *__restrict__ traj_any) {
   const int b = blockIdx.x, lane = (int)threadIdx.x;
   const bool is_bad = bad[b] != 0;  // (block-uniform)
-  const int bits = is_bad ? FOLLOW_CLOUD_BAD_BITS : pre_bits[b] | (traj_flags[b] != 0 ? PLAN_BIT_ENV : 0);
+  const int bits = is_bad ? FOLLOW_BAD_BITS : pre_bits[b] | (traj_flags[b] != 0 ? PLAN_BIT_ENV : 0);
   const float nan = __builtin_nanf("");
   const float *src = waypoints + (size_t)b * T * 7;  // (a bad row's waypoints are not written, and not read)
   for (int i = lane; i < T * 7; i += 64) {

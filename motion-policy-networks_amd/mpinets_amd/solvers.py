@@ -117,6 +117,15 @@ def _plan_outputs(B: int, K: int, T: int, dev: torch.device, return_all: bool): 
             torch.empty((B, K), dtype=torch.int32, device=dev) if return_all else None)
 
 
+def _roadmap_outputs(B: int, rows0: tuple, V: int, dev: torch.device, return_graph: bool):
+    """-> traj [B,T,7] (``rows0`` = (T, 7)) or poses [B,W,4,4] (``rows0`` = (W, 4, 4)), status, path, hops, nodes, edge_state, rounds"""
+    return (torch.empty((B,) + rows0, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
+            torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
+            torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)
+
+
 def _ptrs(tensors):
     return [None if t is None else t.data_ptr() for t in tensors]
 
@@ -232,11 +241,7 @@ def franka_roadmap(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cy
     copt, o = _roadmap_options("franka_roadmap", options)
     V = max(int(o["nodes"]), 0)
     prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
-    out = (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
-           torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
-           torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)  # traj, status, path, hops, nodes, edge_state, rounds
+    out = _roadmap_outputs(B, (T, 7), V, dev, return_graph)
     _lib.call("mpx_franka_roadmap", qs.data_ptr(), _lib.ptr(qg), B, int(T), float(finger), lim.data_ptr(), *prims,
               *options_tail(copt, seed, env_offset), *_ptrs(out))
     return out if return_graph else out[:4]
@@ -302,14 +307,58 @@ def gripper_roadmap(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=N
         box = box.expand(B, 2, 3)
     box = _lib.f32c(box)
     prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
-    out = (torch.empty((B, max(W, 0), 4, 4), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
-           torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
-           torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)  # poses, status, path, hops, nodes, edge_state, rounds
+    out = _roadmap_outputs(B, (max(W, 0), 4, 4), V, dev, return_graph)
     _lib.call("mpx_gripper_roadmap", sp.data_ptr(), gp.data_ptr(), B, W, box.data_ptr(), float(finger), *prims,
               *options_tail(copt, seed, env_offset), *_ptrs(out))
     return out if return_graph else out[:2]
+
+
+def _at(p, row, b0):  # row b0 of a [B, ...] operand of 4-byte elements, by its address (``row`` None: not one per problem)
+    return p if p is None or row is None else p + 4 * b0 * row
+
+
+def _follow(who: str, q_start, poses, others: tuple, T, v_init, progress, return_path, return_state, limits, finger, options: dict,
+            environment):
+    """What ``franka_follow`` and ``franka_follow_cloud`` have in common, which is all but the environment: the inputs and
+    options, the outputs, the slabs of problems that share one dense-path buffer of at most ``FOLLOW_PATH_BYTES`` and the
+    call of ``mpx_<who>`` per slab.  ``environment(B, dev, o)`` (``o``: the merged options) -> the most problems its own
+    operands allow in a slab, ``block(b0, n)`` -> (the environment arguments of problems b0 .. b0 + n - 1, between ``limits``
+    and ``v_init``; what trails the outputs), and the tensors to hold until the last call returns."""
+    _lib.require_cuda(poses, v_init, progress)
+    assert poses.ndim == 4 and tuple(poses.shape[2:]) == (4, 4) and poses.size(0) == q_start.size(0)
+    B, dev, qs, vi, lim = _inputs(q_start, (7,), v_init, limits, *others)
+    copt, o = _follow_options(who, options)
+    W, rows = poses.size(1), min(max(int(o["max_steps"]), 0), FOLLOW_MAX_STEPS) + 1  # (out of range: the call refuses)
+    ps = _lib.f32c(poses)
+    pg = None
+    if progress is not None:
+        assert progress.shape == (B, 3)
+        pg = _lib.i32c(progress)
+    bound, block, held = environment(B, dev, o)  # (``held`` stays in this local until the last call has returned)
+
+    def f32(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    def i32(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+
+    slab = max(B, 1) if return_path else max(1, min(max(B, 1), FOLLOW_PATH_BYTES // (32 * rows), bound))
+    path, arc = f32(B if return_path else min(B, slab), rows, 7), f32(B if return_path else min(B, slab), rows)
+    traj, status, bits, steps = f32(B, T, 7), i32(B), i32(B), i32(B)
+    traj_any = f32(B, T, 7) if return_path else None
+    state = (f32(B, 7), f32(B, 7), i32(B, 3)) if return_state else (None, None, None)
+    outs = tuple(zip(_ptrs((path, arc, status, bits, steps, traj, traj_any) + state),  # 4-byte elements per problem behind each
+                     (rows * 7 if return_path else 0, rows if return_path else 0, 1, 1, 1, T * 7, T * 7, 7, 7, 3)))
+    for b0 in range(0, max(B, 1), slab):
+        n = min(slab, B - b0)
+        env, trailing = block(b0, n)
+        _lib.call("mpx_" + who, _at(qs.data_ptr(), 7, b0), _at(ps.data_ptr(), W * 16, b0), n, W, int(T), float(finger),
+                  lim.data_ptr(), *env, _at(_lib.ptr(vi), 7, b0), _at(_lib.ptr(pg), 3, b0), ctypes.byref(copt),
+                  *(_at(p, row, b0) for p, row in outs), *trailing)
+    out = (traj, status, bits, steps)
+    if return_path:
+        out += (traj_any, path, arc)
+    return out + state if return_state else out
 
 
 def franka_follow(q_start: torch.Tensor, poses: torch.Tensor, cuboids=None, cylinders=None, T: int = 50,
@@ -341,45 +390,14 @@ def franka_follow(q_start: torch.Tensor, poses: torch.Tensor, cuboids=None, cyli
         path whether or not it is returned (32 (max_steps + 1) bytes a problem: 33 kB with the defaults).  With
         ``return_path`` all of it is allocated, 269 MB at B = 8192; without, the batch runs in slabs of problems that
         share one buffer of at most ``FOLLOW_PATH_BYTES`` (rows do not depend on one another: the result is the same)."""
-    _lib.require_cuda(poses, v_init, progress)
-    assert poses.ndim == 4 and tuple(poses.shape[2:]) == (4, 4) and poses.size(0) == q_start.size(0)
-    B, dev, qs, vi, lim = _inputs(q_start, (7,), v_init, limits)
-    copt, o = _follow_options("franka_follow", options)
-    W, rows = poses.size(1), min(max(int(o["max_steps"]), 0), FOLLOW_MAX_STEPS) + 1  # (out of range: the call refuses)
-    ps = _lib.f32c(poses)
-    pg = None
-    if progress is not None:
-        assert progress.shape == (B, 3)
-        pg = _lib.i32c(progress)
-    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    def environment(B, dev, o):
+        prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+        M1, M2 = prims[6], prims[10]
+        prim_rows = (0, 0, 0, None, M1 * 16, M1 * 3, None, M2 * 16, M2, M2, None)  # floats per problem behind each pointer
+        return max(B, 1), lambda b0, n: ([_at(p, row, b0) for p, row in zip(prims, prim_rows)], ()), held
 
-    def f32(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-
-    def i32(*shape):
-        return torch.empty(shape, dtype=torch.int32, device=dev)
-
-    slab = max(B, 1) if return_path else max(1, min(max(B, 1), FOLLOW_PATH_BYTES // (32 * rows)))
-    path, arc = f32(B if return_path else min(B, slab), rows, 7), f32(B if return_path else min(B, slab), rows)
-    traj, status, bits, steps = f32(B, T, 7), i32(B), i32(B), i32(B)
-    traj_any = f32(B, T, 7) if return_path else None
-    state = (f32(B, 7), f32(B, 7), i32(B, 3)) if return_state else (None, None, None)
-    M1, M2 = prims[6], prims[10]
-    prim_rows = (0, 0, 0, None, M1 * 16, M1 * 3, None, M2 * 16, M2, M2, None)  # floats per problem behind each pointer
-    for b0 in range(0, max(B, 1), slab):
-
-        def at(p, row):  # row b0 of a [B, ...] operand of 4-byte elements, by its address
-            return p if p is None or row is None else p + 4 * b0 * row
-
-        outs = zip(_ptrs((path, arc, status, bits, steps, traj, traj_any) + state),
-                   (rows * 7 if return_path else 0, rows if return_path else 0, 1, 1, 1, T * 7, T * 7, 7, 7, 3))
-        _lib.call("mpx_franka_follow", at(qs.data_ptr(), 7), at(ps.data_ptr(), W * 16), min(slab, B - b0), W, int(T), float(finger),
-                  lim.data_ptr(), *(at(p, row) for p, row in zip(prims, prim_rows)), at(_lib.ptr(vi), 7), at(_lib.ptr(pg), 3),
-                  ctypes.byref(copt), *(at(p, row) for p, row in outs))
-    out = (traj, status, bits, steps)
-    if return_path:
-        out += (traj_any, path, arc)
-    return out + state if return_state else out
+    return _follow("franka_follow", q_start, poses, (), T, v_init, progress, return_path, return_state, limits, finger, options,
+                   environment)
 
 
 def plan_cloud_truncation(point_radius: float = 0.0, clearance: float = 0.0, epsilon: float = PLAN_DEFAULTS["epsilon"],
@@ -480,58 +498,26 @@ def franka_follow_cloud(q_start: torch.Tensor, poses: torch.Tensor, cloud: torch
     :returns: what ``franka_follow`` returns.  Without ``return_path`` the batch runs in slabs of problems whose dense path
         stays below ``FOLLOW_PATH_BYTES`` and whose scratch stays below ``PLAN_CLOUD_SCRATCH_BYTES`` (rows do not depend on
         one another: the result is the same)."""
-    _lib.require_cuda(poses, v_init, progress)
-    assert poses.ndim == 4 and tuple(poses.shape[2:]) == (4, 4) and poses.size(0) == q_start.size(0)
-    B, dev, qs, vi, lim = _inputs(q_start, (7,), v_init, limits, cloud, counts)
-    copt, o = _follow_options("franka_follow_cloud", options)
-    W, rows = poses.size(1), min(max(int(o["max_steps"]), 0), FOLLOW_MAX_STEPS) + 1  # (out of range: the call refuses)
-    ps = _lib.f32c(poses)
-    pg = None
-    if progress is not None:
-        assert progress.shape == (B, 3)
-        pg = _lib.i32c(progress)
-    _, cn = cloud_args("franka_follow_cloud", cloud, counts, B, point_radius)  # (the refusals, and the counts for the field)
-    field = _plan_cloud_field("franka_follow_cloud", cloud, cn, field, B, point_radius, o["clearance"], o["epsilon"], with_base_link)
-    sc, sr, sl = sphere_table(dev, with_base_link)
+    who = "franka_follow_cloud"
 
-    def f32(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
+    def environment(B, dev, o):
+        _, cn = cloud_args(who, cloud, counts, B, point_radius)  # (the refusals, and the counts for the field)
+        fld = _plan_cloud_field(who, cloud, cn, field, B, point_radius, o["clearance"], o["epsilon"], with_base_link)
+        sc, sr, sl = sphere_table(dev, with_base_link)
+        lib, sub = _lib.load(), int(o["substeps"])
+        per = int(lib.mpx_franka_follow_cloud_scratch(1, int(T), sub))
+        nodes = fld.values[0].numel() if B else 0
 
-    def i32(*shape):
-        return torch.empty(shape, dtype=torch.int32, device=dev)
+        def block(b0, n):
+            nbytes = max(int(lib.mpx_franka_follow_cloud_scratch(n, int(T), sub)), 0)
+            buf = scratch_for(dev, nbytes)  # (fetched per call: CloudField.build above, or another entry, may have regrown it)
+            return ((sc.data_ptr(), sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), _at(fld.values.data_ptr(), nodes, b0),
+                     ctypes.byref(fld.grid), *cloud_args(who, cloud, cn, B, point_radius, row=b0)[0]), (buf.data_ptr(), nbytes))
 
-    lib = _lib.load()
-    sub = int(o["substeps"])
-    per = int(lib.mpx_franka_follow_cloud_scratch(1, int(T), sub))
-    slab = max(B, 1)
-    if not return_path:
-        slab = max(1, min(slab, FOLLOW_PATH_BYTES // (32 * rows)))
-        if per > 0:  # (per <= 0: the call refuses)
-            slab = max(1, min(slab, PLAN_CLOUD_SCRATCH_BYTES // per))
-    path, arc = f32(B if return_path else min(B, slab), rows, 7), f32(B if return_path else min(B, slab), rows)
-    traj, status, bits, steps = f32(B, T, 7), i32(B), i32(B), i32(B)
-    traj_any = f32(B, T, 7) if return_path else None
-    state = (f32(B, 7), f32(B, 7), i32(B, 3)) if return_state else (None, None, None)
-    nodes = field.values[0].numel() if B else 0
-    for b0 in range(0, max(B, 1), slab):
-        n = min(slab, B - b0)
-        nbytes = max(int(lib.mpx_franka_follow_cloud_scratch(n, int(T), sub)), 0)
-        buf = scratch_for(dev, nbytes)  # (fetched per call: CloudField.build above, or another entry, may have regrown it)
+        return PLAN_CLOUD_SCRATCH_BYTES // per if per > 0 else max(B, 1), block, None  # (per <= 0: the call refuses)
 
-        def at(p, row):  # row b0 of a [B, ...] operand of 4-byte elements, by its address
-            return p if p is None or row is None else p + 4 * b0 * row
-
-        outs = zip(_ptrs((path, arc, status, bits, steps, traj, traj_any) + state),
-                   (rows * 7 if return_path else 0, rows if return_path else 0, 1, 1, 1, T * 7, T * 7, 7, 7, 3))
-        _lib.call("mpx_franka_follow_cloud", at(qs.data_ptr(), 7), at(ps.data_ptr(), W * 16), n, W, int(T), float(finger),
-                  lim.data_ptr(), sc.data_ptr(), sr.data_ptr(), sl.data_ptr(), int(sc.size(0)),
-                  at(field.values.data_ptr(), nodes), ctypes.byref(field.grid),
-                  *cloud_args("franka_follow_cloud", cloud, cn, B, point_radius, row=b0)[0], at(_lib.ptr(vi), 7),
-                  at(_lib.ptr(pg), 3), ctypes.byref(copt), *(at(p, row) for p, row in outs), buf.data_ptr(), nbytes)
-    out = (traj, status, bits, steps)
-    if return_path:
-        out += (traj_any, path, arc)
-    return out + state if return_state else out
+    return _follow(who, q_start, poses, (cloud, counts), T, v_init, progress, return_path, return_state, limits, finger, options,
+                   environment)
 
 
 def franka_roadmap_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: Optional[torch.Tensor],
@@ -564,11 +550,7 @@ def franka_roadmap_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: Opt
         field = _plan_cloud_field("franka_roadmap_cloud", cloud, cn, field, B, point_radius, o["clearance"],
                                   PLAN_DEFAULTS["epsilon"], with_base_link)
     sc, sr, sl = sphere_table(dev, with_base_link)
-    out = (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty((B, V), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-           torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
-           torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
-           torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)  # traj, status, path, hops, nodes, edge_state, rounds
+    out = _roadmap_outputs(B, (T, 7), V, dev, return_graph)
     _lib.call("mpx_franka_roadmap_cloud", qs.data_ptr(), _lib.ptr(qg), B, int(T), float(finger), lim.data_ptr(), sc.data_ptr(),
               sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), None if field is None else field.values.data_ptr(),
               None if field is None else ctypes.byref(field.grid), float(point_radius), float(field_slack),
