@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: additions, no caller of an earlier 341 library needs rebuilding): mpx_franka_follow_cloud,
+int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding):
+                          mpx_gripper_roadmap_cloud; 341 (unchanged, likewise): mpx_franka_follow_cloud,
                           mpx_franka_follow_cloud_scratch; 341 (unchanged, likewise): mpx_franka_roadmap_cloud,
                           mpx_franka_plan_cloud_seeded, MPX_FRANKA_MAX_SPHERE_RADIUS; 341 (unchanged, likewise): mpx_gripper_roadmap,
                           struct mpx_gripper_roadmap_options; 341 (unchanged, likewise): mpx_franka_follow,
@@ -704,6 +705,41 @@ int mpx_franka_roadmap_cloud(const float *q_start, const float *q_goal, int B, i
                              const mpx_roadmap_options *options, uint64_t seed, int64_t env_offset, float *traj,
                              int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state,
                              int32_t *rounds, mpx_stream_t stream);
+
+/* mpx_gripper_roadmap against a POINT CLOUD, read through its distance field: the guide of mpx_franka_follow_cloud where
+ * there are no primitives to plan the gripper through.  Still the STAND-IN for the reference's OMPL end-effector planner,
+ * NOT a port of it.  Every clause of mpx_gripper_roadmap's contract holds unchanged -- the gripper's rows of the sphere
+ * table (links 9 / 12 / 13) and where a pose puts them, the self test on the three frame origins, the nodes (Philox stream
+ * 17 keyed by (seed, GLOBAL problem id, node): the same seed gives the same nodes as mpx_gripper_roadmap, bit for bit), the
+ * metric, the pieces and the nlerp of an edge, the search, the statuses, path / hops / nodes / edge_state / rounds, the
+ * resampling to W guide poses with rows 0-2 of the last one goal_pose's bit for bit, NaN rows where status != 0, the
+ * options with the same defaults -- except the ENVIRONMENT half of what makes a pose invalid:
+ *   some gripper sphere s is BLOCKED.  Its centre c is placed from the pose as stated there, in float32; (inside, D) =
+ *   mpx_cloud_field_sample's INSIDE and dist of `field` [B,nz,ny,nx] (environment b of THIS call, built by
+ *   mpx_cloud_field_build on `grid`) at c.  Blocked: c is inside the grid AND D < trunc AND
+ *       d <= check_margin + field_slack,   d = ((D - point_radius) - r_s) - clearance
+ *   (mpx_franka_roadmap_cloud's rule, in the same words: d in that order in float32, the right-hand side summed once on
+ *   the host in float32).  A centre outside the grid, or where the field is saturated, counts as FREE; a NaN centre is
+ *   outside the grid and reads no memory.  field == NULL: no environment test (grid is not read); S may then be 0 and the
+ *   self test still runs.
+ * The field is an APPROXIMATION, within (sqrt(3)/2) h of the true distance (see mpx_franka_roadmap_cloud): a row may get
+ * status 2 or 1 where the exact swept-sphere test would not object, and a guide pose may graze the cloud.  Nothing here is
+ * an exact verdict: the poses only GUIDE mpx_franka_follow_cloud, which judges its trajectory by the exact test.
+ * field_slack >= 0 [m] widens the threshold: 0 uses the field as it is, 0.866 h makes the roadmap conservative.
+ * Refused before any launch: what mpx_gripper_roadmap refuses (the options, W, S > 64, env_offset, B x W x 16 >= 2^31, NULL
+ * outputs or operands) and what mpx_franka_roadmap_cloud refuses about the field: a bad grid (with a field), point_radius or
+ * field_slack negative or not finite, a field with S == 0, and a field whose
+ *   trunc <= MPX_FRANKA_MAX_SPHERE_RADIUS + point_radius + max(clearance, 0) + (check_margin + field_slack)
+ * -- the joint roadmap's bound although the gripper's largest sphere is smaller: one rule for every reader of a field.
+ * One workgroup of 256 threads per problem, LDS 8192 B below mpx_gripper_roadmap's (no primitive rows: 33 804 B at 256
+ * nodes), the field read from global memory.  No allocation, no scratch, no global atomics; one kernel on `stream`
+ * (capturable).  B == 0 launches nothing (a bad option is still refused).                                              */
+int mpx_gripper_roadmap_cloud(const float *start_pose, const float *goal_pose, int B, int W, const float *bounds, float finger,
+                              const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                              const float *field, const mpx_field_grid *grid, float point_radius, float field_slack,
+                              const mpx_gripper_roadmap_options *options, uint64_t seed, int64_t env_offset, float *poses,
+                              int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state,
+                              int32_t *rounds, mpx_stream_t stream);
 
 /* mpx_franka_follow against a POINT CLOUD: the same follower -- still the STAND-IN for the reference's Geometric Fabrics
  * expert, NOT Lula's fabric, no parity claimed.  Every clause of mpx_franka_follow's contract holds unchanged -- the state,

@@ -53,6 +53,7 @@ PROTOTYPES = {
     "mpx_franka_plan_cloud": [P, P, I, I, F, P, P, P, P, I, P, P, P, L, I, I, P, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, L, P],
     "mpx_franka_plan_cloud_seeded": [P, P, I, I, F, P, P, P, P, I, P, P, P, L, I, I, P, F, P, ctypes.c_uint64, L, P, I, P, P, P, P, P, P, L, P],
     "mpx_franka_roadmap_cloud": [P, P, I, I, F, P, P, P, P, I, P, P, F, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
+    "mpx_gripper_roadmap_cloud": [P, P, I, I, P, F, P, P, P, I, P, P, F, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_collision_hinge": [P, L, I, I, I, P, P, I, P, P, P, I, F, P, P, L, I, P],
     "mpx_point_match": [P, P, I, I, F, F, P, P, P],
     "mpx_franka_cloud_grad": [P, I, F, P, P, P, I, P, L, I, P, P],

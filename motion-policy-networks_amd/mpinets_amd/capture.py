@@ -157,7 +157,8 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
                   env_offset: int = 0, field=None, ik_options: Optional[dict] = None,
                   plan_options: Optional[dict] = None, global_plan: bool = False,
                   roadmap_options: Optional[dict] = None, follow: bool = False, follow_poses: int = 8,
-                  follow_options: Optional[dict] = None) -> dict:
+                  follow_options: Optional[dict] = None, follow_guide: str = "plan",
+                  gripper_options: Optional[dict] = None) -> dict:
     """From a cloud and a target pose to a checked trajectory: ``robot.franka_ik_cloud`` for the goal configuration, then
     ``robot.franka_plan_cloud`` from ``q_start`` to it, both against the same ``cloud`` (``counts``, ``point_radius``).  The
     optimiser-based counterpart of the reference demo's ``Planner.plan(q0, target_pose, obstacle_pc)``
@@ -180,7 +181,20 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
         (built here when ``field`` is None and shared with the planner); ``follow_options`` are its keyword options.  Adds
         ``followed_trajectory`` [B,T,7] (NaN rows where ``follow_status`` != 0), ``follow_status`` int32 [B] (2 for every row
         without a plan: its guide is NaN), ``follow_bits`` and ``follow_steps`` int32 [B].  The same call with
-        ``max_steps`` and the returned state of ``franka_follow_cloud`` is the controller stepped against that cloud."""
+        ``max_steps`` and the returned state of ``franka_follow_cloud`` is the controller stepped against that cloud.
+    :param follow_guide: "plan" (every key and bit as before: the follower's guide is read off the plan), or "gripper"
+        (needs ``follow``): the guide is ``robot.gripper_roadmap_cloud``'s -- a roadmap for the free-flying gripper through
+        the cloud's distance field, a stand-in for the reference's OMPL end-effector planner, NOT a port -- from the
+        right_gripper pose of ``q_start`` to that of ``q_goal``, at ``follow_poses`` poses, against the same cloud, counts,
+        ``point_radius`` and the one shared field, keyed by ``seed`` / ``env_offset``; ``gripper_options`` are its keyword
+        options (``field_slack`` among them).  A row without an IK goal has a NaN goal pose and gets status 2.  Adds
+        ``follow_guide_poses`` [B,W,4,4] (NaN rows without a path) and ``follow_guide_status`` int32 [B].  The guide no longer
+        needs the optimiser: a row whose plan failed but whose IK succeeded can come back with a ``followed_trajectory``
+        (``follow_status`` 0, free by ``check_cloud``'s test); ``valid`` keeps its meaning (both the IK and the plan)."""
+    if follow_guide not in ("plan", "gripper"):
+        raise ValueError(f"follow_guide must be 'plan' or 'gripper', got {follow_guide!r}")
+    if follow_guide == "gripper" and not follow:
+        raise ValueError("follow_guide='gripper' chooses the follower's guide: it needs follow=True")
     if follow and field is None:  # (one field for the planner and the follower)
         from ._operands import cloud_args
         from .field import DEFAULT_VOXEL, CloudField
@@ -207,7 +221,17 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
 
         B, W = q_start.size(0), int(follow_poses)
         at = [int(round(i * (int(T) - 1) / W)) for i in range(1, W + 1)]
-        guide = frames_to_matrix(franka_fk(traj[:, at].reshape(-1, 7))[:, ft.LINK_ID["right_gripper"]]).reshape(B, W, 4, 4)
+        gripper = ft.LINK_ID["right_gripper"]
+        if follow_guide == "gripper":
+            from .solvers import gripper_roadmap_cloud
+
+            ends = frames_to_matrix(franka_fk(torch.cat([q_start, q_goal]))[:, gripper])  # (a row without a goal: NaN, status 2)
+            guide, extra["follow_guide_status"] = gripper_roadmap_cloud(
+                ends[:B].contiguous(), ends[B:].contiguous(), cloud, counts, field=field, point_radius=point_radius, W=W,
+                seed=seed, env_offset=env_offset, **(gripper_options or {}))
+            extra["follow_guide_poses"] = guide
+        else:
+            guide = frames_to_matrix(franka_fk(traj[:, at].reshape(-1, 7))[:, gripper]).reshape(B, W, 4, 4)
         extra["followed_trajectory"], extra["follow_status"], extra["follow_bits"], extra["follow_steps"] = franka_follow_cloud(
             q_start, guide, cloud, counts, field=field, point_radius=point_radius, T=T, **(follow_options or {}))
     return dict({"q_goal": q_goal, "ik_status": ik_status, "trajectory": traj, "plan_status": plan_status,

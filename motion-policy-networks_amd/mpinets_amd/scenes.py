@@ -352,24 +352,38 @@ def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
 
 
 def _hybrid_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, global_solutions: torch.Tensor,
-                               expert_valid: torch.Tensor, point_radius: float) -> Dict[str, torch.Tensor]:
+                               expert_valid: torch.Tensor, point_radius: float, q_goal: Optional[torch.Tensor] = None,
+                               seed: int = 0, env_offset: int = 0, gripper_guide: bool = False) -> Dict[str, torch.Tensor]:
     """``hybrid_against="cloud"``: ``_hybrid_trajectories`` with ``solvers.franka_follow_cloud`` (still the stand-in for the
     reference's Geometric Fabrics expert, NOT Lula) following the same eight right_gripper poses of the cloud plan against
     the batch's own scene cloud, at the expert's ``point_radius``: the cloud's distance field steers, ``check_cloud``'s test
     judges, so ``hybrid_valid`` and ``expert_valid`` mean free by one and the same test.  One field is built here and
-    handed to the follower."""
+    handed to the follower.
+
+    ``gripper_guide`` (``hybrid_guide="gripper_cloud"``): as in ``_hybrid_trajectories``, the guide is planned for the
+    free-flying gripper, here by ``solvers.gripper_roadmap_cloud`` against the same scene cloud at the same ``point_radius``
+    through that one field, from the right_gripper pose of ``q_start`` to that of ``q_goal``, keyed by the batch's ``seed`` /
+    ``env_offset``.  No fall-back to the global guide: a row without a gripper path hands NaN poses to the follower."""
     from .field import DEFAULT_VOXEL, CloudField
     from .robot import franka_fk, frames_to_matrix
-    from .solvers import FOLLOW_DEFAULTS, franka_follow_cloud, plan_cloud_truncation
+    from .solvers import FOLLOW_DEFAULTS, franka_follow_cloud, gripper_roadmap_cloud, plan_cloud_truncation
 
     B = q_start.size(0)
     at = [int(round(i * (EXPERT_LENGTH - 1) / HYBRID_GUIDE_POSES)) for i in range(1, HYBRID_GUIDE_POSES + 1)]
     gripper = ft.LINK_ID["right_gripper"]
-    guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
     field = CloudField.build(scene_cloud, None, truncation=plan_cloud_truncation(
         point_radius, FOLLOW_DEFAULTS["clearance"], FOLLOW_DEFAULTS["epsilon"], DEFAULT_VOXEL))
+    extra = {}
+    if gripper_guide:
+        ends = frames_to_matrix(franka_fk(torch.cat([q_start, q_goal]))[:, gripper])  # (an invalid row's NaN goal: status 2)
+        guide, guide_status = gripper_roadmap_cloud(ends[:B].contiguous(), ends[B:].contiguous(), scene_cloud, field=field,
+                                                    point_radius=point_radius, W=HYBRID_GUIDE_POSES, seed=seed,
+                                                    env_offset=env_offset)
+        extra = {"hybrid_guide_poses": guide, "hybrid_guide_status": guide_status}
+    else:
+        guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
     traj, status, _, _ = franka_follow_cloud(q_start, guide, scene_cloud, field=field, point_radius=point_radius, T=EXPERT_LENGTH)
-    return dict(hybrid_solutions=traj, hybrid_valid=expert_valid & (status == 0),
+    return dict(extra, hybrid_solutions=traj, hybrid_valid=expert_valid & (status == 0),
                 hybrid_target_pose=frames_to_matrix(franka_fk(traj[:, -1].contiguous())[:, gripper]))
 
 
@@ -443,8 +457,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     cloud test of the plan with the primitive test of the follower.
 
     ``hybrid_against`` (with ``hybrid``; default "primitives", which leaves every key and every bit as it was): "cloud" needs
-    ``expert_from`` "cloud" or "cloud_roadmap" and ``hybrid_guide="global"`` (the gripper roadmap has no cloud form).  The
-    follower is then ``solvers.franka_follow_cloud`` (the same stand-in controller) along the same eight poses of the cloud
+    ``expert_from`` "cloud" or "cloud_roadmap" and ``hybrid_guide`` "global" or "gripper_cloud" ("gripper" plans through the
+    primitives).  The follower is then ``solvers.franka_follow_cloud`` (the same stand-in controller) along the same eight poses of the cloud
     plan, against the same scene cloud at ``expert_point_radius`` through one shared distance field; ``hybrid_valid`` =
     ``expert_valid`` & followed and free by ``check_cloud``'s test, the test the plan was judged by.  The keys are the same
     three, and ``problems_to_dataset(prob, "hybrid_solutions")`` reads them unchanged.
@@ -456,7 +470,11 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     (gen_data.py:156-189); a stand-in for that OMPL planner, not a port, valid by this engine's sphere model.  No fall-back
     between the guides: a row without a gripper path is not ``hybrid_valid``, which still requires ``expert_valid`` as the
     reference requires the global plan.  Also ``hybrid_guide_poses`` [B,8,4,4] (NaN rows without a path) and
-    ``hybrid_guide_status`` int32 [B] (``gripper_roadmap``'s)."""
+    ``hybrid_guide_status`` int32 [B] (``gripper_roadmap``'s).  "gripper_cloud" (only with ``hybrid_against="cloud"``) is the
+    same stage against the scene cloud: ``solvers.gripper_roadmap_cloud`` at ``expert_point_radius``, through the one field
+    the cloud follower reads, with the same two extra keys; its verdicts come from the field, which approximates, so the
+    exact judge stays ``check_cloud``'s test on the follower's trajectory.  "gripper" with ``hybrid_against="cloud"`` is
+    refused."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
@@ -468,14 +486,18 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
         if expert_from not in ("cloud", "cloud_roadmap"):
             raise ValueError("hybrid_against='cloud' needs expert_from='cloud' or 'cloud_roadmap': a plan judged against the "
                              f"primitives is not what the cloud follower would be judged by, got {expert_from!r}")
-        if hybrid_guide != "global":
-            raise ValueError("hybrid_against='cloud' needs hybrid_guide='global': the gripper roadmap has no cloud form")
+        if hybrid_guide == "gripper":
+            raise ValueError("hybrid_against='cloud' needs hybrid_guide='global' or 'gripper_cloud': 'gripper' plans through "
+                             "the primitives, and that gripper roadmap has no cloud form: use 'gripper_cloud'")
     elif hybrid and expert_from in ("cloud", "cloud_roadmap"):  # (``hybrid_valid`` would mix two tests)
         raise ValueError("hybrid=True needs expert_from='primitives' or 'roadmap': the follower runs against the primitives, "
                          "a plan judged against the point cloud is not what it would be judged by "
                          "(hybrid_against='cloud' follows against the cloud instead)")
-    if hybrid_guide not in ("global", "gripper"):
-        raise ValueError(f"hybrid_guide must be 'global' or 'gripper', got {hybrid_guide!r}")
+    if hybrid_guide not in ("global", "gripper", "gripper_cloud"):
+        raise ValueError(f"hybrid_guide must be 'global', 'gripper' or 'gripper_cloud', got {hybrid_guide!r}")
+    if hybrid_guide == "gripper_cloud" and hybrid_against != "cloud":
+        raise ValueError("hybrid_guide='gripper_cloud' plans the gripper against the scene cloud: it needs "
+                         "hybrid_against='cloud' ('gripper' plans it through the primitives)")
     if expert_from not in ("primitives", "cloud", "roadmap", "cloud_roadmap"):
         raise ValueError(f"expert_from must be 'primitives', 'cloud', 'roadmap' or 'cloud_roadmap', got {expert_from!r}")
 
@@ -519,7 +541,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     np.random.set_state(state)
     if hybrid and hybrid_against == "cloud":
         out.update(_hybrid_trajectories_cloud(xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3], q,
-                                              out["global_solutions"], out["expert_valid"], expert_point_radius))
+                                              out["global_solutions"], out["expert_valid"], expert_point_radius, q_goal, seed,
+                                              env_offset, gripper_guide=hybrid_guide == "gripper_cloud"))
     elif hybrid:
         out.update(_hybrid_trajectories(out, q, out["global_solutions"], out["expert_valid"], q_goal, seed, env_offset,
                                         gripper_guide=hybrid_guide == "gripper"))

@@ -269,6 +269,24 @@ def franka_plan_global(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None
     return tuple(out) + (rm_status,)
 
 
+def _gripper_inputs(start_pose: torch.Tensor, goal_pose: torch.Tensor, bounds, *others):
+    """What both gripper roadmaps start from: the two pose batches [B,4,4] and the other tensors of the call on the current
+    GPU -> B, the device, the poses as contiguous float32 and the position boxes [B,2,3] (``bounds`` None: the box hull of the
+    two positions, grown by ``GRIPPER_ROADMAP_BOUNDS_PAD`` per side)."""
+    _lib.require_cuda(start_pose, goal_pose, *others)
+    assert start_pose.ndim == 3 and tuple(start_pose.shape[1:]) == (4, 4) and goal_pose.shape == start_pose.shape
+    B, dev = start_pose.size(0), start_pose.device
+    sp, gp = _lib.f32c(start_pose), _lib.f32c(goal_pose)
+    if bounds is None:
+        ends = torch.stack((sp[:, :3, 3], gp[:, :3, 3]), 1)
+        box = torch.stack((ends.amin(1) - GRIPPER_ROADMAP_BOUNDS_PAD, ends.amax(1) + GRIPPER_ROADMAP_BOUNDS_PAD), 1)
+    else:
+        box = torch.as_tensor(bounds, dtype=torch.float32, device=dev)
+        assert tuple(box.shape) in ((2, 3), (B, 2, 3))
+        box = box.expand(B, 2, 3)
+    return B, dev, sp, gp, _lib.f32c(box)
+
+
 def gripper_roadmap(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=None, cylinders=None, W: int = 8, bounds=None,
                     seed: int = 0, env_offset: int = 0, return_graph: bool = False, with_base_link: bool = False,
                     finger: float = ft.FINGER_OPENING, **options):
@@ -292,20 +310,9 @@ def gripper_roadmap(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=N
         non-finite, outside ``bounds`` or invalid); with ``return_graph`` also ``path`` int32 [B,V], ``hops`` int32 [B],
         ``nodes`` [B,V,7] (position, quaternion x y z w), ``edge_state`` uint8 [B,V,V] and ``rounds`` int32 [B], as
         ``franka_roadmap`` returns them."""
-    _lib.require_cuda(start_pose, goal_pose)
-    assert start_pose.ndim == 3 and tuple(start_pose.shape[1:]) == (4, 4) and goal_pose.shape == start_pose.shape
-    B, dev = start_pose.size(0), start_pose.device
-    sp, gp = _lib.f32c(start_pose), _lib.f32c(goal_pose)
+    B, dev, sp, gp, box = _gripper_inputs(start_pose, goal_pose, bounds)
     copt, o = _gripper_roadmap_options("gripper_roadmap", options)
     V, W = max(int(o["nodes"]), 0), int(W)
-    if bounds is None:
-        ends = torch.stack((sp[:, :3, 3], gp[:, :3, 3]), 1)
-        box = torch.stack((ends.amin(1) - GRIPPER_ROADMAP_BOUNDS_PAD, ends.amax(1) + GRIPPER_ROADMAP_BOUNDS_PAD), 1)
-    else:
-        box = torch.as_tensor(bounds, dtype=torch.float32, device=dev)
-        assert tuple(box.shape) in ((2, 3), (B, 2, 3))
-        box = box.expand(B, 2, 3)
-    box = _lib.f32c(box)
     prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
     out = _roadmap_outputs(B, (max(W, 0), 4, 4), V, dev, return_graph)
     _lib.call("mpx_gripper_roadmap", sp.data_ptr(), gp.data_ptr(), B, W, box.data_ptr(), float(finger), *prims,
@@ -556,6 +563,47 @@ def franka_roadmap_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: Opt
               None if field is None else ctypes.byref(field.grid), float(point_radius), float(field_slack),
               *options_tail(copt, seed, env_offset), *_ptrs(out))
     return out if return_graph else out[:4]
+
+
+def gripper_roadmap_cloud(start_pose: torch.Tensor, goal_pose: torch.Tensor, cloud: Optional[torch.Tensor],
+                          counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, field_slack: float = 0.0,
+                          W: int = 8, bounds=None, seed: int = 0, env_offset: int = 0, return_graph: bool = False,
+                          with_base_link: bool = False, finger: float = ft.FINGER_OPENING, **options):
+    """``gripper_roadmap`` against one POINT CLOUD per environment (csrc/gripper_roadmap_cloud.hip): the guide poses
+    ``franka_follow_cloud`` is handed where a captured cloud has no primitives to plan the gripper through.  The same
+    stand-in (NOT a port of the reference's OMPL planner), the same nodes (the same seed draws the same nodes, bit for bit),
+    metric, edges, search, statuses and guide poses, with the cloud's truncated distance field as the environment test.  A
+    gripper sphere blocks a pose when its centre is inside the grid, the field is not saturated there and
+    ``((D - point_radius) - r) - clearance <= check_margin + field_slack``; outside the grid and where the field is
+    saturated it counts as free.  The field is an APPROXIMATION: the trilinear interpolant is within (sqrt(3)/2) x voxel of
+    the true distance, so a row may get status 2 or 1 where ``check_cloud`` would not object, and a guide pose may graze
+    the cloud.  Nothing here is an exact verdict: the exact judge is ``check_cloud`` on whatever trajectory the follower
+    produces along these poses.
+
+    :param start_pose, goal_pose, W, bounds: as for ``gripper_roadmap``
+    :param cloud, counts: as for ``franka_roadmap_cloud``; only used to build the field.  None with ``field`` None: no
+        environment (every pose that passes the self test is valid)
+    :param field: a ``CloudField`` of the cloud (batch B), or None: one is built on the default grid with
+        ``plan_cloud_truncation(point_radius, clearance)`` at the follower's default ``epsilon``
+    :param field_slack: >= 0 [m], added to the threshold: 0 uses the field as it is (unbiased), ``0.866 * voxel`` makes the
+        roadmap conservative
+    :param options: the fields of ``mpx_gripper_roadmap_options``, see ``GRIPPER_ROADMAP_DEFAULTS``
+    :returns: what ``gripper_roadmap`` returns."""
+    who = "gripper_roadmap_cloud"
+    B, dev, sp, gp, box = _gripper_inputs(start_pose, goal_pose, bounds, cloud, counts)
+    copt, o = _gripper_roadmap_options(who, options)
+    V, W = max(int(o["nodes"]), 0), int(W)
+    if cloud is not None or field is not None:
+        cn = None if cloud is None else cloud_args(who, cloud, counts, B, point_radius)[1]
+        field = _plan_cloud_field(who, cloud, cn, field, B, point_radius, o["clearance"], FOLLOW_DEFAULTS["epsilon"],
+                                  with_base_link)
+    sc, sr, sl = sphere_table(dev, with_base_link)
+    out = _roadmap_outputs(B, (max(W, 0), 4, 4), V, dev, return_graph)
+    _lib.call("mpx_gripper_roadmap_cloud", sp.data_ptr(), gp.data_ptr(), B, W, box.data_ptr(), float(finger), sc.data_ptr(),
+              sr.data_ptr(), sl.data_ptr(), int(sc.size(0)), None if field is None else field.values.data_ptr(),
+              None if field is None else ctypes.byref(field.grid), float(point_radius), float(field_slack),
+              *options_tail(copt, seed, env_offset), *_ptrs(out))
+    return out if return_graph else out[:2]
 
 
 def franka_plan_global_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.Tensor,
