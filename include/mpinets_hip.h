@@ -30,6 +30,7 @@ typedef void *mpx_stream_t;
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
 int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding):
+                          the form query mpx_linear_form; 341 (unchanged, likewise):
                           mpx_gripper_roadmap_cloud; 341 (unchanged, likewise): mpx_franka_follow_cloud,
                           mpx_franka_follow_cloud_scratch; 341 (unchanged, likewise): mpx_franka_roadmap_cloud,
                           mpx_franka_plan_cloud_seeded, MPX_FRANKA_MAX_SPHERE_RADIUS; 341 (unchanged, likewise): mpx_gripper_roadmap,
@@ -1085,6 +1086,13 @@ int mpx_franka_collision_route(int B, int T, int S, int M1, int M2, int frames_a
  * slices of K, k per slice.  (mpx_linear's row-per-lane form for N = 128, K = 68 and the DMA staging of the tile kernel
  * also depend on the operands' addresses and strides; they replace form 1 only.)                                        */
 int mpx_linear_route(int M, int N, int K, int32_t *route);
+/* What mpx_linear would launch for exactly these operands (the same arguments, checked the same way; non-zero where
+ * mpx_linear refuses them or M < 1).  form[3]: form[0] as route[0] above; form[1] = 1: the row-per-lane kernel (N = 128,
+ * K = 68, no bias, no activation, ldx even, ldy % 4 == 0, x and w 8-byte and y 16-byte aligned, more rows than the gemv
+ * form takes); form[2] = 1: the first slab of rows takes the tile kernel and stages its operands by DMA (K % 16 == 0 and
+ * operands a 32-bit byte offset spans).  The predicates are the launcher's own.                                          */
+int mpx_linear_form(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K, int act,
+                    const float *y, int ldy, int32_t *form);
 /* mpx_linear_wgrad / _bf16x3, route[3]: tile (64 or 128), splits over the rows (mpx_linear_wgrad_scratch = splits *
  * (N K + N) floats; 1: the gradient is written directly when db follows dw), rows per split.                            */
 int mpx_linear_wgrad_route(int M, int N, int K, int32_t *route);

@@ -428,6 +428,11 @@ static bool rowlane_ok(const float *x, int ldx, const float *w, const float *bia
   return N == 128 && K == 68 && bias == nullptr && act == MPX_ACT_NONE && ldx % 2 == 0 && ldy % 4 == 0 &&
          (((uintptr_t)x | (uintptr_t)w) & 7) == 0 && ((uintptr_t)y & 15) == 0;
 }
+// mpx_linear's choice of the kernel above (a few rows take the gemv kernel)
+static bool rowlane_taken(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K, int act, const float *y,
+                          int ldy) {
+  return linear_route(M, N, K).form != LINEAR_GEMV && rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy);
+}
 
 // What a linear_kernel launch adds to x . w^T (linear_launch; the defaults: nothing).
 struct LinearEpi {
@@ -441,14 +446,18 @@ struct LinearEpi {
   bool gemv = false;               // a slab of <= 8 rows takes the gemv kernel (mpx_linear)
 };
 
+// rows of one linear_kernel launch, and of the slab that starts at row m0 (linear_launch; mpx_linear_form)
+static int64_t linear_slab(int ldx) { return mpx_row_slab(BM, (int64_t)ldx * 4); }
+static int linear_slab_rows(int64_t M, int64_t m0, int64_t slab) { return (int)(M - m0 < slab ? M - m0 : slab); }
+
 // The one launch site of linear_kernel.  Rows past one launch are walked in slabs (common.h); per slab: the route, the row
 // operands' offsets, and the zeroing of the row-max output in front of its kernel.  Launch errors: the caller's check.
 template <bool POOL>
 static int linear_launch(const char *name, const float *x, int ldx, const float *w, int M, int N, int K, float *y, int ldy,
                          const LinearEpi &e, mpx_stream_t stream) {
-  const int64_t slab = mpx_row_slab(BM, (int64_t)ldx * 4);  // (split-K: M <= 1024, one slab)
+  const int64_t slab = linear_slab(ldx);  // (split-K: M <= 1024, one slab)
   for (int64_t m0 = 0; m0 < M; m0 += slab) {
-    const int m = (int)(M - m0 < slab ? M - m0 : slab);
+    const int m = linear_slab_rows(M, m0, slab);
     const float *xs = x + m0 * ldx;
     float *ys = e.seg ? y : y + (POOL ? m0 / BM : m0) * ldy;  // (the keys are per segment, not per row)
     if (e.gemv && linear_route(m, N, K).form == LINEAR_GEMV) {
@@ -488,7 +497,7 @@ MPX_EXPORT int mpx_linear(const float *x, int ldx, const float *w, const float *
   MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear: unknown activation %d", act);
   if (M == 0) return 0;
   // short K, 128 outputs: a row per lane, W in registers (every M: one rounding order; a few rows take the gemv kernel)
-  if (linear_route(M, N, K).form != LINEAR_GEMV && rowlane_ok(x, ldx, w, bias, N, K, act, y, ldy)) {
+  if (rowlane_taken(x, ldx, w, bias, M, N, K, act, y, ldy)) {
     int cus = mpx_cu_count();
     if (cus <= 0) cus = 256;
     const int64_t tiles = ((int64_t)M + 31) / 32, waves = (int64_t)cus * 4 * MPX_ROWLANE_WAVES;
@@ -534,6 +543,19 @@ __global__ void __launch_bounds__(256)
 MPX_EXPORT int mpx_linear_route(int M, int N, int K, int32_t *route) {
   const LinearRoute r = linear_route(M, N, K);
   route[0] = r.form, route[1] = r.S, route[2] = r.kslice;
+  return 0;
+}
+// What mpx_linear would launch for exactly these operands (a host call: nothing is launched, no operand is read).  The
+// predicates are mpx_linear's and linear_launch's own.
+MPX_EXPORT int mpx_linear_form(const float *x, int ldx, const float *w, const float *bias, int M, int N, int K, int act,
+                               const float *y, int ldy, int32_t *form) {
+  if (linear_check("mpx_linear_form", x, ldx, w, M, N, K, ldy)) return 1;
+  MPX_REQUIRE(act >= 0 && act <= 2, "mpx_linear_form: unknown activation %d", act);
+  MPX_REQUIRE(M >= 1 && form != nullptr, "mpx_linear_form: no rows, or no place for the answer");
+  const int m = linear_slab_rows(M, 0, linear_slab(ldx));  // the first slab
+  form[0] = linear_route(M, N, K).form;
+  form[1] = rowlane_taken(x, ldx, w, bias, M, N, K, act, y, ldy) ? 1 : 0;
+  form[2] = !form[1] && linear_route(m, N, K).form != LINEAR_GEMV && dma_ok(m, N, K, ldx, K) ? 1 : 0;
   return 0;
 }
 MPX_EXPORT int64_t mpx_linear_workspace(int M, int N, int K) {

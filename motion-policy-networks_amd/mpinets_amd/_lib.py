@@ -81,6 +81,7 @@ PROTOTYPES = {
     "mpx_fps_route": [I, I, P],
     "mpx_franka_collision_route": [I, I, I, I, I, I, P],
     "mpx_linear_route": [I, I, I, P],
+    "mpx_linear_form": [P, I, P, P, I, I, I, I, P, I, P],
     "mpx_linear_wgrad_route": [I, I, I, P],
     "mpx_pool_wgrad_route": [L, I, I, P],
     "mpx_sa_mlp_route": [I, I, I, I, I, I, I, I, I, P],

@@ -57,6 +57,13 @@ def linear_route(M, N, K):
     return ("gemv", "tile", "split-K")[_query("mpx_linear_route", 3, M, N, K)[0]]
 
 
+def linear_form(x, ldx, w, bias, M, N, K, act, y, ldy):
+    """-> (route, rowlane, dma) of ``mpx_linear`` for exactly these operands (addresses as integers, None = NULL): the
+    ``linear_route`` name, whether the row-per-lane kernel is launched, whether the first slab's tile kernel stages by DMA."""
+    form, rowlane, dma = _query("mpx_linear_form", 3, x, ldx, w, bias, M, N, K, act, y, ldy)
+    return ("gemv", "tile", "split-K")[form], bool(rowlane), bool(dma)
+
+
 def wgrad_route(M, N, K):
     return WgradRoute(*_query("mpx_linear_wgrad_route", 3, M, N, K))
 
