@@ -30,6 +30,7 @@ typedef void *mpx_stream_t;
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
 int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding):
+                          mpx_task_candidates, struct mpx_task_candidates_options; 341 (unchanged, likewise):
                           the form query mpx_linear_form; 341 (unchanged, likewise):
                           mpx_gripper_roadmap_cloud; 341 (unchanged, likewise): mpx_franka_follow_cloud,
                           mpx_franka_follow_cloud_scratch; 341 (unchanged, likewise): mpx_franka_roadmap_cloud,
@@ -575,6 +576,74 @@ int mpx_gripper_roadmap(const float *start_pose, const float *goal_pose, int B, 
                         const mpx_gripper_roadmap_options *options, uint64_t seed, int64_t env_offset, float *poses,
                         int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state, int32_t *rounds,
                         mpx_stream_t stream);
+
+/* TASK-ORIENTED gripper pose candidates: where the reference's scene generators draw a start or goal ON a scene's supports
+ * (tabletop_environment.py:354-404, a point on a table top lifted onto the object it lies on, raised 1 to 12 cm, the gripper
+ * pointing down; cubby_environment.py:440-549, a point inside a pocket, the gripper reaching in) and keep a draw when the
+ * free-flying gripper is clear of the scene.  A restatement of those DISTRIBUTIONS, judged by this engine's sphere model
+ * (the hand and fingertip spheres of the table, mpx_gripper_roadmap's gripper), not by PyBullet's meshes; the IK half of
+ * the reference's test is mpx_franka_ik on the poses this entry returns.  One workgroup per problem, draw n on thread n;
+ * the result depends on the inputs alone.
+ *   support_boxes [B,NS,12]: centre (3), dims (3), UNIT quaternion w x y z (4), approach (1: the world yaw of the axis the
+ *   gripper reaches along, volumes only), weight (1).  support_kind int32 [B,NS]: 0 padding, 1 a SURFACE (the box's top
+ *   face, local z = +dims_z / 2), 2 a VOLUME (the box).  1 <= NS <= MPX_TASK_MAX_SUPPORTS.  exclude int32 [B] or NULL: the
+ *   one support row of problem b that is not drawn from (-1 or out of range: none).  The sphere table and the primitives
+ *   exactly as for mpx_gripper_roadmap (S <= 64, M1, M2 <= 64, zero-volume rows skipped); the primitives are ASSUMED to be
+ *   rotated about the world z axis only: the top of a primitive is taken as -f_23 + size_z / 2, where f_23 is row 2,
+ *   column 3 of its inverse frame (mpx_prim_frames: that entry is -centre_z exactly for such a rotation) and size_z the
+ *   cuboid's third dim or the cylinder's height.
+ *   Draw n = 0 .. N-1 (N = options->draws) of problem b: words 0-3 = Philox4x32-10(counter = {2n, GLOBAL problem id =
+ *   env_offset + b, stream 18, options->role}, key = seed), words 4-7 the block with counter word 0 = 2n + 1; u_i = u01 of
+ *   word i (top 24 bits / 2^24).  u_0 picks the support, u_1 u_2 u_3 the position, u_4 u_5 u_6 the orientation, u_7 is
+ *   not used.  role 0 draws a start, role 1 a goal: two independent streams.
+ *   1 Support.  w_s = weight_s where kind_s != 0, s != exclude_b and weight_s > 0, else 0 (NaN: 0); c_s = c_{s-1} + w_s
+ *   in float32, s ascending; total = c_{NS-1}.  The draw's support is the first s with c_s > u_0 total.  total = 0:
+ *   the problem has no live support and count = 0.
+ *   2 Position.  With R_s the matrix of the support's quaternion (mpx_gripper_roadmap's R, its (x, y, z, w) read from
+ *   (w, x, y, z) here) and l = ((u_1 - 0.5f) dims_x, (u_2 - 0.5f) dims_y, l_z): p = R_s l + centre, the product as
+ *   fma(R_i2, l_z, fma(R_i1, l_y, R_i0 l_x)) + centre_i.  Volume: l_z = (u_3 - 0.5f) dims_z.  Surface: l_z = 0.5f dims_z;
+ *   then every live primitive is visited in index order, cuboids before cylinders, and where its signed distance
+ *   (mpx_cuboid_sdf / mpx_cylinder_sdf) to the CURRENT p is <= 0.01f, p_z becomes that primitive's top (the reference walks
+ *   its objects the same way, against the already lifted point); then p_z += fma(1 - sqrtf(u_3), 0.11f, 0.01f): 1 to 12 cm,
+ *   densest near the surface.
+ *   3 Orientation.  Surface: roll = fma(u_4, pi/2, 3 pi/4), pitch = fma(u_5, pi/4, -pi/8), yaw = fma(u_6, pi, -pi/2)
+ *   (roll in 3 pi/4 .. 5 pi/4, pitch +-pi/8, yaw +-pi/2), R = Rz(yaw) Ry(pitch) Rx(roll):
+ *     R = [cy cp, cy sp sr - sy cr, cy sp cr + sy sr;  sy cp, sy sp sr + cy cr, sy sp cr - cy sr;  -sp, cp sr, cp cr],
+ *   every product and sum rounded on its own, left to right (the convention is this entry's: geometrout's SO3.from_rpy is
+ *   not restated anywhere in this project).  Volume: a = approach + fma(u_4, pi/2, -pi/4); the gripper's z axis is
+ *   (cos a, sin a, 0), its x axis (0, 0, -1), y = z x x:  R = [0, -sin a, cos a;  0, cos a, sin a;  -1, 0, 0].  The
+ *   constants are the float32 nearest to pi/2, pi/4, pi, 3 pi/4, pi/8; sines and cosines are float32 (within 2e-7).
+ *   4 Verdict.  The draw is FREE when every entry of (R, p) is finite and the pose (R, p) is valid by
+ *   mpx_gripper_roadmap's clause with check_margin 0: no gripper sphere with sdf <= r_s + clearance (with S = 0 or no live
+ *   primitive this test passes), and with test_self none of the origins of frames 9, 12, 13 inside
+ *   0.15 + 0.01 + self_margin of the base segment.
+ *   Outputs, 1 <= C <= MPX_TASK_MAX_CANDIDATES: the first C free draws IN DRAW ORDER (an ordered compaction across the
+ *   workgroup's waves: wave ballots and popcounts, no atomics).  count int32 [B] = min(C, free draws); for j < count:
+ *   poses [B,C,4,4] row-major = [R | p; 0 0 0 1], draw int32 [B,C] = n (strictly ascending in j), support int32 [B,C] = s.
+ *   Rows j >= count: all 16 pose entries NaN, draw = support = -1.
+ *   Refused before any launch: draws outside 1 .. MPX_TASK_MAX_DRAWS, C or NS out of range, role not 0 or 1, clearance NaN,
+ *   self_margin negative or NaN, S > 64, M1 or M2 > 64, env_offset + B > 2^32, B x C x 16 >= 2^31, NULL operands.  B == 0
+ *   launches nothing.  One launch of B workgroups of 128 threads on grid.x, like the other per-problem entries (no slab
+ *   walk: grid.x reaches 2^31 - 1); 9.3 kB of LDS, no scratch, no allocation, no global atomics; enqueued on `stream`
+ *   (capturable).                                                                                                        */
+#define MPX_TASK_MAX_DRAWS 128
+#define MPX_TASK_MAX_CANDIDATES 16
+#define MPX_TASK_MAX_SUPPORTS 64
+#define MPX_TASK_DEFAULT_DRAWS 100 /* the reference's tries per candidate */
+typedef struct mpx_task_candidates_options { /* NULL options: draws MPX_TASK_DEFAULT_DRAWS, clearance 0, test_self 1,
+                                                self_margin 0, role 0 */
+  int draws;                                 /* 1 .. MPX_TASK_MAX_DRAWS: one thread each                       */
+  float clearance;                           /* [m], added to the radii                                        */
+  int test_self;                             /* non-zero: the body column rejects a draw                       */
+  float self_margin;                         /* >= 0 [m], added to the self distances                          */
+  int role;                                  /* 0 a start, 1 a goal: counter word 3 of every draw              */
+} mpx_task_candidates_options;
+int mpx_task_candidates(const float *support_boxes, const int32_t *support_kind, int B, int NS, const int32_t *exclude, int C,
+                        float finger, const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                        const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                        const float *cyl_radii, const float *cyl_heights, int M2,
+                        const mpx_task_candidates_options *options, uint64_t seed, int64_t env_offset, float *poses,
+                        int32_t *draw, int32_t *support, int32_t *count, mpx_stream_t stream);
 
 /* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
  * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at

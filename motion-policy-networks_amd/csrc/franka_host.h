@@ -1,5 +1,5 @@
 // franka_host.h -- host-only (no __device__ code): the option defaults, the argument checks and the cloud launch table that
-// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, follow.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
+// the Franka geometry entries share (ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, task_candidates.hip, follow.hip, cloud_collision.hip, cloud_field.hip; cloud_clean.hip for
 // env_offset and scratch size); a new entry takes its defaults and its checks from here, and states a refusal of its own only
 // where no other entry has it.  Each takes the name of the entry the caller invoked, reports through MPX_REQUIRE and
 // returns 0 or 1 (field_grid_check's idiom).  Sizes and values are checked before an entry's "nothing to do" return, pointers after.
@@ -30,6 +30,7 @@ static inline mpx_gripper_roadmap_options gripper_roadmap_defaults() {
           MPX_GRIPPER_ROADMAP_DEFAULT_ORIENT_SPREAD, __builtin_inff(), MPX_GRIPPER_ROADMAP_DEFAULT_MAX_ROUNDS,
           MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
 }
+static inline mpx_task_candidates_options task_candidates_defaults() { return {MPX_TASK_DEFAULT_DRAWS, 0.0f, 1, 0.0f, 0}; }
 static inline mpx_follow_options franka_follow_defaults() {
   return {MPX_FOLLOW_DEFAULT_DT, MPX_FOLLOW_DEFAULT_MAX_STEPS, MPX_FOLLOW_DEFAULT_ATTRACT, MPX_FOLLOW_DEFAULT_DAMPING,
           MPX_IK_DEFAULT_LAMBDA, MPX_IK_DEFAULT_STEP_CLIP, MPX_FOLLOW_DEFAULT_REPEL, MPX_PLAN_DEFAULT_EPSILON, 0.0f,
@@ -113,6 +114,18 @@ static inline int gripper_roadmap_options_check(const char *who, int W, const mp
   MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
   MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
   MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
+  return 0;
+}
+// (NS supports per problem, C kept candidates)
+static inline int task_candidates_options_check(const char *who, int NS, int C, const mpx_task_candidates_options &opt) {
+  MPX_REQUIRE(opt.draws >= 1 && opt.draws <= MPX_TASK_MAX_DRAWS, "%s: draws = %d, need 1 .. %d (one thread each)", who, opt.draws,
+              MPX_TASK_MAX_DRAWS);
+  MPX_REQUIRE(C >= 1 && C <= MPX_TASK_MAX_CANDIDATES, "%s: C = %d kept candidates, need 1 .. %d", who, C, MPX_TASK_MAX_CANDIDATES);
+  MPX_REQUIRE(NS >= 1 && NS <= MPX_TASK_MAX_SUPPORTS, "%s: NS = %d supports per problem, need 1 .. %d", who, NS,
+              MPX_TASK_MAX_SUPPORTS);
+  MPX_REQUIRE(opt.role == 0 || opt.role == 1, "%s: role = %d, need 0 (start) or 1 (goal)", who, opt.role);
+  MPX_REQUIRE(opt.self_margin >= 0.0f, "%s: negative (or NaN) self_margin", who);
   MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
   return 0;
 }

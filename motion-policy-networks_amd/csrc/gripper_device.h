@@ -1,5 +1,6 @@
 // gripper_device.h -- the free-flying gripper as the two gripper roadmap kernels take it (gripper_roadmap.hip against
-// primitives, gripper_roadmap_cloud.hip against a distance field): a node (position, unit quaternion x y z w) from a pose
+// primitives, gripper_roadmap_cloud.hip against a distance field) and, for its validity against primitives,
+// task_candidates.hip: a node (position, unit quaternion x y z w) from a pose
 // and back, the SE(3) metric, the nlerp edge pose and the self half of a pose's validity.  One text for both; what differs
 // between them (the LDS layout, the environment half of the validity, the host entry) stays in each .hip, and the statement
 // blocks they share are gripper_spheres.inc, gripper_nodes.inc and gripper_tail.inc.  The contract is stated in
@@ -7,6 +8,7 @@
 #pragma once
 #include "common.h"
 #include "plan_device.h"
+#include "plan_prims_device.h"
 
 enum { STREAM_GRIPPER_ROADMAP = 17 };
 enum { GRM_MAX_SPHERES = 64 };
@@ -96,4 +98,30 @@ __device__ __forceinline__ bool gripper_self_hit(const Rigid &g, float finger, f
   rigid_apply(g, 0.0f, finger, tip, o.t[0], o.t[1], o.t[2]);
   hit |= franka_self_hit<13>(o, self_margin);
   return hit;
+}
+
+// the planner's validity clause on the gripper alone, against a problem's live primitives (the LDS rows of
+// franka_live_rows.inc, the gripper's sphere rows of gripper_spheres.inc): a sphere with sdf <= r_s + reach, or (test_self)
+// the origin of the hand or a fingertip frame inside the body column.  gripper_roadmap.hip judges its nodes and edge poses
+// by it, task_candidates.hip its drawn poses (which are frames already: gripper_frame_hit).
+__device__ __forceinline__ bool gripper_frame_hit(const Rigid &g, float finger, const float *gsph, int n_g,
+                                                  const float *prim_rows, int n_cub, int n_cyl, float reach, bool test_self,
+                                                  float self_margin) {
+  bool hit = false;
+  if (n_cub + n_cyl > 0) {
+    for (int s = 0; s < n_g; ++s) {
+      float x, y, z;
+      rigid_apply(g, gsph[4 * s + 0], gsph[4 * s + 1], gsph[4 * s + 2], x, y, z);
+      int arg;
+      const float best = plan_min_sdf(prim_rows, n_cub, n_cyl, x, y, z, arg);
+      hit |= best <= gsph[4 * s + 3] + reach;
+    }
+  }
+  if (test_self) hit |= gripper_self_hit(g, finger, self_margin);
+  return hit;
+}
+__device__ __forceinline__ bool gripper_pose_hit(const float *node, float finger, const float *gsph, int n_g,
+                                                 const float *prim_rows, int n_cub, int n_cyl, float reach, bool test_self,
+                                                 float self_margin) {
+  return gripper_frame_hit(gripper_frame(node), finger, gsph, n_g, prim_rows, n_cub, n_cyl, reach, test_self, self_margin);
 }

@@ -12,7 +12,7 @@
 // untested edges of the round's path (passes of 256), thread = output pose (W <= 64).  Every branch around a barrier is
 // workgroup-uniform: it reads a value from LDS behind a barrier, or a barrier's own reduction.  The search is the statement
 // block both kernels include (roadmap_search.inc), with the gripper's metric and edge pose (gripper_device.h) and this
-// file's validity.  The sphere set, the node draw and the tail are the statement blocks gripper_roadmap_cloud.hip runs too
+// file's validity (gripper_pose_hit, which gripper_device.h states for this kernel and task_candidates.hip).  The sphere set, the node draw and the tail are the statement blocks gripper_roadmap_cloud.hip runs too
 // (gripper_spheres.inc, gripper_nodes.inc, gripper_tail.inc).
 #include "common.h"
 #include "franka_host.h"
@@ -26,26 +26,6 @@
 __host__ __device__ static inline size_t gripper_roadmap_lds_words(int V) {
   return (size_t)128 * 16 + (size_t)GRM_MAX_SPHERES * 4 + (size_t)V * 7 + 2 * (size_t)V + 6 * (size_t)V + (size_t)V + 1 + 1 +
          1 + ((size_t)V * V + 15) / 16;
-}
-
-// the planner's validity clause on the gripper alone: a sphere with sdf <= r_s + reach, or (test_self) the origin of the
-// hand or a fingertip frame inside the body column
-__device__ __forceinline__ bool gripper_pose_hit(const float *node, float finger, const float *gsph, int n_g,
-                                                 const float *prim_rows, int n_cub, int n_cyl, float reach, bool test_self,
-                                                 float self_margin) {
-  const Rigid g = gripper_frame(node);
-  bool hit = false;
-  if (n_cub + n_cyl > 0) {
-    for (int s = 0; s < n_g; ++s) {
-      float x, y, z;
-      rigid_apply(g, gsph[4 * s + 0], gsph[4 * s + 1], gsph[4 * s + 2], x, y, z);
-      int arg;
-      const float best = plan_min_sdf(prim_rows, n_cub, n_cyl, x, y, z, arg);
-      hit |= best <= gsph[4 * s + 3] + reach;
-    }
-  }
-  if (test_self) hit |= gripper_self_hit(g, finger, self_margin);
-  return hit;
 }
 
 __global__ void __launch_bounds__(ROADMAP_THREADS)

@@ -47,6 +47,7 @@ PROTOTYPES = {
     "mpx_franka_follow_cloud_scratch": [I, I, I],
     "mpx_franka_follow_cloud": [P, P, I, I, I, F, P, P, P, P, I, P, P, P, L, I, I, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, P],
     "mpx_gripper_roadmap": [P, P, I, I, P, F, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
+    "mpx_task_candidates": [P, P, I, I, P, I, F, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
     "mpx_franka_plan_cloud_scratch": [I, I, I, I],
@@ -166,6 +167,11 @@ class GripperRoadmapOptions(ctypes.Structure):
     _fields_ = [("nodes", c_int), ("resolution", c_float), ("rot_weight", c_float), ("orient_spread", c_float),
                 ("connect_radius", c_float), ("max_rounds", c_int), ("check_margin", c_float), ("clearance", c_float),
                 ("check_self", c_int)]
+
+
+class TaskCandidatesOptions(ctypes.Structure):
+    """``mpx_task_candidates_options`` (include/mpinets_hip.h)."""
+    _fields_ = [("draws", c_int), ("clearance", c_float), ("test_self", c_int), ("self_margin", c_float), ("role", c_int)]
 
 
 class FollowOptions(ctypes.Structure):

@@ -35,7 +35,18 @@ def _yaw_quat(yaw):
     return q
 
 
-def _tabletop(rng, M1, M2):
+SUPPORT_PADDING, SUPPORT_SURFACE, SUPPORT_VOLUME = 0, 1, 2  # ``support_kind`` (``solvers.TASK_*``)
+
+
+def _support(supports, kind, centre, dims, quat, approach, weight):
+    """One row of ``make_task_scenes``' ``support_boxes`` / ``support_kind`` (``supports`` None: ``make_scenes``, nothing kept).
+    Nothing here draws from an rng: the supports are read off what a generator has already placed."""
+    if supports is not None:
+        supports.append((kind, np.concatenate([np.asarray(centre, float), np.asarray(dims, float), np.asarray(quat, float),
+                                               [float(approach), float(weight)]])))
+
+
+def _tabletop(rng, M1, M2, supports=None):
     cc, cd, cq = np.zeros((M1, 3)), np.zeros((M1, 3)), np.tile([1.0, 0, 0, 0], (M1, 1))
     yc, yr, yh, yq = np.zeros((M2, 3)), np.zeros((M2, 1)), np.zeros((M2, 1)), np.tile([1.0, 0, 0, 0], (M2, 1))
     h = 0.0 if rng.random() < 0.35 else rng.uniform(0.0, 0.4)
@@ -44,10 +55,12 @@ def _tabletop(rng, M1, M2):
     thick = 0.05
     n = 0
     cc[n], cd[n] = [(x0 + x1) / 2, 0.0, h - thick / 2], [x1 - x0, w, thick]
+    _support(supports, SUPPORT_SURFACE, cc[n], cd[n], cq[n], 0.0, cd[n][0] * cd[n][1])  # (weight: the top face's area)
     n += 1
     if rng.random() < 0.5:  # side table
         side = rng.choice([-1.0, 1.0])
         cc[n], cd[n] = [0.0, side * (w / 4 + 0.45), h - thick / 2], [0.9, w / 2, thick]
+        _support(supports, SUPPORT_SURFACE, cc[n], cd[n], cq[n], 0.0, cd[n][0] * cd[n][1])
         n += 1
     cc[n], cd[n] = [-0.35, 0.0, -0.025], [0.6, 0.6, 0.05]  # mount table under the robot
     n += 1
@@ -66,7 +79,7 @@ def _tabletop(rng, M1, M2):
     return cc, cd, cq, yc, yr, yh, yq
 
 
-def _cubby(rng, M1, M2):
+def _cubby(rng, M1, M2, supports=None):
     cc, cd, cq = np.zeros((M1, 3)), np.zeros((M1, 3)), np.tile([1.0, 0, 0, 0], (M1, 1))
     yc, yr, yh, yq = np.zeros((M2, 3)), np.zeros((M2, 1)), np.zeros((M2, 1)), np.tile([1.0, 0, 0, 0], (M2, 1))
     t = rng.uniform(0.01, 0.03)
@@ -84,10 +97,17 @@ def _cubby(rng, M1, M2):
         cc[i] = R @ np.array(lc) + np.array([cx, 0, cz])
         cd[i] = dims
         cq[i] = _yaw_quat(yaw)
+    # the four pockets: the interior between the shelves, the walls and the back that bound each (the opening faces -x of
+    # the cubby's frame, toward the robot: the gripper reaches along world x, approach 0, as the reference's does)
+    for z0, z1 in ((t / 2, H / 2 - t / 2), (H / 2 + t / 2, H - t / 2)):
+        for y0, y1 in ((-W / 2 + t / 2, -t / 2), (t / 2, W / 2 - t / 2)):
+            lc = [-t / 4, (y0 + y1) / 2, (z0 + z1) / 2]  # (x from the opening at -D / 2 to the back plate's face)
+            _support(supports, SUPPORT_VOLUME, R @ np.array(lc) + np.array([cx, 0, cz]), [D - t / 2, y1 - y0, z1 - z0],
+                     _yaw_quat(yaw), 0.0, 1.0)
     return cc, cd, cq, yc, yr, yh, yq
 
 
-def _dresser(rng, M1, M2):
+def _dresser(rng, M1, M2, supports=None):
     cc, cd, cq = np.zeros((M1, 3)), np.zeros((M1, 3)), np.tile([1.0, 0, 0, 0], (M1, 1))
     yc, yr, yh, yq = np.zeros((M2, 3)), np.zeros((M2, 1)), np.zeros((M2, 1)), np.tile([1.0, 0, 0, 0], (M2, 1))
     W, D, H = 1.0 + rng.uniform(-0.2, 0.2), 0.3 + rng.uniform(-0.1, 0.1), 0.7 + rng.uniform(-0.15, 0.15)
@@ -104,23 +124,61 @@ def _dresser(rng, M1, M2):
         cc[i] = R @ lc + np.array([cx, 0, 0])
         cd[i] = [w_ * 0.95, D, h_ * 0.2]
         cq[i] = _yaw_quat(yaw)
+        # the free space above the plate inside its cell (a stand-in: this dresser is not the reference's recursive one);
+        # the reach runs along the plate's depth axis (local y), in the sense that has a positive world-x component
+        depth_yaw = yaw + (np.pi / 2 if s < 0 else -np.pi / 2)  # (local y is (-s, c, 0) in the world)
+        _support(supports, SUPPORT_VOLUME, R @ np.array([lc[0], lc[1], (r_ + 0.8) * h_]) + np.array([cx, 0, 0]),
+                 [w_ * 0.95, D, h_ * 0.4], _yaw_quat(yaw), depth_yaw, 1.0)
     return cc, cd, cq, yc, yr, yh, yq
 
 
 _GENERATORS = {"tabletop": _tabletop, "cubby": _cubby, "dresser": _dresser}
 
 
-def make_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16) -> Dict[str, np.ndarray]:
-    """-> float32 arrays cuboid_{centers,dims,quats} [B,M1,*], cylinder_{centers,radii,heights,quats} [B,M2,*]."""
+def _scene_arrays(B: int, seed: int, kinds, M1: int, M2: int, S: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """``make_scenes`` (``S`` None) and ``make_task_scenes``: one rng, one walk over the generators."""
     rng = np.random.default_rng(seed)
     out = [[] for _ in range(7)]
+    boxes = np.zeros((B, S or 0, 12), np.float32)
+    boxes[..., 6] = 1.0  # (padding: zero dims, the identity quaternion, weight 0)
+    kind = np.zeros((B, S or 0), np.int32)
     for b in range(B):
-        parts = _GENERATORS[kinds[b % len(kinds)]](rng, M1, M2)
+        supports = None if S is None else []
+        parts = _GENERATORS[kinds[b % len(kinds)]](rng, M1, M2, supports)
         for o, p in zip(out, parts):
             o.append(p)
+        for i, (k, row) in enumerate((supports or [])[:S]):
+            kind[b, i], boxes[b, i] = k, row
     names = ["cuboid_centers", "cuboid_dims", "cuboid_quats", "cylinder_centers", "cylinder_radii",
              "cylinder_heights", "cylinder_quats"]
-    return {k: np.asarray(v, dtype=np.float32) for k, v in zip(names, out)}
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in zip(names, out)}
+    if S is not None:
+        arrays.update(support_boxes=boxes, support_kind=kind)
+    return arrays
+
+
+def make_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16) -> Dict[str, np.ndarray]:
+    """-> float32 arrays cuboid_{centers,dims,quats} [B,M1,*], cylinder_{centers,radii,heights,quats} [B,M2,*]."""
+    return _scene_arrays(B, seed, kinds, M1, M2)
+
+
+def make_task_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16, S: int = 8) -> Dict[str, np.ndarray]:
+    """``make_scenes``' arrays, bit for bit (the supports cost no draw of the rng), plus where each scene can be worked on:
+    ``support_boxes`` float32 [B,S,12] -- centre (3), dims (3), quaternion w x y z (4), ``approach`` (the world yaw of the axis
+    the gripper reaches along) and ``weight`` -- and ``support_kind`` int32 [B,S]: 0 padding (zero dims, the identity
+    quaternion, weight 0, like the primitive padding), 1 a surface (the top face of the box), 2 a volume.  What
+    ``solvers.task_candidates`` draws from, and what the reference's ``check_final_region`` judges by.
+
+    * tabletop: the front table and the side table, when present, are surfaces (the reference's ``clear_tables``; the mount
+      table under the robot is not one); weight = the top face's area, ``approach`` unused (0).
+    * cubby: the four pockets are volumes, each the interior between the shelves and walls that bound it; the quaternion is
+      the cubby's yaw, weight 1, ``approach`` 0: the world x axis, which the reference uses and this cubby's opening faces.
+    * dresser: a STAND-IN with no reference counterpart (this dresser is "dresser-like", not the reference's recursive one):
+      one volume per plate, the free space above it inside its cell; ``approach`` is the horizontal direction along the
+      plate's depth axis that has a positive world-x component (the reach runs from the robot inward), weight 1.  With more
+      plates than ``S`` the first ``S`` are kept."""
+    assert S >= 1
+    return _scene_arrays(B, seed, kinds, M1, M2, S)
 
 
 def sample_scene_clouds_host(scn: Dict[str, np.ndarray], num_points: int, seed: int = 0) -> np.ndarray:
@@ -271,6 +329,72 @@ def _collision_free_problems(prims: Dict[str, torch.Tensor], q_draw: torch.Tenso
     return q_start, q_pose, q_goal, valid
 
 
+TASK_CANDIDATES = 8  # free gripper poses per start and per goal that ``problems="task"`` hands to the IK, in draw order
+
+
+def _task_problems(prims: Dict[str, torch.Tensor], support_boxes: torch.Tensor, support_kind: torch.Tensor, q_draw: torch.Tensor,
+                   q_target: torch.Tensor, seed: int, env_offset: int):
+    """``make_problem_batch(problems="task")``: start and goal are the reference's task-oriented candidates -- per role the
+    first of ``solvers.task_candidates``' free gripper poses (draw order) that ``franka_ik`` solves against the scene: "the
+    first free gripper pose that has an IK solution" of up to 100 draws.  In a scene of volumes the goal is drawn with the
+    start's support excluded (different pockets).  Every draw is keyed by (seed, role, candidate, GLOBAL row): shards agree.
+    -> start q, goal q (NaN rows where invalid), ``valid``, and per role the chosen pose [B,4,4] (NaN) and support (-1)."""
+    from .geometry import TorchCuboids, TorchCylinders
+    from .solvers import franka_ik, task_candidates
+
+    B, dev = q_draw.size(0), q_draw.device
+    cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
+    cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
+                         prims["cylinder_quats"])
+    eye = torch.eye(4, dtype=torch.float32, device=dev)
+
+    def first_solved(role, exclude):
+        poses, _, support, count = task_candidates(support_boxes, support_kind, cub, cyl, C=TASK_CANDIDATES, seed=seed,
+                                                   env_offset=env_offset, role=role, exclude=exclude)
+        q = torch.full((B, 7), float("nan"), dtype=torch.float32, device=dev)
+        pose = torch.full((B, 4, 4), float("nan"), dtype=torch.float32, device=dev)
+        chosen = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        found = torch.zeros(B, dtype=torch.bool, device=dev)
+        for c in range(TASK_CANDIDATES):
+            live = count > c  # (a row past ``count`` is NaN: the IK is handed the identity there and its answer dropped)
+            target = torch.where(live[:, None, None], poses[:, c], eye).contiguous()
+            qc, sc = franka_ik(target, cub, cyl, seed=seed + 7919 * (1 + TASK_CANDIDATES * role + c), env_offset=env_offset)
+            ok = live & (sc == 0) & ~found
+            q[ok], pose[ok], chosen[ok] = qc[ok], poses[ok, c], support[ok, c]
+            found |= ok
+            if B == 0 or bool((found | (count <= c + 1)).all()):
+                break
+        return q, pose, chosen, found
+
+    q_s, pose_s, sup_s, ok_s = first_solved(0, None)
+    volumes = (support_kind == SUPPORT_VOLUME).any(1)
+    q_g, pose_g, sup_g, ok_g = first_solved(1, torch.where(volumes & ok_s, sup_s, torch.full_like(sup_s, -1)))
+    valid = ok_s & ok_g
+    nan = float("nan")
+    q_start = torch.where(valid[:, None], q_s, q_draw)  # (invalid rows keep their unchecked uniform draw, as "uniform" does)
+    q_goal = torch.where(valid[:, None], q_g, torch.full_like(q_g, nan))
+    start_pose = torch.where(valid[:, None, None], pose_s, torch.full_like(pose_s, nan))
+    goal_pose = torch.where(valid[:, None, None], pose_g, torch.full_like(pose_g, nan))
+    target_support = torch.where(valid, sup_g, torch.full_like(sup_g, -1))
+    return q_start, q_goal, valid, start_pose, goal_pose, target_support
+
+
+def _task_region_keys(support_boxes: torch.Tensor, support_kind: torch.Tensor, target_support: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """What the reference's inference problems carry for ``check_final_region``: ``target_volume`` [B,10] (centre, dims,
+    quaternion w x y z of the goal's support; NaN where it is a surface or the row is invalid) and
+    ``target_negative_volumes`` [B,S,10] (the OTHER live volume supports of the scene; NaN rows elsewhere)."""
+    B, S = support_kind.shape
+    nan = float("nan")
+    ts = target_support.long()
+    at = ts.clamp(min=0)
+    rows = torch.arange(B, device=support_kind.device)
+    is_volume = (ts >= 0) & (support_kind[rows, at] == SUPPORT_VOLUME)
+    volume = torch.where(is_volume[:, None], support_boxes[rows, at, :10], torch.full((B, 10), nan, device=support_boxes.device))
+    other = (support_kind == SUPPORT_VOLUME) & (torch.arange(S, device=ts.device)[None] != ts[:, None]) & (ts >= 0)[:, None]
+    negative = torch.where(other[..., None], support_boxes[..., :10], torch.full_like(support_boxes[..., :10], nan))
+    return {"target_volume": volume, "target_negative_volumes": negative}
+
+
 EXPERT_LENGTH = 50  # the reference's SEQUENCE_LENGTH (data_pipeline/gen_data.py)
 
 
@@ -417,7 +541,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        total_envs: Optional[int] = None, collision_free: bool = False,
                        max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
                        expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False,
-                       hybrid_guide: str = "global", hybrid_against: str = "primitives") -> Dict[str, torch.Tensor]:
+                       hybrid_guide: str = "global", hybrid_against: str = "primitives",
+                       problems: str = "uniform") -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -474,7 +599,24 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     same stage against the scene cloud: ``solvers.gripper_roadmap_cloud`` at ``expert_point_radius``, through the one field
     the cloud follower reads, with the same two extra keys; its verdicts come from the field, which approximates, so the
     exact judge stays ``check_cloud``'s test on the follower's trajectory.  "gripper" with ``hybrid_against="cloud"`` is
-    refused."""
+    refused.
+
+    ``problems`` (default "uniform", which leaves every key and every bit as it was: start and goal are the forward
+    kinematics of uniform draws over the joint limits, poses anywhere in the air).  "task" (needs ``collision_free``): the
+    problems the reference's generators pose.  Start and goal are TASK-ORIENTED candidates drawn on the scene's supports
+    (``make_task_scenes``) by ``solvers.task_candidates`` -- above a table top or an object on it with the gripper pointing
+    down, inside a cubby pocket with the gripper reaching in, start and goal in different pockets -- and per role the first
+    free candidate, of up to 100 draws, that ``franka_ik`` solves against the scene.  Free means free by this engine's
+    sphere model, not by PyBullet's meshes, and the dresser's supports are a stand-in with no reference counterpart.
+    ``valid`` = both were found (no redraws: ``max_redraws`` is not used); ``q``, ``q_goal``, ``target_pose`` and the 128
+    target rows of the slab come from the chosen candidates, and ``expert``, ``hybrid`` and every ``expert_from`` /
+    ``hybrid_guide`` / ``hybrid_against`` run unchanged on them.  New keys: ``support_boxes`` / ``support_kind`` (the scene's),
+    ``start_pose`` [B,4,4], ``target_support`` int32 [B] (the goal's support row, -1 where invalid), ``target_volume`` [B,10]
+    (centre, dims, quaternion of the goal's support; NaN for a surface) and ``target_negative_volumes`` [B,S,10] (the other
+    live volume supports; NaN rows elsewhere): what the reference's inference problems carry for ``check_final_region``
+    (``metrics.BatchedEvaluator``).  Invalid rows keep their uniform draws as start and target pose, a NaN ``q_goal`` and NaN /
+    -1 in the new keys.  The reference's neutral starts (``random_neutral``) need robofin's constants, which are not in the
+    tree: out of scope."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
@@ -500,6 +642,11 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                          "hybrid_against='cloud' ('gripper' plans it through the primitives)")
     if expert_from not in ("primitives", "cloud", "roadmap", "cloud_roadmap"):
         raise ValueError(f"expert_from must be 'primitives', 'cloud', 'roadmap' or 'cloud_roadmap', got {expert_from!r}")
+    if problems not in ("uniform", "task"):
+        raise ValueError(f"problems must be 'uniform' or 'task', got {problems!r}")
+    task = problems == "task"
+    if task and not collision_free:
+        raise ValueError("problems='task' poses checked starts and goals: it needs collision_free=True")
 
     dev = torch.device(device)
     total = env_offset + B if total_envs is None else int(total_envs)
@@ -507,15 +654,23 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     nscene = total if scene_pool is None else min(total, scene_pool)
     gid = env_offset + np.arange(B)  # global environment ids of this batch's rows
     sid = gid % nscene  # environment g sits in scene g mod nscene
-    scn = make_scenes(nscene if scene_pool is not None else int(sid.max()) + 1 if B else 0, seed, kinds, M1, M2)
+    scn = (make_task_scenes if task else make_scenes)(nscene if scene_pool is not None else int(sid.max()) + 1 if B else 0,
+                                                      seed, kinds, M1, M2)
     cloud = None if device_clouds else sample_scene_clouds_host(scn, NUM_OBSTACLE_POINTS, seed)
     out = {k: torch.from_numpy(np.ascontiguousarray(v[sid])).to(dev) for k, v in scn.items()}
     q = torch.from_numpy(random_configurations(env_offset + B, seed)[env_offset:]).to(dev)
     q_target = torch.from_numpy(random_configurations(env_offset + B, seed + 7)[env_offset:]).to(dev)
     lim = torch.as_tensor(ft.JOINT_LIMITS_REAL, dtype=torch.float32, device=dev)
-    if collision_free:
+    task_pose = None
+    if task:
+        q, q_goal, valid, start_pose, task_pose, target_support = _task_problems(out, out["support_boxes"], out["support_kind"],
+                                                                                 q, q_target, seed, env_offset)
+        out.update(q_goal=q_goal, valid=valid, start_pose=start_pose, target_support=target_support,
+                   **_task_region_keys(out["support_boxes"], out["support_kind"], target_support))
+    elif collision_free:
         q, q_target, q_goal, valid = _collision_free_problems(out, q, q_target, seed, env_offset, max_redraws)
         out.update(q_goal=q_goal, valid=valid)
+    if collision_free:
         if expert and expert_from in ("primitives", "roadmap"):
             out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset, roadmap=expert_from == "roadmap"))
     state = np.random.get_state()
@@ -537,6 +692,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
         out.update(_expert_trajectories_cloud(scene_cloud, q, q_goal, valid, seed, env_offset, expert_point_radius,
                                               roadmap=expert_from == "cloud_roadmap"))
     target_pose = frames_to_matrix(franka_fk(q_target)[:, ft.LINK_ID["right_gripper"]])
+    if task:  # (valid rows: the chosen goal candidate; the others keep the pose of their uniform draw)
+        target_pose = torch.where(out["valid"][:, None, None], task_pose, target_pose)
     xyz[:, NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS:, :3] = sampler.sample_end_effector(target_pose, NUM_TARGET_POINTS)
     np.random.set_state(state)
     if hybrid and hybrid_against == "cloud":

@@ -43,6 +43,10 @@ GRIPPER_ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.01, rot_weight=0.12, orie
                                 max_rounds=256, check_margin=1e-4, clearance=0.0, check_self=True)
 GRIPPER_ROADMAP_BOUNDS_PAD = 0.3  # [m] ``bounds=None``: the box hull of the two positions, grown by this much per side
 
+TASK_PADDING, TASK_SURFACE, TASK_VOLUME = 0, 1, 2  # ``support_kind`` of ``task_candidates``
+# MPX_TASK_DEFAULT_DRAWS and the NULL-options values (include/mpinets_hip.h); ``role`` is the wrapper's own argument
+TASK_CANDIDATES_DEFAULTS = dict(draws=100, clearance=0.0, test_self=True, self_margin=0.0, role=0)
+
 FOLLOW_VALID, FOLLOW_INVALID, FOLLOW_BAD_INPUT = 0, 1, 2  # status values of ``franka_follow``
 FOLLOW_BIT_MISS = 8  # MPX_FOLLOW_BIT_MISS, beside PLAN_BIT_ENV_HIT / PLAN_BIT_SELF_HIT / PLAN_BIT_JERK in ``bits``
 FOLLOW_MAX_STEPS = 4096  # MPX_FOLLOW_MAX_STEPS
@@ -318,6 +322,49 @@ def gripper_roadmap(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=N
     _lib.call("mpx_gripper_roadmap", sp.data_ptr(), gp.data_ptr(), B, W, box.data_ptr(), float(finger), *prims,
               *options_tail(copt, seed, env_offset), *_ptrs(out))
     return out if return_graph else out[:2]
+
+
+def task_candidates(support_boxes: torch.Tensor, support_kind: torch.Tensor, cuboids=None, cylinders=None, C: int = 8,
+                    seed: int = 0, env_offset: int = 0, role: int = 0, exclude: Optional[torch.Tensor] = None,
+                    with_base_link: bool = False, finger: float = ft.FINGER_OPENING, **options):
+    """Task-oriented gripper pose candidates on the GPU (csrc/task_candidates.hip): per problem ``draws`` poses drawn ON the
+    scene's supports the way the reference's generators pose their problems -- on a SURFACE a point of the top face, lifted
+    onto the object it lies on and raised 1 to 12 cm, the gripper pointing down (roll 3pi/4..5pi/4, pitch +-pi/8, yaw
+    +-pi/2; ``tabletop_environment.py:354-404``); in a VOLUME a uniform point, the gripper reaching along ``approach`` within
+    +-pi/4 (``cubby_environment.py:440-549``) -- and the first ``C`` of them, in draw order, that are free for the
+    free-flying gripper.  A restatement of those distributions: free means free by this engine's sphere model (the hand and
+    fingertip spheres, ``gripper_roadmap``'s clause), not by PyBullet's meshes, and the IK half of the reference's test is
+    ``franka_ik`` on the returned poses.  Draws are Philox keyed by (``seed``, ``env_offset`` + row, draw, ``role``).
+
+    :param support_boxes: [B,S,12] float32 (``scenes.make_task_scenes``): centre, dims, unit quaternion w x y z, approach,
+        weight; ``support_kind`` int [B,S]: 0 padding, ``TASK_SURFACE``, ``TASK_VOLUME``
+    :param cuboids, cylinders: as for ``franka_plan`` (rotated about z only: a primitive's top is its centre z plus half its
+        z extent)
+    :param C: kept candidates per problem, 1 .. 16
+    :param role: 0 a start, 1 a goal (independent draws); ``exclude``: int [B] or None, the support row not drawn from (-1:
+        none) -- the goal call passes the start's support so that the two lie in different pockets
+    :param options: the fields of ``mpx_task_candidates_options``, see ``TASK_CANDIDATES_DEFAULTS``
+    :returns: ``poses`` [B,C,4,4], ``draw`` int32 [B,C] (the draw index of each kept candidate, strictly ascending),
+        ``support`` int32 [B,C] and ``count`` int32 [B]; rows past ``count`` hold NaN poses and -1.  A problem without a live
+        support has count 0."""
+    if support_boxes.ndim != 3 or support_boxes.size(2) != 12 or tuple(support_kind.shape) != tuple(support_boxes.shape[:2]):
+        raise _lib.MpxError(f"task_candidates: support_boxes must be [B,S,12] and support_kind [B,S], got "
+                            f"{tuple(support_boxes.shape)} and {tuple(support_kind.shape)}")
+    B, NS = support_boxes.shape[:2]
+    dev = support_boxes.device
+    if exclude is not None and tuple(exclude.shape) != (B,):
+        raise _lib.MpxError(f"task_candidates: exclude must be [B={B}], got {tuple(exclude.shape)}")
+    copt, _ = merge_options("task_candidates", _lib.TaskCandidatesOptions, TASK_CANDIDATES_DEFAULTS, dict(options, role=role))
+    _lib.require_cuda(support_boxes, support_kind, exclude)  # (the refusals above need no device)
+    sb, sk = _lib.f32c(support_boxes), _lib.i32c(support_kind)
+    ex = None if exclude is None else _lib.i32c(exclude)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    Cn = max(int(C), 0)
+    out = (torch.empty((B, Cn, 4, 4), dtype=torch.float32, device=dev), torch.empty((B, Cn), dtype=torch.int32, device=dev),
+           torch.empty((B, Cn), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    _lib.call("mpx_task_candidates", sb.data_ptr(), sk.data_ptr(), B, NS, _lib.ptr(ex), int(C), float(finger), *prims,
+              *options_tail(copt, seed, env_offset), *_ptrs(out))
+    return out
 
 
 def _at(p, row, b0):  # row b0 of a [B, ...] operand of 4-byte elements, by its address (``row`` None: not one per problem)
