@@ -30,6 +30,7 @@ typedef void *mpx_stream_t;
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
 int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding):
+                          mpx_franka_shortcut, mpx_franka_shortcut_cloud, struct mpx_shortcut_options; 341 (unchanged, likewise):
                           mpx_task_candidates, struct mpx_task_candidates_options; 341 (unchanged, likewise):
                           the form query mpx_linear_form; 341 (unchanged, likewise):
                           mpx_gripper_roadmap_cloud; 341 (unchanged, likewise): mpx_franka_follow_cloud,
@@ -775,6 +776,80 @@ int mpx_franka_roadmap_cloud(const float *q_start, const float *q_goal, int B, i
                              const mpx_roadmap_options *options, uint64_t seed, int64_t env_offset, float *traj,
                              int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state,
                              int32_t *rounds, mpx_stream_t stream);
+
+/* Shortcutting of a joint-space polyline per problem, between a roadmap and the seeded optimiser: where the reference's
+ * data generator asks its planner for shortcut = True (data_pipeline/gen_data.py:131-143).  A STAND-IN, valid by this
+ * engine's sphere model; no parity with OMPL's path simplifier is claimed.  One workgroup per problem, no randomness (no
+ * seed, no env_offset): row b depends on row b's inputs alone.
+ *   points float32 [B,Pin,7], count int32 [B]: the polyline of problem b is its first count_b rows, 2 <= Pin <=
+ *   MPX_ROADMAP_MAX_NODES.  The caller vouches for it: its own segments are never tested.  (There is no limits operand:
+ *   a chord between two vertices inside a box of joint limits lies inside it.)
+ *   status int32 [B]: 0 a polyline is returned, shortened or unchanged; 2 a bad row -- count < 2, count > Pin or a vertex
+ *   that is not finite -- for which no chord is tested.  There is no status 1: the input is always a fallback.
+ *   A configuration is VALID by mpx_franka_roadmap's clause (mpx_franka_shortcut) or by mpx_franka_roadmap_cloud's
+ *   (mpx_franka_shortcut_cloud: point_radius, field_slack, "outside the grid or saturated: free", field == NULL: no
+ *   environment test), with this struct's check_margin, clearance and check_self.
+ *   Length of a segment (a,b): mpx_franka_roadmap's w.  CHORD from a to e, a before e in the pass's order: d = q_e - q_a,
+ *   n = min(2^20, max(1, (int)ceilf(w / resolution))) pieces, interior configuration i = 1 .. n-1 is
+ *   fma((float)i / (float)n, d, q_a); the chord is BLOCKED exactly when an interior configuration is invalid (the
+ *   roadmap's edge test, from the end that comes first).
+ *   Pass p = 0 .. passes-1, skipped once the polyline has two vertices.  An odd pass reverses the polyline's vertices,
+ *   does the steps below and reverses the result back.
+ *   Densify.  With v_0 .. v_h the pass's vertices, w_i = |v_{i+1} - v_i|, L = w_0 + .. + w_{h-1} summed in that order in
+ *   float32 and extra = P - (h+1), P = options->points: edge i, i ascending, gets m_i = min((int)floorf(w_i * (float)extra
+ *   / L), what is left of extra) interior points (the product first); every m_i is 0 when extra <= 0 or L is 0 or not
+ *   finite.  Interior point k = 1 .. m_i is fma((float)k / (float)(m_i+1), v_{i+1} - v_i, v_i); the vertices are copied.
+ *   The dense polyline d_0 .. d_{N-1} has N = h + 1 + sum m_i <= P points.
+ *   Greedy.  Anchor a = 0, d_0 is kept; until a = N-1: lo = a+1, hi = N-1 (the segment a -> lo is part of the pass's
+ *   polyline and taken as free).  While hi > lo one LEVEL tests the chords from a to the probes lo + (span k + K-1) / K
+ *   (integer division), k = 1 .. K, span = hi - lo, K = options->fanout, equal probes merged; a level's chords are laid out
+ *   probe ascending, `chords` counts them and `configs` their interior configurations.  If the chord to hi is free, lo =
+ *   hi and the search ends.  Otherwise lo becomes the largest probe below hi whose chord is free (kept if none is), and hi
+ *   becomes (the smallest probe above the new lo) - 1.  Then d_lo is kept and a = lo.  K = 1 is the linear scan from the
+ *   far end; K >= span tests every point of the span at once.
+ *   Every edge of the returned polyline is therefore a chord tested free here, or a piece of an edge of the polyline its
+ *   pass started from (in exact arithmetic: a dense point is on its edge to float32 rounding).
+ *   points_out [B,P,7], count_out int32 [B]: the returned polyline, NaN rows behind it (status 2: count_out 0, all NaN).
+ *   Its first and last vertex are bit-equal to the input's.  length float32 [B,2]: the input's and the returned
+ *   polyline's length, each summed in path order in float32 (NaN with status 2).  Optional: chords int32 [B], configs
+ *   int32 [B] (0 with status 2).
+ *   traj [B,T,7]: mpx_franka_roadmap's clause "traj" over the returned polyline, by the same statements (one edge: the
+ *   planner's line bit for bit; else resampled and rounded by smooth_passes passes).  With passes = 0 and the vertices
+ *   nodes[path] of a roadmap it is that roadmap's traj bit for bit.  Rows with status 2 are NaN.
+ *   T, finger, the sphere table, the primitives, field, grid, point_radius and field_slack exactly as for
+ *   mpx_franka_roadmap / mpx_franka_roadmap_cloud.
+ * Refused before any launch: what those entries refuse about T, S, M1, M2, the field and NULL pointers; Pin outside 2 ..
+ * MPX_ROADMAP_MAX_NODES; points outside Pin .. MPX_ROADMAP_MAX_NODES; passes < 0; fanout outside 1 ..
+ * MPX_SHORTCUT_MAX_FANOUT; resolution <= 0 or NaN; smooth_passes < 0; check_margin < 0; a NaN clearance.
+ * One workgroup of 256 threads per problem, everything but the field in LDS (35 352 B at 256 points, 27 160 B for the
+ * cloud form).  No allocation, no scratch, no global atomics; one kernel on `stream` (capturable).  B == 0 launches nothing. */
+#define MPX_SHORTCUT_DEFAULT_POINTS 64
+#define MPX_SHORTCUT_DEFAULT_PASSES 2
+#define MPX_SHORTCUT_DEFAULT_FANOUT 4
+#define MPX_SHORTCUT_MAX_FANOUT 256
+typedef struct mpx_shortcut_options { /* NULL options: the defaults above, resolution MPX_ROADMAP_DEFAULT_RESOLUTION,
+                                         smooth_passes MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, check_margin
+                                         MPX_PLAN_DEFAULT_CHECK_MARGIN, clearance 0, check_self 1 */
+  int points;                         /* P: Pin .. MPX_ROADMAP_MAX_NODES, the dense polyline's points        */
+  int passes;                         /* >= 0: forward, backward, forward, ...                              */
+  int fanout;                         /* K: 1 .. MPX_SHORTCUT_MAX_FANOUT probes per level                   */
+  float resolution;                   /* > 0 [rad]: the longest piece of a chord (joint-space 2-norm)       */
+  int smooth_passes;                  /* >= 0: (1/4, 1/2, 1/4) passes over the resampled polyline           */
+  float check_margin;                 /* >= 0 [m], as in mpx_plan_options                                   */
+  float clearance;                    /* [m], added to the radii                                            */
+  int check_self;                     /* non-zero: self collisions invalidate a configuration               */
+} mpx_shortcut_options;
+int mpx_franka_shortcut(const float *points, const int32_t *count, int B, int Pin, int T, float finger,
+                        const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                        const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                        const float *cyl_radii, const float *cyl_heights, int M2, const mpx_shortcut_options *options,
+                        float *traj, int32_t *status, float *points_out, int32_t *count_out, float *length, int32_t *chords,
+                        int32_t *configs, mpx_stream_t stream);
+int mpx_franka_shortcut_cloud(const float *points, const int32_t *count, int B, int Pin, int T, float finger,
+                              const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                              const float *field, const mpx_field_grid *grid, float point_radius, float field_slack,
+                              const mpx_shortcut_options *options, float *traj, int32_t *status, float *points_out,
+                              int32_t *count_out, float *length, int32_t *chords, int32_t *configs, mpx_stream_t stream);
 
 /* mpx_gripper_roadmap against a POINT CLOUD, read through its distance field: the guide of mpx_franka_follow_cloud where
  * there are no primitives to plan the gripper through.  Still the STAND-IN for the reference's OMPL end-effector planner,

@@ -25,6 +25,10 @@ static inline mpx_roadmap_options franka_roadmap_defaults() {
   return {MPX_ROADMAP_DEFAULT_NODES, MPX_ROADMAP_DEFAULT_RESOLUTION, __builtin_inff(), MPX_ROADMAP_DEFAULT_MAX_ROUNDS,
           MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
 }
+static inline mpx_shortcut_options franka_shortcut_defaults() {
+  return {MPX_SHORTCUT_DEFAULT_POINTS, MPX_SHORTCUT_DEFAULT_PASSES, MPX_SHORTCUT_DEFAULT_FANOUT, MPX_ROADMAP_DEFAULT_RESOLUTION,
+          MPX_ROADMAP_DEFAULT_SMOOTH_PASSES, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
+}
 static inline mpx_gripper_roadmap_options gripper_roadmap_defaults() {
   return {MPX_GRIPPER_ROADMAP_DEFAULT_NODES, MPX_GRIPPER_ROADMAP_DEFAULT_RESOLUTION, MPX_GRIPPER_ROADMAP_DEFAULT_ROT_WEIGHT,
           MPX_GRIPPER_ROADMAP_DEFAULT_ORIENT_SPREAD, __builtin_inff(), MPX_GRIPPER_ROADMAP_DEFAULT_MAX_ROUNDS,
@@ -97,6 +101,22 @@ static inline int franka_roadmap_options_check(const char *who, int T, const mpx
   MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
   MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
   MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
+  MPX_REQUIRE(opt.smooth_passes >= 0, "%s: smooth_passes = %d, need >= 0", who, opt.smooth_passes);
+  MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
+  return 0;
+}
+// (Pin: the rows of the caller's polylines; a thread per vertex and per dense point, so both stay within the roadmap's nodes)
+static inline int franka_shortcut_options_check(const char *who, int T, int Pin, const mpx_shortcut_options &opt) {
+  if (franka_plan_T_check(who, T)) return 1;
+  MPX_REQUIRE(Pin >= 2 && Pin <= MPX_ROADMAP_MAX_NODES, "%s: Pin = %d vertices per polyline, need 2 .. %d (one thread each)", who,
+              Pin, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.points >= Pin && opt.points <= MPX_ROADMAP_MAX_NODES, "%s: points = %d, need Pin = %d .. %d (one thread each)",
+              who, opt.points, Pin, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.passes >= 0, "%s: passes = %d, need >= 0", who, opt.passes);
+  MPX_REQUIRE(opt.fanout >= 1 && opt.fanout <= MPX_SHORTCUT_MAX_FANOUT, "%s: fanout = %d, need 1 .. %d", who, opt.fanout,
+              MPX_SHORTCUT_MAX_FANOUT);
+  MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
   MPX_REQUIRE(opt.smooth_passes >= 0, "%s: smooth_passes = %d, need >= 0", who, opt.smooth_passes);
   MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
   MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);

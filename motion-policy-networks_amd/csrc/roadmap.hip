@@ -13,6 +13,9 @@
 // thread 0.  Every branch around a barrier is workgroup-uniform: it reads a value from LDS behind a barrier, or a barrier's
 // own reduction.  The search itself is roadmap_search.inc, shared with gripper_roadmap.hip (the gripper's roadmap in SE(3)) and
 // roadmap_cloud.hip (this roadmap against a point cloud's distance field), which also shares what follows it, roadmap_tail.inc.
+// Behind the roadmap, franka_shortcut_kernel shortens a polyline (the roadmap's path, or any caller's) with the same validity
+// test: its body is shortcut_kernel.inc, shared with roadmap_cloud.hip's form, and ends with the seed trajectory's statements
+// (roadmap_traj.inc, which roadmap_tail.inc ends with).
 #include "common.h"
 #include "franka_host.h"
 #include "plan_prims_device.h"
@@ -119,5 +122,59 @@ MPX_EXPORT int mpx_franka_roadmap(const float *q_start, const float *q_goal, int
                      finger, limits, sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames,
                      cyl_radii, cyl_heights, M2, opt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, traj,
                      status, path, hops, nodes, edge_state, rounds);
+  MPX_LAUNCH_CHECK(who);
+}
+
+// ---- shortcutting a polyline: shortcut_kernel.inc with the planner's validity test --------------------------------------------------
+// LDS: [128 primitive rows x 16 | shortcut_lds_words(P)]
+__global__ void __launch_bounds__(ROADMAP_THREADS)
+    franka_shortcut_kernel(const float *__restrict__ points, const int32_t *__restrict__ count, int Pin, int T, float finger,
+                           const float *__restrict__ sc, const float *__restrict__ sr, const int32_t *__restrict__ sl, int S,
+                           const float *__restrict__ cub_f, const float *__restrict__ cub_d, int M1,
+                           const float *__restrict__ cyl_f, const float *__restrict__ cyl_r, const float *__restrict__ cyl_h,
+                           int M2, mpx_shortcut_options opt, float *__restrict__ traj, int32_t *__restrict__ status,
+                           float *__restrict__ points_out, int32_t *__restrict__ count_out, float *__restrict__ length,
+                           int32_t *__restrict__ chords_out, int32_t *__restrict__ configs_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float *prim_rows = lds;
+  SHORTCUT_LDS_CARVE(prim_rows + 128 * 16, opt.points)
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int k = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const float inf = __builtin_inff(), nan = __builtin_nanf("");
+#define FRANKA_LIVE_ROWS_STORE (k == 0)
+#include "franka_live_rows.inc"
+#undef FRANKA_LIVE_ROWS_STORE
+  const bool test_self = opt.check_self != 0;
+  const float reach = opt.clearance + opt.check_margin;
+  // (the body's first barrier publishes the primitive rows)
+#define SHORTCUT_HIT(q) \
+  plan_config_bits(q, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin)
+#include "shortcut_kernel.inc"
+#undef SHORTCUT_HIT
+}
+
+MPX_EXPORT int mpx_franka_shortcut(const float *points, const int32_t *count, int B, int Pin, int T, float finger,
+                                   const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                                   const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                                   const float *cyl_radii, const float *cyl_heights, int M2,
+                                   const mpx_shortcut_options *options, float *traj, int32_t *status, float *points_out,
+                                   int32_t *count_out, float *length, int32_t *chords, int32_t *configs, mpx_stream_t stream) {
+  const char *who = "mpx_franka_shortcut";
+  const mpx_shortcut_options opt = options ? *options : franka_shortcut_defaults();
+  MPX_REQUIRE(B >= 0 && S >= 0 && M1 >= 0 && M2 >= 0, "%s: negative size", who);
+  if (franka_shortcut_options_check(who, T, Pin, opt) || franka_counts_check(who, S, M1, M2)) return 1;
+  if (B == 0) return 0;
+  MPX_REQUIRE(traj && status && points_out && count_out && length,
+              "%s: NULL output (traj, status, points_out, count_out, length)", who);
+  MPX_REQUIRE(points && count, "%s: NULL operand (points, count)", who);
+  if (franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link) ||
+      franka_primitive_arrays_check(who, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii, cyl_heights, M2))
+    return 1;
+  const size_t lds = 4 * ((size_t)128 * 16 + shortcut_lds_words(opt.points));  // 35 352 B at 256 points
+  hipLaunchKernelGGL(franka_shortcut_kernel, dim3((unsigned)B), dim3(ROADMAP_THREADS), lds, mpx_s(stream), points, count, Pin,
+                     T, finger, sph_centers, sph_radii, sph_link, S, cub_inv_frames, cub_dims, M1, cyl_inv_frames, cyl_radii,
+                     cyl_heights, M2, opt, traj, status, points_out, count_out, length, chords, configs);
   MPX_LAUNCH_CHECK(who);
 }

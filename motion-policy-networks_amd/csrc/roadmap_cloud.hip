@@ -5,6 +5,8 @@
 // are a guide: what mpx_franka_plan_cloud_seeded returns is still judged by the exact swept-sphere test.  Nodes, edges, the
 // search, the statuses and the seed trajectory are mpx_franka_roadmap's, by the same text (roadmap_search.inc,
 // roadmap_tail.inc); the contract is stated in include/mpinets_hip.h.
+// Behind it, franka_shortcut_cloud_kernel is roadmap.hip's franka_shortcut_kernel with this file's validity test (one body,
+// shortcut_kernel.inc).
 //
 // franka_roadmap_kernel's structure: one workgroup of 256 threads per problem, everything but the field in LDS, no scratch
 // memory and no global atomics; thread = node, thread = interior configuration of the round's untested edges, thread =
@@ -150,5 +152,64 @@ MPX_EXPORT int mpx_franka_roadmap_cloud(const float *q_start, const float *q_goa
                      T, finger, limits, sph_centers, sph_radii, sph_link, S, field, G, point_radius, slack_margin, opt,
                      (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)env_offset, traj, status, path, hops, nodes, edge_state,
                      rounds);
+  MPX_LAUNCH_CHECK(who);
+}
+
+// ---- shortcutting a polyline: shortcut_kernel.inc with the field as the validity test (roadmap_cloud_bits' rule) ---------------------
+// LDS: shortcut_lds_words(P)
+__global__ void __launch_bounds__(ROADMAP_THREADS)
+    franka_shortcut_cloud_kernel(const float *__restrict__ points, const int32_t *__restrict__ count, int Pin, int T,
+                                 float finger, const float *__restrict__ sc, const float *__restrict__ sr,
+                                 const int32_t *__restrict__ sl, int S, const float *__restrict__ field, FieldGrid G,
+                                 float point_radius, float slack_margin, mpx_shortcut_options opt, float *__restrict__ traj,
+                                 int32_t *__restrict__ status, float *__restrict__ points_out, int32_t *__restrict__ count_out,
+                                 float *__restrict__ length, int32_t *__restrict__ chords_out,
+                                 int32_t *__restrict__ configs_out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  SHORTCUT_LDS_CARVE(lds, opt.points)
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float inf = __builtin_inff(), nan = __builtin_nanf("");
+  const bool test_self = opt.check_self != 0;
+  const float *fenv = (field != nullptr && S > 0) ? field + (size_t)b * ((size_t)G.nx * G.ny * G.nz) : nullptr;
+#define SHORTCUT_HIT(q) \
+  roadmap_cloud_bits(q, finger, sc, sr, sl, S, fenv, G, point_radius, opt.clearance, slack_margin, test_self, opt.check_margin)
+#include "shortcut_kernel.inc"
+#undef SHORTCUT_HIT
+}
+
+MPX_EXPORT int mpx_franka_shortcut_cloud(const float *points, const int32_t *count, int B, int Pin, int T, float finger,
+                                         const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                                         const float *field, const mpx_field_grid *grid, float point_radius, float field_slack,
+                                         const mpx_shortcut_options *options, float *traj, int32_t *status, float *points_out,
+                                         int32_t *count_out, float *length, int32_t *chords, int32_t *configs,
+                                         mpx_stream_t stream) {
+  const char *who = "mpx_franka_shortcut_cloud";
+  const mpx_shortcut_options opt = options ? *options : franka_shortcut_defaults();
+  const float big = __builtin_huge_valf();
+  MPX_REQUIRE(B >= 0 && S >= 0, "%s: negative size", who);
+  if (franka_shortcut_options_check(who, T, Pin, opt) || franka_counts_check(who, S)) return 1;
+  MPX_REQUIRE(point_radius >= 0.0f && point_radius < big, "%s: point_radius must be finite and >= 0", who);
+  MPX_REQUIRE(field_slack >= 0.0f && field_slack < big, "%s: field_slack must be finite and >= 0", who);
+  FieldGrid G = {};
+  const float slack_margin = opt.check_margin + field_slack;  // (float32, summed once: the kernel's right-hand side)
+  if (field) {  // (mpx_franka_roadmap_cloud's refusals, in its words)
+    if (field_grid_check(who, grid, G)) return 1;
+    MPX_REQUIRE(S > 0, "%s: a field without collision spheres to test it with", who);
+    const float need = MPX_FRANKA_MAX_SPHERE_RADIUS + point_radius + (opt.clearance > 0.0f ? opt.clearance : 0.0f) + slack_margin;
+    MPX_REQUIRE(G.trunc > need,
+                "%s: grid trunc = %g, need more than %g = largest sphere radius %g + point_radius + max(clearance, 0) + "
+                "check_margin + field_slack (an obstacle in between would be missed)",
+                who, (double)G.trunc, (double)need, (double)MPX_FRANKA_MAX_SPHERE_RADIUS);
+  }
+  if (B == 0) return 0;
+  MPX_REQUIRE(traj && status && points_out && count_out && length,
+              "%s: NULL output (traj, status, points_out, count_out, length)", who);
+  MPX_REQUIRE(points && count, "%s: NULL operand (points, count)", who);
+  if (franka_sphere_table_check(who, S, sph_centers, sph_radii, sph_link)) return 1;
+  const size_t lds = 4 * shortcut_lds_words(opt.points);  // 27 160 B at 256 points
+  hipLaunchKernelGGL(franka_shortcut_cloud_kernel, dim3((unsigned)B), dim3(ROADMAP_THREADS), lds, mpx_s(stream), points, count,
+                     Pin, T, finger, sph_centers, sph_radii, sph_link, S, field, G, point_radius, slack_margin, opt, traj,
+                     status, points_out, count_out, length, chords, configs);
   MPX_LAUNCH_CHECK(who);
 }

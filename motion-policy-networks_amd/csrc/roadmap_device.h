@@ -34,3 +34,18 @@ __device__ __forceinline__ void roadmap_edge_set(unsigned *bits, int V, int a, i
   const int idx = (a < b ? a : b) * V + (a < b ? b : a);
   atomicOr(&bits[idx >> 4], (unsigned)state << ((idx & 15) * 2));
 }
+
+// LDS of a shortcut kernel behind its primitive rows, in 4-byte words (shortcut_kernel.inc): [two polylines P x 7 | dist 2 x P
+// (edge lengths; later cumulative and edge lengths) | two trajectories 64 x 7 | path, sel, pidx, pieces, blocked: P ints each |
+// off, first: P + 1 each | ctl 4]
+__host__ __device__ static inline size_t shortcut_lds_words(int P) {
+  return 2 * (size_t)P * 7 + 2 * (size_t)P + 2 * 64 * 7 + 5 * (size_t)P + 2 * ((size_t)P + 1) + 4;
+}
+// ... and its carving, from `base` on
+#define SHORTCUT_LDS_CARVE(base, P)                                                                                     \
+  float *poly = (base);                                                                                                 \
+  float *dist = poly + 2 * (P) * 7;                                                                                     \
+  float *tbuf = dist + 2 * (P);                                                                                         \
+  int *path = reinterpret_cast<int *>(tbuf + 2 * 64 * 7);                                                               \
+  int *sel = path + (P), *pidx = sel + (P), *pieces = pidx + (P), *blocked = pieces + (P);                              \
+  int *off = blocked + (P), *first = off + (P) + 1, *ctl = first + (P) + 1;

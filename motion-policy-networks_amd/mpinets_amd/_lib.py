@@ -55,6 +55,8 @@ PROTOTYPES = {
     "mpx_franka_plan_cloud_seeded": [P, P, I, I, F, P, P, P, P, I, P, P, P, L, I, I, P, F, P, ctypes.c_uint64, L, P, I, P, P, P, P, P, P, L, P],
     "mpx_franka_roadmap_cloud": [P, P, I, I, F, P, P, P, P, I, P, P, F, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_gripper_roadmap_cloud": [P, P, I, I, P, F, P, P, P, I, P, P, F, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
+    "mpx_franka_shortcut": [P, P, I, I, I, F, P, P, P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P],
+    "mpx_franka_shortcut_cloud": [P, P, I, I, I, F, P, P, P, I, P, P, F, F, P, P, P, P, P, P, P, P, P],
     "mpx_collision_hinge": [P, L, I, I, I, P, P, I, P, P, P, I, F, P, P, L, I, P],
     "mpx_point_match": [P, P, I, I, F, F, P, P, P],
     "mpx_franka_cloud_grad": [P, I, F, P, P, P, I, P, L, I, P, P],
@@ -160,6 +162,12 @@ class RoadmapOptions(ctypes.Structure):
     """``mpx_roadmap_options`` (include/mpinets_hip.h); the defaults are the header's MPX_ROADMAP_DEFAULT_*."""
     _fields_ = [("nodes", c_int), ("resolution", c_float), ("connect_radius", c_float), ("max_rounds", c_int),
                 ("smooth_passes", c_int), ("check_margin", c_float), ("clearance", c_float), ("check_self", c_int)]
+
+
+class ShortcutOptions(ctypes.Structure):
+    """``mpx_shortcut_options`` (include/mpinets_hip.h); the defaults are the header's MPX_SHORTCUT_DEFAULT_* and the roadmap's."""
+    _fields_ = [("points", c_int), ("passes", c_int), ("fanout", c_int), ("resolution", c_float), ("smooth_passes", c_int),
+                ("check_margin", c_float), ("clearance", c_float), ("check_self", c_int)]
 
 
 class GripperRoadmapOptions(ctypes.Structure):

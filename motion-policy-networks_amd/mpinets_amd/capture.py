@@ -158,7 +158,7 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
                   plan_options: Optional[dict] = None, global_plan: bool = False,
                   roadmap_options: Optional[dict] = None, follow: bool = False, follow_poses: int = 8,
                   follow_options: Optional[dict] = None, follow_guide: str = "plan",
-                  gripper_options: Optional[dict] = None) -> dict:
+                  gripper_options: Optional[dict] = None, shortcut=False) -> dict:
     """From a cloud and a target pose to a checked trajectory: ``robot.franka_ik_cloud`` for the goal configuration, then
     ``robot.franka_plan_cloud`` from ``q_start`` to it, both against the same ``cloud`` (``counts``, ``point_radius``).  The
     optimiser-based counterpart of the reference demo's ``Planner.plan(q0, target_pose, obstacle_pc)``
@@ -171,6 +171,9 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
     :param global_plan: False (every key and bit as before), or True: the trajectory comes from
         ``robot.franka_plan_global_cloud`` -- a lazy roadmap through the cloud's distance field seeds one more candidate, so a
         target behind an obstacle is not lost to a blocked straight line; ``roadmap_options`` are that roadmap's
+    :param shortcut: False (as before), or True / a dict of ``robot.franka_shortcut_cloud``'s options (needs
+        ``global_plan``): the roadmap's path is shortcut through the same field and seeds one candidate more, in front of
+        the roadmap's own (``franka_plan_global_cloud(shortcut=...)``)
     :returns: dict of ``q_goal`` [B,7] (NaN rows where ``ik_status`` != 0), ``ik_status`` int32 [B], ``trajectory``
         [B,T,7] (NaN rows where ``plan_status`` != 0), ``plan_status`` int32 [B] -- 2 for every row without a goal: the
         planner refuses a NaN endpoint -- and ``valid`` bool [B]: both statuses 0; with ``global_plan`` also ``roadmap_status``
@@ -195,6 +198,8 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
         raise ValueError(f"follow_guide must be 'plan' or 'gripper', got {follow_guide!r}")
     if follow_guide == "gripper" and not follow:
         raise ValueError("follow_guide='gripper' chooses the follower's guide: it needs follow=True")
+    if shortcut and not global_plan:
+        raise ValueError("shortcut shortens the roadmap's path: it needs global_plan=True")
     if follow and field is None:  # (one field for the planner and the follower)
         from ._operands import cloud_args
         from .field import DEFAULT_VOXEL, CloudField
@@ -211,7 +216,7 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
     if global_plan:
         traj, plan_status, extra["roadmap_status"] = franka_plan_global_cloud(
             q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T, seed=seed, env_offset=env_offset,
-            roadmap=roadmap_options, **(plan_options or {}))
+            roadmap=roadmap_options, shortcut=shortcut or None, **(plan_options or {}))
     else:
         traj, plan_status = franka_plan_cloud(q_start, q_goal, cloud, counts, field=field, point_radius=point_radius, T=T,
                                               seed=seed, env_offset=env_offset, **(plan_options or {}))

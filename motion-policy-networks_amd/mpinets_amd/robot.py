@@ -27,6 +27,8 @@ from .solvers import (FOLLOW_BAD_INPUT, FOLLOW_BIT_MISS, FOLLOW_DEFAULTS, FOLLOW
                       FOLLOW_PATH_BYTES, FOLLOW_VALID, _follow_options, franka_follow, franka_follow_cloud)
 from .solvers import (GRIPPER_ROADMAP_BOUNDS_PAD, GRIPPER_ROADMAP_DEFAULTS, _gripper_roadmap_options,  # noqa: F401
                       gripper_roadmap, gripper_roadmap_cloud)
+from .solvers import (SHORTCUT_BAD_ROW, SHORTCUT_DEFAULTS, SHORTCUT_RETURNED, _shortcut_options, franka_shortcut,  # noqa: F401
+                      franka_shortcut_cloud)
 from .solvers import TASK_CANDIDATES_DEFAULTS, TASK_SURFACE, TASK_VOLUME, task_candidates  # noqa: F401
 from .solvers import (IK_BIT_CONVERGED, IK_BIT_ENV_HIT, IK_BIT_SELF_HIT, IK_DEFAULTS, IK_IN_COLLISION,  # noqa: F401
                       IK_NOT_CONVERGED, IK_SEEDS, IK_SOLVED, PLAN_BAD_ENDPOINT, PLAN_BIT_ENV_HIT, PLAN_BIT_JERK,

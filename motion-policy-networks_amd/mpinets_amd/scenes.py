@@ -399,7 +399,7 @@ EXPERT_LENGTH = 50  # the reference's SEQUENCE_LENGTH (data_pipeline/gen_data.py
 
 
 def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
-                         seed: int, env_offset: int, roadmap: bool = False) -> Dict[str, torch.Tensor]:
+                         seed: int, env_offset: int, roadmap: bool = False, shortcut: bool = False) -> Dict[str, torch.Tensor]:
     from .geometry import TorchCuboids, TorchCylinders
     from .solvers import franka_plan, franka_plan_global
 
@@ -408,7 +408,8 @@ def _expert_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
                          prims["cylinder_quats"])
     # (invalid rows have a NaN goal: the kernel reports status 2 and writes a NaN row for them)
     if roadmap:  # ``expert_from="roadmap"``: the same planner with the roadmap's path as one more candidate
-        traj, status, _ = franka_plan_global(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
+        traj, status, _ = franka_plan_global(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset,
+                                             shortcut=True if shortcut else None)
     else:
         traj, status = franka_plan(q_start, q_goal, cub, cyl, T=EXPERT_LENGTH, seed=seed, env_offset=env_offset)
     return {"global_solutions": traj, "expert_valid": valid & (status == 0)}
@@ -418,17 +419,17 @@ EXPERT_CLOUD_POINT_RADIUS = 0.02  # [m] about half the spacing of 4096 points on
 
 
 def _expert_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, q_goal: torch.Tensor, valid: torch.Tensor,
-                               seed: int, env_offset: int, point_radius: float,
-                               roadmap: bool = False) -> Dict[str, torch.Tensor]:
+                               seed: int, env_offset: int, point_radius: float, roadmap: bool = False,
+                               shortcut: bool = False) -> Dict[str, torch.Tensor]:
     """``expert_from="cloud"``: the demonstration is planned against the batch's own scene cloud (a view of the slab),
     with ``solvers.franka_plan_cloud``; valid means free by ``FrankaCollisionSampler.check_cloud`` at ``point_radius``.
     ``roadmap`` (``expert_from="cloud_roadmap"``): with ``solvers.franka_plan_global_cloud``, the same planner with a lazy
-    roadmap's path as one more candidate."""
+    roadmap's path as one more candidate; ``shortcut``: and that path shortcut as another, in front of it."""
     from .solvers import franka_plan_cloud, franka_plan_global_cloud
 
     if roadmap:
         traj, status, _ = franka_plan_global_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH,
-                                                   seed=seed, env_offset=env_offset)
+                                                   seed=seed, env_offset=env_offset, shortcut=True if shortcut else None)
     else:
         traj, status = franka_plan_cloud(q_start, q_goal, scene_cloud, point_radius=point_radius, T=EXPERT_LENGTH, seed=seed,
                                          env_offset=env_offset)
@@ -542,7 +543,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
                        expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False,
                        hybrid_guide: str = "global", hybrid_against: str = "primitives",
-                       problems: str = "uniform") -> Dict[str, torch.Tensor]:
+                       problems: str = "uniform", expert_shortcut: bool = False) -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -571,7 +572,9 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     more candidate, so a problem whose straight line is blocked is not silently dropped; every row ``franka_plan`` solves
     is returned as ``expert_from="primitives"`` returns it.  ``expert_from="cloud_roadmap"`` is the ``"cloud"`` branch with
     ``robot.franka_plan_global_cloud``: the roadmap reads the cloud's distance field, the exact cloud test still judges, and
-    every row ``"cloud"`` solves is returned as ``"cloud"`` returns it.
+    every row ``"cloud"`` solves is returned as ``"cloud"`` returns it.  ``expert_shortcut`` (default off; only with the two
+    roadmap forms) passes ``shortcut=True`` to those planners: the roadmap's path, shortcut by ``robot.franka_shortcut`` /
+    ``franka_shortcut_cloud``, seeds one candidate more, in front of the roadmap's own.
 
     ``hybrid`` (with ``expert``; default off, which leaves every key as it was): also ``hybrid_solutions`` [B,50,7], the
     demonstration of ``solvers.franka_follow`` along eight right_gripper poses of ``global_solutions`` (a reactive follower
@@ -642,6 +645,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                          "hybrid_against='cloud' ('gripper' plans it through the primitives)")
     if expert_from not in ("primitives", "cloud", "roadmap", "cloud_roadmap"):
         raise ValueError(f"expert_from must be 'primitives', 'cloud', 'roadmap' or 'cloud_roadmap', got {expert_from!r}")
+    if expert_shortcut and expert_from not in ("roadmap", "cloud_roadmap"):
+        raise ValueError("expert_shortcut=True needs expert_from='roadmap' or 'cloud_roadmap': there is no roadmap path to shortcut")
     if problems not in ("uniform", "task"):
         raise ValueError(f"problems must be 'uniform' or 'task', got {problems!r}")
     task = problems == "task"
@@ -672,7 +677,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
         out.update(q_goal=q_goal, valid=valid)
     if collision_free:
         if expert and expert_from in ("primitives", "roadmap"):
-            out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset, roadmap=expert_from == "roadmap"))
+            out.update(_expert_trajectories(out, q, q_goal, valid, seed, env_offset, roadmap=expert_from == "roadmap",
+                                            shortcut=expert_shortcut))
     state = np.random.get_state()
     np.random.seed(seed)
     sampler = FrankaSampler(dev)
@@ -690,7 +696,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if expert and expert_from in ("cloud", "cloud_roadmap"):
         scene_cloud = xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3]
         out.update(_expert_trajectories_cloud(scene_cloud, q, q_goal, valid, seed, env_offset, expert_point_radius,
-                                              roadmap=expert_from == "cloud_roadmap"))
+                                              roadmap=expert_from == "cloud_roadmap", shortcut=expert_shortcut))
     target_pose = frames_to_matrix(franka_fk(q_target)[:, ft.LINK_ID["right_gripper"]])
     if task:  # (valid rows: the chosen goal candidate; the others keep the pose of their uniform draw)
         target_pose = torch.where(out["valid"][:, None, None], task_pose, target_pose)

@@ -1,6 +1,6 @@
-"""The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap, the gripper's SE(3) roadmap and
-the path follower, against primitives or a point cloud (csrc/ik.hip, plan.hip, roadmap.hip, gripper_roadmap.hip, follow.hip,
-cloud_field.hip, roadmap_cloud.hip, follow_cloud.hip).  Each wrapper is its entry's argument list: the inputs
+"""The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap and the shortcutting of its
+path, the gripper's SE(3) roadmap and the path follower, against primitives or a point cloud (csrc/ik.hip, plan.hip,
+roadmap.hip, gripper_roadmap.hip, follow.hip, cloud_field.hip, roadmap_cloud.hip, follow_cloud.hip; shortcut_kernel.inc).  Each wrapper is its entry's argument list: the inputs
 (``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
 outputs, in the header's order.  ``robot`` re-exports every name here."""
 from __future__ import annotations
@@ -36,6 +36,11 @@ ROADMAP_EDGE_UNTESTED, ROADMAP_EDGE_FREE, ROADMAP_EDGE_BLOCKED = 0, 1, 2  # ``ed
 # MPX_ROADMAP_DEFAULT_* (include/mpinets_hip.h; profiles/roadmap_timing.md holds the runs behind them)
 ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.05, connect_radius=float("inf"), max_rounds=64, smooth_passes=8,
                         check_margin=1e-4, clearance=0.0, check_self=True)
+
+SHORTCUT_RETURNED, SHORTCUT_BAD_ROW = 0, 2  # status values of ``franka_shortcut`` (there is no 1: the input is the fallback)
+# MPX_SHORTCUT_DEFAULT_* and the roadmap's values (include/mpinets_hip.h; profiles/shortcut_timing.md holds the runs behind them)
+SHORTCUT_DEFAULTS = dict(points=64, passes=2, fanout=4, resolution=0.05, smooth_passes=8, check_margin=1e-4, clearance=0.0,
+                         check_self=True)
 
 # MPX_GRIPPER_ROADMAP_DEFAULT_* (include/mpinets_hip.h; profiles/gripper_roadmap_timing.md holds the runs behind them); the
 # status and ``edge_state`` values are the roadmap's (``ROADMAP_FOUND`` ...)
@@ -78,6 +83,11 @@ def _plan_options(who: str, options: dict):
 def _roadmap_options(who: str, options: dict):
     """Keyword options of the roadmap over ``ROADMAP_DEFAULTS`` -> the ``_lib.RoadmapOptions`` and the merged dict."""
     return merge_options(who, _lib.RoadmapOptions, ROADMAP_DEFAULTS, options)
+
+
+def _shortcut_options(who: str, options: dict):
+    """Keyword options of the shortcut over ``SHORTCUT_DEFAULTS`` -> the ``_lib.ShortcutOptions`` and the merged dict."""
+    return merge_options(who, _lib.ShortcutOptions, SHORTCUT_DEFAULTS, options)
 
 
 def _gripper_roadmap_options(who: str, options: dict):
@@ -128,6 +138,30 @@ def _roadmap_outputs(B: int, rows0: tuple, V: int, dev: torch.device, return_gra
             torch.empty((B, V, 7), dtype=torch.float32, device=dev) if return_graph else None,
             torch.empty((B, V, V), dtype=torch.uint8, device=dev) if return_graph else None,
             torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)
+
+
+def _shortcut_call(who: str, points: torch.Tensor, count: torch.Tensor, T: int, return_trace: bool, options: dict, others=()):
+    """What both shortcut wrappers start from and end with: the polylines ``[B,Pin,7]`` and ``count`` ``[B]`` on the current
+    GPU, the options, the outputs in the entry's order -> ``run(entry, *environment)`` that calls ``entry`` and returns
+    ``traj, status, points_out, count_out, length`` (with ``return_trace`` also ``chords, configs``), and the merged options."""
+    _lib.require_cuda(points, count, *others)
+    assert points.ndim == 3 and points.size(2) == 7 and count.shape == (points.size(0),)
+    B, Pin, dev = points.size(0), points.size(1), points.device
+    pts, cn = _lib.f32c(points), _lib.i32c(count)
+    copt, o = _shortcut_options(who, options)
+    P = max(int(o["points"]), 0)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, **i32),
+           torch.empty((B, P, 7), dtype=torch.float32, device=dev), torch.empty(B, **i32),
+           torch.empty((B, 2), dtype=torch.float32, device=dev), torch.empty(B, **i32) if return_trace else None,
+           torch.empty(B, **i32) if return_trace else None)
+
+    def run(entry: str, finger: float, *environment):
+        _lib.call(entry, pts.data_ptr(), cn.data_ptr(), B, Pin, int(T), float(finger), *environment, ctypes.byref(copt),
+                  *_ptrs(out))
+        return out if return_trace else out[:5]
+
+    return run, o, B, dev
 
 
 def _ptrs(tensors):
@@ -251,25 +285,75 @@ def franka_roadmap(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cy
     return out if return_graph else out[:4]
 
 
+def franka_shortcut(polylines: torch.Tensor, count: torch.Tensor, cuboids=None, cylinders=None, T: int = 50,
+                    return_trace: bool = False, with_base_link: bool = False, finger: float = ft.FINGER_OPENING, **options):
+    """Shortcut one joint-space polyline per problem on the GPU (csrc/shortcut_kernel.inc in roadmap.hip): ``passes``
+    alternating forward / backward passes, each densifying the polyline to at most ``points`` points and walking it
+    greedily -- from the current anchor to the furthest point whose chord is free by ``franka_roadmap``'s edge test, found
+    by a ``fanout``-ary search.  Where the reference asks its planner for ``shortcut=True``; a stand-in by this engine's
+    sphere model, not OMPL's simplifier.  Deterministic: no seed.
+
+    :param polylines: [B,Pin,7] float32 (the C entry's ``points``; ``points`` here is the option P), ``count`` int [B]: the
+        polyline of a row is its first ``count`` vertices (2 <= count <= Pin <= 256), e.g. ``nodes[path]`` of
+        ``franka_roadmap(..., return_graph=True)``.  The caller vouches for its segments: they are not tested
+    :param cuboids, cylinders: as for ``franka_roadmap``
+    :param options: the fields of ``mpx_shortcut_options``, see ``SHORTCUT_DEFAULTS``
+    :returns: ``traj`` [B,T,7] (``franka_roadmap``'s resampling and corner filter over the returned polyline; a one-edge
+        result is ``franka_plan``'s line bit for bit; NaN rows where ``status`` != 0), ``status`` int32 [B] (0 a polyline is
+        returned, 2 a bad row: count < 2, count > Pin or a non-finite vertex), ``points_out`` [B,P,7] (NaN rows beyond
+        ``count_out``), ``count_out`` int32 [B] and ``length`` [B,2] (before, after); with ``return_trace`` also ``chords``
+        and ``configs`` int32 [B], the chords and interior configurations tested."""
+    run, o, B, dev = _shortcut_call("franka_shortcut", polylines, count, T, return_trace, options)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    return run("mpx_franka_shortcut", finger, *prims)
+
+
+def _path_vertices(nodes: torch.Tensor, path: torch.Tensor, hops: torch.Tensor):
+    """``nodes[path]`` of a roadmap's graph -> the polylines [B,V,7] (rows behind a path: node 0) and their vertex counts
+    (0 where the roadmap found nothing: a bad row for the shortcut, whose NaN ``traj`` is the planner's NaN seed)."""
+    idx = path.clamp(min=0).long()[:, :, None].expand(-1, -1, 7)
+    return torch.gather(nodes, 1, idx), torch.where(hops > 0, hops + 1, torch.zeros_like(hops))
+
+
+def _shortcut_arg(shortcut) -> Optional[dict]:
+    """``shortcut`` of the global planners -> None (off) or the options dict."""
+    if shortcut is None or shortcut is False:
+        return None
+    return {} if shortcut is True else dict(shortcut)
+
+
 def franka_plan_global(q_start: torch.Tensor, q_goal: torch.Tensor, cuboids=None, cylinders=None, T: int = 50, seed: int = 0,
                        env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL,
                        with_base_link: bool = False, finger: float = ft.FINGER_OPENING, roadmap: Optional[dict] = None,
-                       **options):
+                       shortcut=None, **options):
     """``franka_roadmap``, then ``franka_plan`` with the roadmap's trajectory as one more candidate behind the drawn ones:
     a row ``franka_plan`` solves comes back identical, a row whose straight line is blocked gets a start that already
     goes round the obstacle.  Rows where the roadmap found nothing pass a NaN seed (bits 7).
 
     :param roadmap: options of ``franka_roadmap`` (``ROADMAP_DEFAULTS``); ``check_margin``, ``clearance`` and ``check_self``
         default to the planner's values in ``options``
-    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 <= 16
-    :returns: what ``franka_plan`` returns (``all_traj`` / ``all_status`` with ``candidates`` + 1 rows, the seed last), then
-        the roadmap's ``status`` int32 [B]."""
+    :param shortcut: None (the call above, unchanged), or True / a dict of ``franka_shortcut``'s options
+        (``SHORTCUT_DEFAULTS``; the three shared ones and ``resolution`` / ``smooth_passes`` default to the roadmap's): the
+        roadmap's path is shortcut and TWO seeds are passed, the shortcut trajectory (candidate ``candidates``) in front of
+        the roadmap's (``candidates`` + 1).  The lowest valid candidate wins, so no row solved without ``shortcut`` is lost
+    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 (with ``shortcut``: + 2) <= 16
+    :returns: what ``franka_plan`` returns (``all_traj`` / ``all_status`` with the seeds last), then the roadmap's
+        ``status`` int32 [B]."""
     _, o = _plan_options("franka_plan_global", options)
     shared = {k: o[k] for k in ("check_margin", "clearance", "check_self")}
-    seed_traj, rm_status, _, _ = franka_roadmap(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, False, limits,
-                                                with_base_link, finger, **dict(shared, **(roadmap or {})))
+    ropt = dict(shared, **(roadmap or {}))
+    sopt = _shortcut_arg(shortcut)
+    seed_traj, rm_status, path, hops, *graph = franka_roadmap(q_start, q_goal, cuboids, cylinders, T, seed, env_offset,
+                                                              sopt is not None, limits, with_base_link, finger, **ropt)
+    seeds = seed_traj[:, None]
+    if sopt is not None:
+        pts, cnt = _path_vertices(graph[0], path, hops)
+        inherited = {k: ropt[k] for k in ("check_margin", "clearance", "check_self", "resolution", "smooth_passes") if k in ropt}
+        short = franka_shortcut(pts, cnt, cuboids, cylinders, T, False, with_base_link, finger,
+                                **{"points": max(SHORTCUT_DEFAULTS["points"], pts.size(1)), **inherited, **sopt})[0]
+        seeds = torch.stack((short, seed_traj), 1)
     out = franka_plan(q_start, q_goal, cuboids, cylinders, T, seed, env_offset, return_all, limits, with_base_link, finger,
-                      seeds=seed_traj[:, None], **options)
+                      seeds=seeds, **options)
     return tuple(out) + (rm_status,)
 
 
@@ -612,6 +696,31 @@ def franka_roadmap_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: Opt
     return out if return_graph else out[:4]
 
 
+def franka_shortcut_cloud(polylines: torch.Tensor, count: torch.Tensor, cloud: Optional[torch.Tensor],
+                          counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, field_slack: float = 0.0,
+                          T: int = 50, return_trace: bool = False, with_base_link: bool = False,
+                          finger: float = ft.FINGER_OPENING, **options):
+    """``franka_shortcut`` against one POINT CLOUD per environment (csrc/shortcut_kernel.inc in roadmap_cloud.hip): the same
+    passes, densification, greedy walk and outputs, with ``franka_roadmap_cloud``'s validity test -- the cloud's truncated
+    distance field, ``point_radius``, ``field_slack``, "outside the grid or saturated: free".  The field approximates the
+    distance, so the result only seeds ``franka_plan_cloud(seeds=...)``, which judges by the exact test.
+
+    :param polylines, count: as for ``franka_shortcut``
+    :param cloud, counts, field, point_radius, field_slack: as for ``franka_roadmap_cloud`` (None and None: no environment)
+    :param options: the fields of ``mpx_shortcut_options``, see ``SHORTCUT_DEFAULTS``
+    :returns: what ``franka_shortcut`` returns."""
+    who = "franka_shortcut_cloud"
+    run, o, B, dev = _shortcut_call(who, polylines, count, T, return_trace, options, (cloud, counts))
+    if cloud is not None or field is not None:
+        cn = None if cloud is None else cloud_args(who, cloud, counts, B, point_radius)[1]
+        field = _plan_cloud_field(who, cloud, cn, field, B, point_radius, o["clearance"], PLAN_DEFAULTS["epsilon"],
+                                  with_base_link)
+    sc, sr, sl = sphere_table(dev, with_base_link)
+    return run("mpx_franka_shortcut_cloud", finger, sc.data_ptr(), sr.data_ptr(), sl.data_ptr(), int(sc.size(0)),
+               None if field is None else field.values.data_ptr(), None if field is None else ctypes.byref(field.grid),
+               float(point_radius), float(field_slack))
+
+
 def gripper_roadmap_cloud(start_pose: torch.Tensor, goal_pose: torch.Tensor, cloud: Optional[torch.Tensor],
                           counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, field_slack: float = 0.0,
                           W: int = 8, bounds=None, seed: int = 0, env_offset: int = 0, return_graph: bool = False,
@@ -657,7 +766,7 @@ def franka_plan_global_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud:
                              counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, T: int = 50,
                              seed: int = 0, env_offset: int = 0, return_all: bool = False, limits=ft.JOINT_LIMITS_REAL,
                              with_base_link: bool = False, finger: float = ft.FINGER_OPENING, field_slack: float = 0.0,
-                             roadmap: Optional[dict] = None, **options):
+                             roadmap: Optional[dict] = None, shortcut=None, **options):
     """``franka_roadmap_cloud``, then ``franka_plan_cloud`` with the roadmap's trajectory as one more candidate behind the
     drawn ones, both reading ONE field of the cloud (built here when ``field`` is None): a row ``franka_plan_cloud`` solves
     comes back identical, a row whose straight line is blocked gets a start that already goes round the obstacle.  Rows
@@ -665,9 +774,12 @@ def franka_plan_global_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud:
 
     :param roadmap: options of ``franka_roadmap_cloud`` (``ROADMAP_DEFAULTS``); ``check_margin``, ``clearance`` and
         ``check_self`` default to the planner's values in ``options``
-    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 <= 16
-    :returns: what ``franka_plan_cloud`` returns (``all_traj`` / ``all_status`` with ``candidates`` + 1 rows, the seed last),
-        then the roadmap's ``status`` int32 [B]."""
+    :param shortcut: None (the call above, unchanged), or True / a dict of ``franka_shortcut_cloud``'s options, on
+        ``franka_plan_global``'s terms: two seeds, the shortcut trajectory in front of the roadmap's, through the same field
+        at the same ``point_radius`` and ``field_slack``
+    :param options: the fields of ``mpx_plan_options``; ``candidates`` (8) + 1 (with ``shortcut``: + 2) <= 16
+    :returns: what ``franka_plan_cloud`` returns (``all_traj`` / ``all_status`` with the seeds last), then the roadmap's
+        ``status`` int32 [B]."""
     _, o = _plan_options("franka_plan_global_cloud", options)
     B = q_start.size(0)
     _lib.require_cuda(q_start, cloud, counts)
@@ -675,9 +787,18 @@ def franka_plan_global_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud:
     field = _plan_cloud_field("franka_plan_global_cloud", cloud, cn, field, B, point_radius, o["clearance"], o["epsilon"],
                               with_base_link)
     shared = {k: o[k] for k in ("check_margin", "clearance", "check_self")}
-    seed_traj, rm_status, _, _ = franka_roadmap_cloud(q_start, q_goal, cloud, counts, field, point_radius, field_slack, T, seed,
-                                                      env_offset, False, limits, with_base_link, finger,
-                                                      **dict(shared, **(roadmap or {})))
+    ropt = dict(shared, **(roadmap or {}))
+    sopt = _shortcut_arg(shortcut)
+    seed_traj, rm_status, path, hops, *graph = franka_roadmap_cloud(q_start, q_goal, cloud, counts, field, point_radius,
+                                                                    field_slack, T, seed, env_offset, sopt is not None, limits,
+                                                                    with_base_link, finger, **ropt)
+    seeds = seed_traj[:, None]
+    if sopt is not None:
+        pts, cnt = _path_vertices(graph[0], path, hops)
+        inherited = {k: ropt[k] for k in ("check_margin", "clearance", "check_self", "resolution", "smooth_passes") if k in ropt}
+        short = franka_shortcut_cloud(pts, cnt, cloud, counts, field, point_radius, field_slack, T, False, with_base_link,
+                                      finger, **{"points": max(SHORTCUT_DEFAULTS["points"], pts.size(1)), **inherited, **sopt})[0]
+        seeds = torch.stack((short, seed_traj), 1)
     out = franka_plan_cloud(q_start, q_goal, cloud, counts, field, point_radius, T, seed, env_offset, return_all, limits,
-                            with_base_link, finger, seeds=seed_traj[:, None], **options)
+                            with_base_link, finger, seeds=seeds, **options)
     return tuple(out) + (rm_status,)
