@@ -30,7 +30,8 @@ typedef void *mpx_stream_t;
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
 int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding):
-                          mpx_franka_shortcut, mpx_franka_shortcut_cloud, struct mpx_shortcut_options; 341 (unchanged, likewise):
+                          mpx_gripper_shortcut, mpx_gripper_shortcut_cloud, struct mpx_gripper_shortcut_options;
+                          341 (unchanged, likewise): mpx_franka_shortcut, mpx_franka_shortcut_cloud, struct mpx_shortcut_options; 341 (unchanged, likewise):
                           mpx_task_candidates, struct mpx_task_candidates_options; 341 (unchanged, likewise):
                           the form query mpx_linear_form; 341 (unchanged, likewise):
                           mpx_gripper_roadmap_cloud; 341 (unchanged, likewise): mpx_franka_follow_cloud,
@@ -885,6 +886,78 @@ int mpx_gripper_roadmap_cloud(const float *start_pose, const float *goal_pose, i
                               const mpx_gripper_roadmap_options *options, uint64_t seed, int64_t env_offset, float *poses,
                               int32_t *status, int32_t *path, int32_t *hops, float *nodes, uint8_t *edge_state,
                               int32_t *rounds, mpx_stream_t stream);
+
+/* Shortcutting of an SE(3) polyline of the free-flying gripper per problem, between a gripper roadmap and the follower:
+ * mpx_franka_shortcut's algorithm over mpx_gripper_roadmap's metric, edge pose and validity.  Part of the same STAND-IN for
+ * the reference's end-effector planner (data_pipeline/gen_data.py:156-189, an asymptotically optimal planner), NOT a port of
+ * it; valid by this engine's sphere model.  One workgroup per problem, no randomness (no seed, no env_offset): row b depends
+ * on row b's inputs alone.
+ *   points float32 [B,Pin,7], count int32 [B]: the polyline of problem b is its first count_b rows, 2 <= Pin <=
+ *   MPX_ROADMAP_MAX_NODES; a vertex is (p, q), position and unit quaternion (x, y, z, w), a node of mpx_gripper_roadmap.
+ *   The caller vouches for its segments: they are never tested.  The sign of an input quaternion is free (q and -q give the
+ *   same lengths, the same interior rotations and the same verdicts).
+ *   status int32 [B]: 0 a polyline is returned, shortened or unchanged; 2 a bad row -- count < 2, count > Pin, a vertex that is
+ *   not finite, or a vertex quaternion whose |q|^2 = fma(q_3, q_3, fma(q_2, q_2, fma(q_1, q_1, q_0 q_0))) is not within
+ *   2^-10 of 1 (|(|q|^2) - 1| <= 2^-10 passes: a quaternion far from unit length would make NaN poses, which every
+ *   comparison calls free) -- for which nothing is tested.  There is no status 1, as for mpx_franka_shortcut.
+ *   Geometry.  The length of a segment (a,b) is mpx_gripper_roadmap's w with this struct's rot_weight, (2 rot_weight)^2
+ *   rounded as there; a CHORD from a to e, a before e in the pass's order, has that contract's n pieces of w(a,e) at this
+ *   struct's resolution and the interior poses i = 1 .. n-1 of its edge (a,e): f = (float)i / (float)n, p by fma, q by nlerp
+ *   toward sigma_ae q_e, taken from a, the end that comes first.  The chord is BLOCKED exactly when an interior pose is
+ *   invalid.
+ *   A pose is VALID by mpx_gripper_roadmap's clause (mpx_gripper_shortcut: the gripper's rows of the sphere table, links 9 /
+ *   12 / 13, against the live primitives; the self test on the three frame origins) or by mpx_gripper_roadmap_cloud's
+ *   (mpx_gripper_shortcut_cloud: the 8-load field sample, point_radius, field_slack, "outside the grid or saturated: free",
+ *   field == NULL: no environment test and S may be 0), with this struct's check_margin, clearance and check_self.
+ *   Pass, Densify, Greedy: mpx_franka_shortcut's clauses, word for word, with "w_i" the length above and an interior point
+ *   k = 1 .. m_i of densify the edge pose of (v_i, v_{i+1}) at f = (float)k / (float)(m_i+1) (fma positions, nlerp), the
+ *   probes lo + (span k + K-1) / K, `chords` and `configs` (interior POSES here) counted as there.  An odd pass reverses the
+ *   vertices, does the steps and reverses the result back; an nlerp taken from the other end may return -q where the even
+ *   pass returns q: the same rotation.
+ *   points_out [B,P,7], count_out int32 [B]: the returned polyline, NaN rows behind it (status 2: count_out 0, all NaN).  Its
+ *   first and last vertex are bit-equal to the input's.  length float32 [B,2]: the input's and the returned polyline's
+ *   length, each summed in path order in float32 (NaN with status 2).  Optional: chords int32 [B], configs int32 [B] (0 with
+ *   status 2).  (w takes the CHORD of a quaternion pair and an nlerp runs along the arc, so the pieces of an edge sum to
+ *   slightly more than the edge: a polyline from which nothing is cut may come back a few parts in a million longer.)
+ *   poses [B,W,4,4], 1 <= W <= MPX_FOLLOW_MAX_POSES: mpx_gripper_roadmap's clause "poses" over the returned polyline, by the
+ *   same statements (c_i, s_t, the last edge with c_i <= s_t, the edge's nlerp in polyline order).  goal_pose [B,4,4] or
+ *   NULL: rows 0-2 of pose W-1 are goal_pose's bit for bit; with NULL they are [R | p] of the last vertex itself.  Row 3 of
+ *   every pose is (0, 0, 0, 1).  Rows with status 2 are NaN (all 16 entries).  With passes = 0, the vertices nodes[path] of a
+ *   gripper roadmap and that roadmap's goal_pose, poses is that roadmap's poses bit for bit.
+ *   finger, the sphere table, the primitives, field, grid, point_radius and field_slack exactly as for mpx_gripper_roadmap /
+ *   mpx_gripper_roadmap_cloud.
+ * Refused before any launch: what mpx_franka_shortcut refuses about Pin, points, passes, fanout, resolution, check_margin,
+ * clearance and NULL pointers; what mpx_gripper_roadmap refuses about W, S > 64, M1 / M2 and rot_weight; B x W x 16 or
+ * B x P x 7 >= 2^31; for the cloud form what mpx_gripper_roadmap_cloud refuses about the field, the grid, point_radius,
+ * field_slack and trunc.  B == 0 launches nothing (a bad option is still refused).
+ * One workgroup of 256 threads per problem, everything but the field in LDS: the 128 primitive rows (8192 B), the 64 gripper
+ * sphere rows and their count (1028 B) and the shortcut's arrays without a trajectory buffer (92 P + 24 B): 32 796 B at 256
+ * points, 24 604 B for the cloud form (no primitive rows).  No allocation, no scratch, no global atomics; one kernel on
+ * `stream` (capturable).                                                                                                */
+typedef struct mpx_gripper_shortcut_options { /* NULL options: MPX_SHORTCUT_DEFAULT_POINTS / _PASSES / _FANOUT, resolution
+                                                 MPX_GRIPPER_ROADMAP_DEFAULT_RESOLUTION, rot_weight
+                                                 MPX_GRIPPER_ROADMAP_DEFAULT_ROT_WEIGHT, check_margin
+                                                 MPX_PLAN_DEFAULT_CHECK_MARGIN, clearance 0, check_self 1 */
+  int points;                                 /* P: Pin .. MPX_ROADMAP_MAX_NODES, the dense polyline's points   */
+  int passes;                                 /* >= 0: forward, backward, forward, ...                         */
+  int fanout;                                 /* K: 1 .. MPX_SHORTCUT_MAX_FANOUT probes per level              */
+  float resolution;                           /* > 0 [m]: the longest piece of a chord (the metric w)          */
+  float rot_weight;                           /* > 0 [m/rad]: what a radian of rotation counts in w            */
+  float check_margin;                         /* >= 0 [m], as in mpx_plan_options                              */
+  float clearance;                            /* [m], added to the radii                                       */
+  int check_self;                             /* non-zero: the body column invalidates a pose                  */
+} mpx_gripper_shortcut_options;
+int mpx_gripper_shortcut(const float *points, const int32_t *count, int B, int Pin, int W, const float *goal_pose, float finger,
+                         const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                         const float *cub_inv_frames, const float *cub_dims, int M1, const float *cyl_inv_frames,
+                         const float *cyl_radii, const float *cyl_heights, int M2,
+                         const mpx_gripper_shortcut_options *options, float *poses, int32_t *status, float *points_out,
+                         int32_t *count_out, float *length, int32_t *chords, int32_t *configs, mpx_stream_t stream);
+int mpx_gripper_shortcut_cloud(const float *points, const int32_t *count, int B, int Pin, int W, const float *goal_pose,
+                               float finger, const float *sph_centers, const float *sph_radii, const int32_t *sph_link, int S,
+                               const float *field, const mpx_field_grid *grid, float point_radius, float field_slack,
+                               const mpx_gripper_shortcut_options *options, float *poses, int32_t *status, float *points_out,
+                               int32_t *count_out, float *length, int32_t *chords, int32_t *configs, mpx_stream_t stream);
 
 /* mpx_franka_follow against a POINT CLOUD: the same follower -- still the STAND-IN for the reference's Geometric Fabrics
  * expert, NOT Lula's fabric, no parity claimed.  Every clause of mpx_franka_follow's contract holds unchanged -- the state,

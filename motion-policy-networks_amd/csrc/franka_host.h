@@ -34,6 +34,10 @@ static inline mpx_gripper_roadmap_options gripper_roadmap_defaults() {
           MPX_GRIPPER_ROADMAP_DEFAULT_ORIENT_SPREAD, __builtin_inff(), MPX_GRIPPER_ROADMAP_DEFAULT_MAX_ROUNDS,
           MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
 }
+static inline mpx_gripper_shortcut_options gripper_shortcut_defaults() {
+  return {MPX_SHORTCUT_DEFAULT_POINTS, MPX_SHORTCUT_DEFAULT_PASSES, MPX_SHORTCUT_DEFAULT_FANOUT,
+          MPX_GRIPPER_ROADMAP_DEFAULT_RESOLUTION, MPX_GRIPPER_ROADMAP_DEFAULT_ROT_WEIGHT, MPX_PLAN_DEFAULT_CHECK_MARGIN, 0.0f, 1};
+}
 static inline mpx_task_candidates_options task_candidates_defaults() { return {MPX_TASK_DEFAULT_DRAWS, 0.0f, 1, 0.0f, 0}; }
 static inline mpx_follow_options franka_follow_defaults() {
   return {MPX_FOLLOW_DEFAULT_DT, MPX_FOLLOW_DEFAULT_MAX_STEPS, MPX_FOLLOW_DEFAULT_ATTRACT, MPX_FOLLOW_DEFAULT_DAMPING,
@@ -133,6 +137,23 @@ static inline int gripper_roadmap_options_check(const char *who, int W, const mp
   MPX_REQUIRE(opt.orient_spread >= 0.0f && opt.orient_spread < __builtin_inff(), "%s: orient_spread must be >= 0 and finite", who);
   MPX_REQUIRE(opt.connect_radius == opt.connect_radius, "%s: connect_radius is NaN", who);
   MPX_REQUIRE(opt.max_rounds >= 1, "%s: max_rounds = %d, need >= 1", who, opt.max_rounds);
+  MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
+  MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
+  return 0;
+}
+// (the shortcut's sizes in mpx_franka_shortcut's words, W and rot_weight in mpx_gripper_roadmap's)
+static inline int gripper_shortcut_options_check(const char *who, int W, int Pin, const mpx_gripper_shortcut_options &opt) {
+  MPX_REQUIRE(W >= 1 && W <= MPX_FOLLOW_MAX_POSES, "%s: W = %d guide poses, need 1 .. %d (one thread each)", who, W,
+              MPX_FOLLOW_MAX_POSES);
+  MPX_REQUIRE(Pin >= 2 && Pin <= MPX_ROADMAP_MAX_NODES, "%s: Pin = %d vertices per polyline, need 2 .. %d (one thread each)", who,
+              Pin, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.points >= Pin && opt.points <= MPX_ROADMAP_MAX_NODES, "%s: points = %d, need Pin = %d .. %d (one thread each)",
+              who, opt.points, Pin, MPX_ROADMAP_MAX_NODES);
+  MPX_REQUIRE(opt.passes >= 0, "%s: passes = %d, need >= 0", who, opt.passes);
+  MPX_REQUIRE(opt.fanout >= 1 && opt.fanout <= MPX_SHORTCUT_MAX_FANOUT, "%s: fanout = %d, need 1 .. %d", who, opt.fanout,
+              MPX_SHORTCUT_MAX_FANOUT);
+  MPX_REQUIRE(opt.resolution > 0.0f, "%s: resolution must be > 0", who);
+  MPX_REQUIRE(opt.rot_weight > 0.0f && opt.rot_weight < __builtin_inff(), "%s: rot_weight must be > 0 and finite", who);
   MPX_REQUIRE(opt.check_margin >= 0.0f, "%s: negative check_margin", who);
   MPX_REQUIRE(opt.clearance == opt.clearance, "%s: clearance is NaN", who);
   return 0;

@@ -1,7 +1,7 @@
 // franka_live_rows.inc -- problem b's live primitives, compacted into 128 LDS rows of 16 floats,
 // [R | Rt (3 x 4 floats) | full sizes]: cuboids from row 0, cylinders from row 64 (M1, M2 <= 64).  Lane m of a wave tests
 // primitive m; a live one takes the slot = number of live ones before it.  Included as a statement block by ik.hip,
-// plan.hip, roadmap.hip, gripper_roadmap.hip and task_candidates.hip (one inline function for both made franka_ik_kernel slower: profiles/franka_device_timing.md); the compiler
+// plan.hip, roadmap.hip, gripper_roadmap.hip, gripper_shortcut.hip and task_candidates.hip (one inline function for both made franka_ik_kernel slower: profiles/franka_device_timing.md); the compiler
 // sees the lines it saw when each kernel wrote them out.
 //   in scope: b, lane, cub_f, cub_d, M1, cyl_f, cyl_r, cyl_h, M2, float *prim_rows
 //   FRANKA_LIVE_ROWS_STORE: this wave writes the rows (every wave gets the counts)

@@ -1,9 +1,9 @@
 // gripper_device.h -- the free-flying gripper as the two gripper roadmap kernels take it (gripper_roadmap.hip against
-// primitives, gripper_roadmap_cloud.hip against a distance field) and, for its validity against primitives,
-// task_candidates.hip: a node (position, unit quaternion x y z w) from a pose
+// primitives, gripper_roadmap_cloud.hip against a distance field), the two shortcut kernels behind them (gripper_shortcut.hip,
+// gripper_shortcut_cloud.hip) and, for its validity against primitives, task_candidates.hip: a node (position, unit quaternion x y z w) from a pose
 // and back, the SE(3) metric, the nlerp edge pose and the self half of a pose's validity.  One text for both; what differs
 // between them (the LDS layout, the environment half of the validity, the host entry) stays in each .hip, and the statement
-// blocks they share are gripper_spheres.inc, gripper_nodes.inc and gripper_tail.inc.  The contract is stated in
+// blocks they share are gripper_spheres.inc, gripper_nodes.inc, gripper_tail.inc and gripper_poses.inc.  The contract is stated in
 // include/mpinets_hip.h (mpx_gripper_roadmap).
 #pragma once
 #include "common.h"
@@ -49,8 +49,19 @@ __device__ __forceinline__ Rigid gripper_frame(const float *node) {
   return g;
 }
 
+// rows 0-2 of the row-major 4x4 pose [R | p] of a frame (12 floats)
+__device__ __forceinline__ void gripper_frame_rows(const Rigid &g, float *o) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) o[4 * r + 0] = g.r[3 * r + 0], o[4 * r + 1] = g.r[3 * r + 1], o[4 * r + 2] = g.r[3 * r + 2], o[4 * r + 3] = g.t[r];
+}
+
 __device__ __forceinline__ float gripper_dot4(const float *a, const float *b) {
   return mpx_fma(a[3], b[3], mpx_fma(a[2], b[2], mpx_fma(a[1], b[1], a[0] * b[0])));
+}
+
+// a caller's vertex (mpx_gripper_shortcut): its quaternion's squared norm is not within 2^-10 of 1 (NaN: bad)
+__device__ __forceinline__ bool gripper_vertex_bad(const float *node) {
+  return !(fabsf(gripper_dot4(node + 3, node + 3) - 1.0f) <= 0x1p-10f);
 }
 
 // w_ab: k ascending, the first square rounded on its own, the others fused; positions first, then (2 rot_weight)^2 times

@@ -18,6 +18,7 @@
 #include "field_device.h"
 #include "roadmap_device.h"
 #include "gripper_device.h"
+#include "gripper_cloud_device.h"
 
 // LDS, in 4-byte words: gripper_roadmap.hip's layout without the primitive rows: [gripper spheres 64 x 4 (point in the
 // right_gripper frame, radius) | nodes V x 7 | dist 2 x V (later: cumulative and edge lengths) | pred, path, rev, pieces,
@@ -25,29 +26,6 @@
 __host__ __device__ static inline size_t gripper_roadmap_cloud_lds_words(int V) {
   return (size_t)GRM_MAX_SPHERES * 4 + (size_t)V * 7 + 2 * (size_t)V + 6 * (size_t)V + (size_t)V + 1 + 1 + 1 +
          ((size_t)V * V + 15) / 16;
-}
-
-// roadmap_cloud_bits' rule on the gripper alone: a sphere whose centre is inside the grid, where the field is not saturated
-// and d = ((D - point_radius) - r_s) - clearance <= slack_margin (= check_margin + field_slack, summed once on the host), or
-// (test_self) the origin of the hand or a fingertip frame inside the body column.  `f` is ONE environment's nodes, nullptr:
-// no environment test.  (A NaN centre is outside the grid: it reads no memory.)
-__device__ __forceinline__ bool gripper_cloud_pose_hit(const float *node, float finger, const float *gsph, int n_g,
-                                                       const float *__restrict__ f, const FieldGrid &G, float point_radius,
-                                                       float clearance, float slack_margin, bool test_self,
-                                                       float self_margin) {
-  const Rigid g = gripper_frame(node);
-  bool hit = false;
-  if (f) {
-    for (int s = 0; s < n_g; ++s) {
-      float x, y, z, D, gx, gy, gz;
-      rigid_apply(g, gsph[4 * s + 0], gsph[4 * s + 1], gsph[4 * s + 2], x, y, z);
-      const bool inside = field_sample<false>(f, G, x, y, z, D, gx, gy, gz);
-      const float d = ((D - point_radius) - gsph[4 * s + 3]) - clearance;
-      hit |= inside && D < G.trunc && d <= slack_margin;
-    }
-  }
-  if (test_self) hit |= gripper_self_hit(g, finger, self_margin);
-  return hit;
 }
 
 __global__ void __launch_bounds__(ROADMAP_THREADS)

@@ -1,7 +1,8 @@
 // gripper_spheres.inc -- the gripper's rows of the sphere table (links 9, 12, 13), in table order, as points of the
 // right_gripper frame, compacted into LDS: a point h of the hand frame sits at (-h_x, -h_y, h_z - 0.1); a fingertip frame is
 // the hand frame shifted by (0, +-finger, 0.0584 + 0.045).  Wave 1 lane s takes row s (S <= 64).  Included as a statement
-// block by gripper_roadmap.hip, gripper_roadmap_cloud.hip and task_candidates.hip; the compiler sees the lines it saw when the first wrote them
+// block by gripper_roadmap.hip, gripper_roadmap_cloud.hip, task_candidates.hip and the two gripper shortcut kernels
+// (gripper_shortcut.hip, gripper_shortcut_cloud.hip); the compiler sees the lines it saw when the first wrote them
 // out (profiles/gripper_roadmap_cloud_timing.md has the instruction-stream comparison).
 //   in scope: k (the wave), lane, sc, sr, sl, S, finger, float *gsph (GRM_MAX_SPHERES x 4: point, radius), int *ng_lds
 //   The caller's barrier publishes the rows and the count.

@@ -14,8 +14,8 @@
 // own reduction.  The search itself is roadmap_search.inc, shared with gripper_roadmap.hip (the gripper's roadmap in SE(3)) and
 // roadmap_cloud.hip (this roadmap against a point cloud's distance field), which also shares what follows it, roadmap_tail.inc.
 // Behind the roadmap, franka_shortcut_kernel shortens a polyline (the roadmap's path, or any caller's) with the same validity
-// test: its body is shortcut_kernel.inc, shared with roadmap_cloud.hip's form, and ends with the seed trajectory's statements
-// (roadmap_traj.inc, which roadmap_tail.inc ends with).
+// test: its body is shortcut_kernel.inc, shared with roadmap_cloud.hip's form and with the gripper's shortcut kernels
+// (gripper_shortcut.hip), and it ends with the seed trajectory's statements (roadmap_traj.inc, which roadmap_tail.inc ends with).
 #include "common.h"
 #include "franka_host.h"
 #include "plan_prims_device.h"
@@ -151,8 +151,20 @@ __global__ void __launch_bounds__(ROADMAP_THREADS)
   // (the body's first barrier publishes the primitive rows)
 #define SHORTCUT_HIT(q) \
   plan_config_bits(q, finger, sc, sr, sl, S, prim_rows, n_cub, n_cyl, reach, test_self, opt.check_margin)
+#define SHORTCUT_LENGTH(a, e) roadmap_length(a, e)
+#define SHORTCUT_POINT(a, e, f, q) \
+  _Pragma("unroll") for (int j = 0; j < 7; ++j) q[j] = mpx_fma(f, e[j] - a[j], a[j]);
 #include "shortcut_kernel.inc"
 #undef SHORTCUT_HIT
+#undef SHORTCUT_LENGTH
+#undef SHORTCUT_POINT
+  // ---- the seed trajectory over the returned polyline (vertex i is nodes[path[i]], path[i] = i) --------------------------------------
+  const int V = P, hops = n - 1;
+  const float *nodes = cur;
+  float qs[7], qg[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) qs[j] = st == 0 ? cur[j] : nan, qg[j] = st == 0 ? cur[(n - 1) * 7 + j] : nan;
+#include "roadmap_traj.inc"
 }
 
 MPX_EXPORT int mpx_franka_shortcut(const float *points, const int32_t *count, int B, int Pin, int T, float finger,

@@ -174,8 +174,20 @@ __global__ void __launch_bounds__(ROADMAP_THREADS)
   const float *fenv = (field != nullptr && S > 0) ? field + (size_t)b * ((size_t)G.nx * G.ny * G.nz) : nullptr;
 #define SHORTCUT_HIT(q) \
   roadmap_cloud_bits(q, finger, sc, sr, sl, S, fenv, G, point_radius, opt.clearance, slack_margin, test_self, opt.check_margin)
+#define SHORTCUT_LENGTH(a, e) roadmap_length(a, e)
+#define SHORTCUT_POINT(a, e, f, q) \
+  _Pragma("unroll") for (int j = 0; j < 7; ++j) q[j] = mpx_fma(f, e[j] - a[j], a[j]);
 #include "shortcut_kernel.inc"
 #undef SHORTCUT_HIT
+#undef SHORTCUT_LENGTH
+#undef SHORTCUT_POINT
+  // ---- the seed trajectory over the returned polyline (vertex i is nodes[path[i]], path[i] = i) --------------------------------------
+  const int V = P, hops = n - 1;
+  const float *nodes = cur;
+  float qs[7], qg[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) qs[j] = st == 0 ? cur[j] : nan, qg[j] = st == 0 ? cur[(n - 1) * 7 + j] : nan;
+#include "roadmap_traj.inc"
 }
 
 MPX_EXPORT int mpx_franka_shortcut_cloud(const float *points, const int32_t *count, int B, int Pin, int T, float finger,

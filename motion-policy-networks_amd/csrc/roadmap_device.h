@@ -1,5 +1,5 @@
 // roadmap_device.h -- what the roadmap kernels share besides the search itself (roadmap_search.inc): the workgroup size, the
-// edge states and their 2-bit store in LDS, the pieces of an edge, the joint-space edge length.  roadmap.hip and roadmap_cloud.hip (joint space), gripper_roadmap.hip (SE(3)).
+// edge states and their 2-bit store in LDS, the pieces of an edge, the joint-space edge length.  roadmap.hip and roadmap_cloud.hip (joint space), gripper_roadmap.hip and gripper_shortcut.hip (SE(3)) and their cloud forms.
 #pragma once
 #include "common.h"
 
@@ -37,15 +37,17 @@ __device__ __forceinline__ void roadmap_edge_set(unsigned *bits, int V, int a, i
 
 // LDS of a shortcut kernel behind its primitive rows, in 4-byte words (shortcut_kernel.inc): [two polylines P x 7 | dist 2 x P
 // (edge lengths; later cumulative and edge lengths) | two trajectories 64 x 7 | path, sel, pidx, pieces, blocked: P ints each |
-// off, first: P + 1 each | ctl 4]
-__host__ __device__ static inline size_t shortcut_lds_words(int P) {
-  return 2 * (size_t)P * 7 + 2 * (size_t)P + 2 * 64 * 7 + 5 * (size_t)P + 2 * ((size_t)P + 1) + 4;
+// off, first: P + 1 each | ctl 4].  The gripper's shortcut kernels (gripper_shortcut.hip, gripper_shortcut_cloud.hip) end with
+// guide poses, not a trajectory: their tbuf has no words.
+__host__ __device__ static inline size_t shortcut_lds_words(int P, int tbuf_words = 2 * 64 * 7) {
+  return 2 * (size_t)P * 7 + 2 * (size_t)P + (size_t)tbuf_words + 5 * (size_t)P + 2 * ((size_t)P + 1) + 4;
 }
 // ... and its carving, from `base` on
-#define SHORTCUT_LDS_CARVE(base, P)                                                                                     \
+#define SHORTCUT_LDS_CARVE_T(base, P, TW)                                                                               \
   float *poly = (base);                                                                                                 \
   float *dist = poly + 2 * (P) * 7;                                                                                     \
   float *tbuf = dist + 2 * (P);                                                                                         \
-  int *path = reinterpret_cast<int *>(tbuf + 2 * 64 * 7);                                                               \
+  int *path = reinterpret_cast<int *>(tbuf + (TW));                                                                     \
   int *sel = path + (P), *pidx = sel + (P), *pieces = pidx + (P), *blocked = pieces + (P);                              \
   int *off = blocked + (P), *first = off + (P) + 1, *ctl = first + (P) + 1;
+#define SHORTCUT_LDS_CARVE(base, P) SHORTCUT_LDS_CARVE_T(base, P, 2 * 64 * 7)

@@ -1,8 +1,8 @@
 // roadmap_traj.inc -- the seed trajectory of a polyline in joint space: the planner's line for a one-edge polyline; else
 // the polyline resampled by arc length to T waypoints and rounded by opt.smooth_passes passes of (1/4, 1/2, 1/4).  The
 // clause "traj" of mpx_franka_roadmap's contract (include/mpinets_hip.h).  Included as a statement block, last in the
-// kernel, by roadmap_tail.inc (the roadmap kernels: the polyline is the path found) and shortcut_kernel.inc (the polyline
-// returned); the compiler sees the lines it saw when roadmap_tail.inc wrote them out (profiles/shortcut_timing.md has the
+// kernel, by roadmap_tail.inc (the roadmap kernels: the polyline is the path found) and, behind shortcut_kernel.inc, by the
+// two joint-space shortcut kernels of roadmap.hip and roadmap_cloud.hip (the polyline returned); the compiler sees the lines it saw when roadmap_tail.inc wrote them out (profiles/shortcut_timing.md has the
 // instruction-stream comparison).
 //   in scope: b, tid, T, nan, st (0: there is a polyline), hops (its edges), V, opt (.smooth_passes), float *nodes and
 //             int *path (vertex i is nodes[path[i]]), qs[7], qg[7] (its ends), float *dist (2 V), float *tbuf (2 x 64 x 7),

@@ -1,23 +1,26 @@
-// shortcut_kernel.inc -- the body of a shortcut kernel, from the caller's polyline to the seed trajectory: the row check, the
+// shortcut_kernel.inc -- the body of a shortcut kernel, from the caller's polyline to the returned one: the row check, the
 // length before, `passes` passes of (reverse on odd passes | densify to <= P points | greedy furthest-free-chord walk with a
-// K-ary search | reverse back), the length after, points_out / count_out / the trace, then roadmap_traj.inc over the
-// returned polyline.  The clauses "Pass", "Densify", "Greedy" and the outputs of mpx_franka_shortcut's contract
-// (include/mpinets_hip.h).  Included as a statement block, last in the kernel, by roadmap.hip (primitives) and
-// roadmap_cloud.hip (a point cloud's distance field).
-//   in scope: b, tid, T, opt (mpx_shortcut_options), Pin, nan, inf, the operands points, count and the outputs traj, status,
-//             points_out, count_out, length, chords_out, configs_out; in LDS float *poly (2 x P x 7), *dist (2 P), *tbuf
-//             (2 x 64 x 7), int *path, *sel, *pidx, *pieces, *blocked (P each), *off, *first (P + 1 each), *ctl (4); the
-//             helpers of roadmap_device.h
-//   SHORTCUT_HIT(q): the configuration float q[7] is invalid
+// K-ary search | reverse back), the length after, points_out / count_out / the trace.  The clauses "Pass", "Densify", "Greedy"
+// and the outputs of mpx_franka_shortcut's contract (include/mpinets_hip.h), which mpx_gripper_shortcut's refers to.  Included
+// as a statement block by roadmap.hip and roadmap_cloud.hip (joint space: the seed trajectory's statements, roadmap_traj.inc,
+// follow it) and by gripper_shortcut.hip and gripper_shortcut_cloud.hip (SE(3): the guide poses, gripper_poses.inc, follow it).
+//   in scope: b, tid, opt (.points, .passes, .fanout, .resolution), Pin, nan, inf, the operands points, count and the outputs
+//             status, points_out, count_out, length, chords_out, configs_out; in LDS float *poly (2 x P x 7), *dist (2 P),
+//             int *path, *sel, *pidx, *pieces, *blocked (P each), *off, *first (P + 1 each), *ctl (4); the helpers of
+//             roadmap_device.h
+//   the hooks roadmap_search.inc has -- SHORTCUT_LENGTH(a, e): the length of the segment between the vertices float a[7], e[7];
+//             SHORTCUT_POINT(a, e, f, q): float q[7] (registers or LDS) = the point at fraction f from a toward e; SHORTCUT_HIT(q): q is invalid --
+//             and, where a vertex can be bad beyond "not finite", SHORTCUT_VERTEX_BAD(v)
+//   leaves:   st (0 or 2), n (the vertices returned, 0 with st 2), float *cur (the returned polyline), P, path[i] = i
 // Three mappings: thread = vertex (load, reverse, densify, copy), thread = interior configuration across the concatenated
-// chords of one probe level (roadmap_search.inc's first[] prefix mapping), thread = waypoint (roadmap_traj.inc).  The anchor
+// chords of one probe level (roadmap_search.inc's first[] prefix mapping), thread = output row (what follows).  The anchor
 // walk, the probes and the prefix sums are serial on thread 0.  Every branch around a barrier is workgroup-uniform: it reads
 // a value from LDS behind a barrier, a kernel argument, or a barrier's own reduction.
 const int P = opt.points;
 const int cnt = count[b];
 float *cur = poly, *oth = poly + P * 7;
 bool broken = cnt < 2 || cnt > Pin;
-if (tid < P) path[tid] = tid;  // (roadmap_traj.inc walks nodes[path[i]]: the returned polyline in its own order)
+if (tid < P) path[tid] = tid;  // (what follows walks nodes[path[i]]: the returned polyline in its own order)
 if (!broken && tid < cnt) {
 #pragma unroll
   for (int j = 0; j < 7; ++j) {
@@ -25,6 +28,9 @@ if (!broken && tid < cnt) {
     cur[tid * 7 + j] = v;
     broken |= !(fabsf(v) < inf);
   }
+#ifdef SHORTCUT_VERTEX_BAD
+  broken |= SHORTCUT_VERTEX_BAD((cur + tid * 7));
+#endif
 }
 const int st = __syncthreads_or(broken) ? 2 : 0;  // (publishes the polyline and path[])
 int n = st == 0 ? cnt : 0;                        // the vertices of the current polyline
@@ -33,7 +39,7 @@ float before = nan, after = nan;
 if (st == 0) {
   if (tid == 0) {
     before = 0.0f;
-    for (int i = 0; i + 1 < n; ++i) before += roadmap_length(cur + i * 7, cur + (i + 1) * 7);
+    for (int i = 0; i + 1 < n; ++i) before += SHORTCUT_LENGTH((cur + i * 7), (cur + (i + 1) * 7));
   }
   for (int pass = 0; pass < opt.passes && n > 2; ++pass) {
     const bool backward = (pass & 1) != 0;
@@ -51,7 +57,7 @@ if (st == 0) {
       float *w = dist;
       float L = 0.0f;
       for (int i = 0; i + 1 < n; ++i) {
-        w[i] = roadmap_length(cur + i * 7, cur + (i + 1) * 7);
+        w[i] = SHORTCUT_LENGTH((cur + i * 7), (cur + (i + 1) * 7));
         L += w[i];
       }
       const int extra = P - n;
@@ -79,8 +85,7 @@ if (st == 0) {
         for (int j = 0; j < 7; ++j) oth[tid * 7 + j] = cur[i * 7 + j];
       } else {
         const float f = (float)k / (float)(off[i + 1] - off[i]);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) oth[tid * 7 + j] = mpx_fma(f, cur[(i + 1) * 7 + j] - cur[i * 7 + j], cur[i * 7 + j]);
+        SHORTCUT_POINT((cur + i * 7), (cur + (i + 1) * 7), f, (oth + tid * 7))
       }
     }
     __syncthreads();
@@ -120,7 +125,7 @@ if (st == 0) {
             const int pr = lo + (span * k + K - 1) / K;
             if (level > 0 && pidx[level - 1] == pr) continue;
             pidx[level] = pr;
-            pieces[level] = roadmap_pieces(roadmap_length(D + a * 7, D + pr * 7), opt.resolution);
+            pieces[level] = roadmap_pieces(SHORTCUT_LENGTH((D + a * 7), (D + pr * 7)), opt.resolution);
             first[level + 1] = first[level] + pieces[level] - 1;
             blocked[level] = 0;
             ++level;
@@ -143,8 +148,7 @@ if (st == 0) {
         const float *qe = D + pidx[i] * 7;
         const float f = (float)(c - first[i] + 1) / (float)pieces[i];
         float q[7];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) q[j] = mpx_fma(f, qe[j] - qa[j], qa[j]);
+        SHORTCUT_POINT(qa, qe, f, q)
         if (SHORTCUT_HIT(q)) blocked[i] = 1;  // (every lane that stores, stores 1)
       }
       __syncthreads();
@@ -167,7 +171,7 @@ if (st == 0) {
   }
   if (tid == 0) {
     after = 0.0f;
-    for (int i = 0; i + 1 < n; ++i) after += roadmap_length(cur + i * 7, cur + (i + 1) * 7);
+    for (int i = 0; i + 1 < n; ++i) after += SHORTCUT_LENGTH((cur + i * 7), (cur + (i + 1) * 7));
   }
 }
 
@@ -179,9 +183,3 @@ if (tid == 0) {
   if (configs_out) configs_out[b] = n_configs;
 }
 for (int i = tid; i < P * 7; i += ROADMAP_THREADS) points_out[(size_t)b * P * 7 + i] = i < n * 7 ? cur[i] : nan;
-const int V = P, hops = n - 1;
-const float *nodes = cur;
-float qs[7], qg[7];
-#pragma unroll
-for (int j = 0; j < 7; ++j) qs[j] = st == 0 ? cur[j] : nan, qg[j] = st == 0 ? cur[(n - 1) * 7 + j] : nan;
-#include "roadmap_traj.inc"

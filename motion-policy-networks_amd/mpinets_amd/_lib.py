@@ -57,6 +57,8 @@ PROTOTYPES = {
     "mpx_gripper_roadmap_cloud": [P, P, I, I, P, F, P, P, P, I, P, P, F, F, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_franka_shortcut": [P, P, I, I, I, F, P, P, P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P],
     "mpx_franka_shortcut_cloud": [P, P, I, I, I, F, P, P, P, I, P, P, F, F, P, P, P, P, P, P, P, P, P],
+    "mpx_gripper_shortcut": [P, P, I, I, I, P, F, P, P, P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P],
+    "mpx_gripper_shortcut_cloud": [P, P, I, I, I, P, F, P, P, P, I, P, P, F, F, P, P, P, P, P, P, P, P, P],
     "mpx_collision_hinge": [P, L, I, I, I, P, P, I, P, P, P, I, F, P, P, L, I, P],
     "mpx_point_match": [P, P, I, I, F, F, P, P, P],
     "mpx_franka_cloud_grad": [P, I, F, P, P, P, I, P, L, I, P, P],
@@ -175,6 +177,13 @@ class GripperRoadmapOptions(ctypes.Structure):
     _fields_ = [("nodes", c_int), ("resolution", c_float), ("rot_weight", c_float), ("orient_spread", c_float),
                 ("connect_radius", c_float), ("max_rounds", c_int), ("check_margin", c_float), ("clearance", c_float),
                 ("check_self", c_int)]
+
+
+class GripperShortcutOptions(ctypes.Structure):
+    """``mpx_gripper_shortcut_options`` (include/mpinets_hip.h); the defaults are the header's MPX_SHORTCUT_DEFAULT_* and the
+    gripper roadmap's."""
+    _fields_ = [("points", c_int), ("passes", c_int), ("fanout", c_int), ("resolution", c_float), ("rot_weight", c_float),
+                ("check_margin", c_float), ("clearance", c_float), ("check_self", c_int)]
 
 
 class TaskCandidatesOptions(ctypes.Structure):

@@ -121,7 +121,7 @@ _OPTION_FIELDS = {
     s: (itemgetter(*("damping" if n == "lambda_" and "damping" not in dict(s._fields_) else n for n, _ in s._fields_)),
         tuple(_self_flag if n in ("check_self", "test_self") else float if t is ctypes.c_float else int for n, t in s._fields_))
     for s in (_lib.IkOptions, _lib.PlanOptions, _lib.RoadmapOptions, _lib.ShortcutOptions, _lib.GripperRoadmapOptions,
-              _lib.FollowOptions, _lib.TaskCandidatesOptions)}
+              _lib.GripperShortcutOptions, _lib.FollowOptions, _lib.TaskCandidatesOptions)}
 
 
 def merge_options(who: str, struct, defaults: dict, options: dict):

@@ -158,7 +158,7 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
                   plan_options: Optional[dict] = None, global_plan: bool = False,
                   roadmap_options: Optional[dict] = None, follow: bool = False, follow_poses: int = 8,
                   follow_options: Optional[dict] = None, follow_guide: str = "plan",
-                  gripper_options: Optional[dict] = None, shortcut=False) -> dict:
+                  gripper_options: Optional[dict] = None, shortcut=False, follow_shortcut=False) -> dict:
     """From a cloud and a target pose to a checked trajectory: ``robot.franka_ik_cloud`` for the goal configuration, then
     ``robot.franka_plan_cloud`` from ``q_start`` to it, both against the same ``cloud`` (``counts``, ``point_radius``).  The
     optimiser-based counterpart of the reference demo's ``Planner.plan(q0, target_pose, obstacle_pc)``
@@ -193,11 +193,17 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
         options (``field_slack`` among them).  A row without an IK goal has a NaN goal pose and gets status 2.  Adds
         ``follow_guide_poses`` [B,W,4,4] (NaN rows without a path) and ``follow_guide_status`` int32 [B].  The guide no longer
         needs the optimiser: a row whose plan failed but whose IK succeeded can come back with a ``followed_trajectory``
-        (``follow_status`` 0, free by ``check_cloud``'s test); ``valid`` keeps its meaning (both the IK and the plan)."""
+        (``follow_status`` 0, free by ``check_cloud``'s test); ``valid`` keeps its meaning (both the IK and the plan).
+    :param follow_shortcut: False (every key and bit as before), or True / a dict of ``robot.gripper_shortcut_cloud``'s
+        options (needs ``follow_guide="gripper"``): the gripper roadmap's path is shortcut on the device through the same
+        field (``robot.gripper_plan_cloud``) before it is resampled; ``follow_guide_poses`` are then the shortcut's,
+        ``follow_guide_status`` stays the roadmap's."""
     if follow_guide not in ("plan", "gripper"):
         raise ValueError(f"follow_guide must be 'plan' or 'gripper', got {follow_guide!r}")
     if follow_guide == "gripper" and not follow:
         raise ValueError("follow_guide='gripper' chooses the follower's guide: it needs follow=True")
+    if follow_shortcut and follow_guide != "gripper":
+        raise ValueError("follow_shortcut shortens the gripper roadmap's path: it needs follow_guide='gripper'")
     if shortcut and not global_plan:
         raise ValueError("shortcut shortens the roadmap's path: it needs global_plan=True")
     if follow and field is None:  # (one field for the planner and the follower)
@@ -228,12 +234,19 @@ def plan_to_poses(cloud: torch.Tensor, q_start: torch.Tensor, target_poses: torc
         at = [int(round(i * (int(T) - 1) / W)) for i in range(1, W + 1)]
         gripper = ft.LINK_ID["right_gripper"]
         if follow_guide == "gripper":
-            from .solvers import gripper_roadmap_cloud
+            from .solvers import gripper_plan_cloud, gripper_roadmap_cloud
 
             ends = frames_to_matrix(franka_fk(torch.cat([q_start, q_goal]))[:, gripper])  # (a row without a goal: NaN, status 2)
-            guide, extra["follow_guide_status"] = gripper_roadmap_cloud(
-                ends[:B].contiguous(), ends[B:].contiguous(), cloud, counts, field=field, point_radius=point_radius, W=W,
-                seed=seed, env_offset=env_offset, **(gripper_options or {}))
+            if follow_shortcut:
+                ropt = dict(gripper_options or {})
+                guide, extra["follow_guide_status"] = gripper_plan_cloud(
+                    ends[:B].contiguous(), ends[B:].contiguous(), cloud, counts, field=field, point_radius=point_radius,
+                    field_slack=ropt.pop("field_slack", 0.0), W=W, seed=seed, env_offset=env_offset, roadmap=ropt,
+                    shortcut=follow_shortcut)
+            else:
+                guide, extra["follow_guide_status"] = gripper_roadmap_cloud(
+                    ends[:B].contiguous(), ends[B:].contiguous(), cloud, counts, field=field, point_radius=point_radius, W=W,
+                    seed=seed, env_offset=env_offset, **(gripper_options or {}))
             extra["follow_guide_poses"] = guide
         else:
             guide = frames_to_matrix(franka_fk(traj[:, at].reshape(-1, 7))[:, gripper]).reshape(B, W, 4, 4)

@@ -27,6 +27,8 @@ from .solvers import (FOLLOW_BAD_INPUT, FOLLOW_BIT_MISS, FOLLOW_DEFAULTS, FOLLOW
                       FOLLOW_PATH_BYTES, FOLLOW_VALID, _follow_options, franka_follow, franka_follow_cloud)
 from .solvers import (GRIPPER_ROADMAP_BOUNDS_PAD, GRIPPER_ROADMAP_DEFAULTS, _gripper_roadmap_options,  # noqa: F401
                       gripper_roadmap, gripper_roadmap_cloud)
+from .solvers import (GRIPPER_SHORTCUT_DEFAULTS, _gripper_shortcut_options, gripper_plan, gripper_plan_cloud,  # noqa: F401
+                      gripper_shortcut, gripper_shortcut_cloud)
 from .solvers import (SHORTCUT_BAD_ROW, SHORTCUT_DEFAULTS, SHORTCUT_RETURNED, _shortcut_options, franka_shortcut,  # noqa: F401
                       franka_shortcut_cloud)
 from .solvers import TASK_CANDIDATES_DEFAULTS, TASK_SURFACE, TASK_VOLUME, task_candidates  # noqa: F401

@@ -441,7 +441,7 @@ HYBRID_GUIDE_POSES = 8  # guide poses handed to the follower: waypoints round(i 
 
 def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, global_solutions: torch.Tensor,
                          expert_valid: torch.Tensor, q_goal: Optional[torch.Tensor] = None, seed: int = 0,
-                         env_offset: int = 0, gripper_guide: bool = False) -> Dict[str, torch.Tensor]:
+                         env_offset: int = 0, gripper_guide: bool = False, shortcut=False) -> Dict[str, torch.Tensor]:
     """``hybrid=True``: the global plan steers, the follower produces.  ``solvers.franka_follow`` (a stand-in for the
     reference's Geometric Fabrics expert, NOT Lula: gen_data.py:156-307) follows the right_gripper poses of eight waypoints
     of ``global_solutions``, its dense path is retimed to 50 waypoints and judged; the target becomes the pose the
@@ -452,10 +452,12 @@ def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
     gripper through the same primitives by ``solvers.gripper_roadmap`` (a stand-in for the reference's OMPL end-effector
     planner, gen_data.py:156-189, NOT a port of it), from the right_gripper pose of ``q_start`` to that of ``q_goal``, keyed
     by the batch's ``seed`` / ``env_offset``.  There is no fall-back to the global guide: a row without a gripper path hands
-    NaN poses to the follower (the reference drops such rows too: "end effector path")."""
+    NaN poses to the follower (the reference drops such rows too: "end effector path").  ``shortcut`` (True or a dict of
+    ``solvers.gripper_shortcut``'s options; only with ``gripper_guide``): the roadmap's path is shortcut by
+    ``solvers.gripper_plan`` before it is resampled to the guide poses."""
     from .geometry import TorchCuboids, TorchCylinders
     from .robot import franka_fk, frames_to_matrix
-    from .solvers import franka_follow, gripper_roadmap
+    from .solvers import franka_follow, gripper_plan, gripper_roadmap
 
     cub = TorchCuboids(prims["cuboid_centers"], prims["cuboid_dims"], prims["cuboid_quats"])
     cyl = TorchCylinders(prims["cylinder_centers"], prims["cylinder_radii"], prims["cylinder_heights"],
@@ -466,8 +468,12 @@ def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
     extra = {}
     if gripper_guide:
         ends = frames_to_matrix(franka_fk(torch.cat([q_start, q_goal]))[:, gripper])  # (an invalid row's NaN goal: status 2)
-        guide, guide_status = gripper_roadmap(ends[:B].contiguous(), ends[B:].contiguous(), cub, cyl, W=HYBRID_GUIDE_POSES,
-                                              seed=seed, env_offset=env_offset)
+        if shortcut:
+            guide, guide_status = gripper_plan(ends[:B].contiguous(), ends[B:].contiguous(), cub, cyl, W=HYBRID_GUIDE_POSES,
+                                               seed=seed, env_offset=env_offset, shortcut=shortcut)
+        else:
+            guide, guide_status = gripper_roadmap(ends[:B].contiguous(), ends[B:].contiguous(), cub, cyl, W=HYBRID_GUIDE_POSES,
+                                                  seed=seed, env_offset=env_offset)
         extra = {"hybrid_guide_poses": guide, "hybrid_guide_status": guide_status}
     else:
         guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
@@ -478,7 +484,8 @@ def _hybrid_trajectories(prims: Dict[str, torch.Tensor], q_start: torch.Tensor, 
 
 def _hybrid_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor, global_solutions: torch.Tensor,
                                expert_valid: torch.Tensor, point_radius: float, q_goal: Optional[torch.Tensor] = None,
-                               seed: int = 0, env_offset: int = 0, gripper_guide: bool = False) -> Dict[str, torch.Tensor]:
+                               seed: int = 0, env_offset: int = 0, gripper_guide: bool = False,
+                               shortcut=False) -> Dict[str, torch.Tensor]:
     """``hybrid_against="cloud"``: ``_hybrid_trajectories`` with ``solvers.franka_follow_cloud`` (still the stand-in for the
     reference's Geometric Fabrics expert, NOT Lula) following the same eight right_gripper poses of the cloud plan against
     the batch's own scene cloud, at the expert's ``point_radius``: the cloud's distance field steers, ``check_cloud``'s test
@@ -488,10 +495,13 @@ def _hybrid_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor,
     ``gripper_guide`` (``hybrid_guide="gripper_cloud"``): as in ``_hybrid_trajectories``, the guide is planned for the
     free-flying gripper, here by ``solvers.gripper_roadmap_cloud`` against the same scene cloud at the same ``point_radius``
     through that one field, from the right_gripper pose of ``q_start`` to that of ``q_goal``, keyed by the batch's ``seed`` /
-    ``env_offset``.  No fall-back to the global guide: a row without a gripper path hands NaN poses to the follower."""
+    ``env_offset``.  No fall-back to the global guide: a row without a gripper path hands NaN poses to the follower.
+    ``shortcut`` (True or a dict of ``solvers.gripper_shortcut_cloud``'s options; only with ``gripper_guide``): the roadmap's
+    path is shortcut by ``solvers.gripper_plan_cloud``, through the same field, before it is resampled to the guide poses."""
     from .field import DEFAULT_VOXEL, CloudField
     from .robot import franka_fk, frames_to_matrix
-    from .solvers import FOLLOW_DEFAULTS, franka_follow_cloud, gripper_roadmap_cloud, plan_cloud_truncation
+    from .solvers import (FOLLOW_DEFAULTS, franka_follow_cloud, gripper_plan_cloud, gripper_roadmap_cloud,
+                          plan_cloud_truncation)
 
     B = q_start.size(0)
     at = [int(round(i * (EXPERT_LENGTH - 1) / HYBRID_GUIDE_POSES)) for i in range(1, HYBRID_GUIDE_POSES + 1)]
@@ -501,9 +511,14 @@ def _hybrid_trajectories_cloud(scene_cloud: torch.Tensor, q_start: torch.Tensor,
     extra = {}
     if gripper_guide:
         ends = frames_to_matrix(franka_fk(torch.cat([q_start, q_goal]))[:, gripper])  # (an invalid row's NaN goal: status 2)
-        guide, guide_status = gripper_roadmap_cloud(ends[:B].contiguous(), ends[B:].contiguous(), scene_cloud, field=field,
-                                                    point_radius=point_radius, W=HYBRID_GUIDE_POSES, seed=seed,
-                                                    env_offset=env_offset)
+        if shortcut:
+            guide, guide_status = gripper_plan_cloud(ends[:B].contiguous(), ends[B:].contiguous(), scene_cloud, field=field,
+                                                     point_radius=point_radius, W=HYBRID_GUIDE_POSES, seed=seed,
+                                                     env_offset=env_offset, shortcut=shortcut)
+        else:
+            guide, guide_status = gripper_roadmap_cloud(ends[:B].contiguous(), ends[B:].contiguous(), scene_cloud, field=field,
+                                                        point_radius=point_radius, W=HYBRID_GUIDE_POSES, seed=seed,
+                                                        env_offset=env_offset)
         extra = {"hybrid_guide_poses": guide, "hybrid_guide_status": guide_status}
     else:
         guide = frames_to_matrix(franka_fk(global_solutions[:, at].reshape(-1, 7))[:, gripper]).reshape(B, len(at), 4, 4)
@@ -543,7 +558,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        max_redraws: int = 4, expert: bool = False, expert_from: str = "primitives",
                        expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False,
                        hybrid_guide: str = "global", hybrid_against: str = "primitives",
-                       problems: str = "uniform", expert_shortcut: bool = False) -> Dict[str, torch.Tensor]:
+                       problems: str = "uniform", expert_shortcut: bool = False,
+                       hybrid_shortcut=False) -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -602,7 +618,12 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     same stage against the scene cloud: ``solvers.gripper_roadmap_cloud`` at ``expert_point_radius``, through the one field
     the cloud follower reads, with the same two extra keys; its verdicts come from the field, which approximates, so the
     exact judge stays ``check_cloud``'s test on the follower's trajectory.  "gripper" with ``hybrid_against="cloud"`` is
-    refused.
+    refused.  ``hybrid_shortcut`` (default off, which leaves every key and every bit as it was; True or a dict of
+    ``solvers.gripper_shortcut``'s options; only with ``hybrid_guide`` "gripper" or "gripper_cloud"): the gripper roadmap's
+    path is shortcut on the device (``solvers.gripper_plan`` / ``gripper_plan_cloud``, the cloud form through the same one
+    field) before it is resampled, and ``hybrid_guide_poses`` are the shortcut's; ``hybrid_guide_status`` stays the
+    roadmap's.  A shorter guide hugs the obstacle: whether the follower does better with it is measured in
+    profiles/gripper_shortcut_timing.md, not promised.
 
     ``problems`` (default "uniform", which leaves every key and every bit as it was: start and goal are the forward
     kinematics of uniform draws over the joint limits, poses anywhere in the air).  "task" (needs ``collision_free``): the
@@ -647,6 +668,9 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
         raise ValueError(f"expert_from must be 'primitives', 'cloud', 'roadmap' or 'cloud_roadmap', got {expert_from!r}")
     if expert_shortcut and expert_from not in ("roadmap", "cloud_roadmap"):
         raise ValueError("expert_shortcut=True needs expert_from='roadmap' or 'cloud_roadmap': there is no roadmap path to shortcut")
+    if hybrid_shortcut and not (hybrid and hybrid_guide in ("gripper", "gripper_cloud")):
+        raise ValueError("hybrid_shortcut needs hybrid=True and hybrid_guide='gripper' or 'gripper_cloud': there is no gripper "
+                         "roadmap path to shortcut")
     if problems not in ("uniform", "task"):
         raise ValueError(f"problems must be 'uniform' or 'task', got {problems!r}")
     task = problems == "task"
@@ -705,10 +729,11 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if hybrid and hybrid_against == "cloud":
         out.update(_hybrid_trajectories_cloud(xyz[:, NUM_ROBOT_POINTS:NUM_ROBOT_POINTS + NUM_OBSTACLE_POINTS, :3], q,
                                               out["global_solutions"], out["expert_valid"], expert_point_radius, q_goal, seed,
-                                              env_offset, gripper_guide=hybrid_guide == "gripper_cloud"))
+                                              env_offset, gripper_guide=hybrid_guide == "gripper_cloud",
+                                              shortcut=hybrid_shortcut))
     elif hybrid:
         out.update(_hybrid_trajectories(out, q, out["global_solutions"], out["expert_valid"], q_goal, seed, env_offset,
-                                        gripper_guide=hybrid_guide == "gripper"))
+                                        gripper_guide=hybrid_guide == "gripper", shortcut=hybrid_shortcut))
     out.update(q=q, q_norm=(q - lim[:, 0]) / (lim[:, 1] - lim[:, 0]) * 2 - 1, xyz=xyz, target_pose=target_pose,
                target_position=target_pose[:, :3, 3].contiguous(), robot_subset=subset, env_offset=int(env_offset))
     return out

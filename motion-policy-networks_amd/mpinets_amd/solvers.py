@@ -1,6 +1,7 @@
 """The device solvers for the Franka: inverse kinematics, trajectory optimisation, the roadmap and the shortcutting of its
 path, the gripper's SE(3) roadmap and the path follower, against primitives or a point cloud (csrc/ik.hip, plan.hip,
-roadmap.hip, gripper_roadmap.hip, follow.hip, cloud_field.hip, roadmap_cloud.hip, follow_cloud.hip; shortcut_kernel.inc).  Each wrapper is its entry's argument list: the inputs
+roadmap.hip, gripper_roadmap.hip, gripper_shortcut.hip, follow.hip, cloud_field.hip, roadmap_cloud.hip, follow_cloud.hip;
+shortcut_kernel.inc).  Each wrapper is its entry's argument list: the inputs
 (``_inputs``), the blocks of ``_operands`` (sphere table and primitives, or cloud; options / seed / env_offset) and the
 outputs, in the header's order.  ``robot`` re-exports every name here."""
 from __future__ import annotations
@@ -46,6 +47,10 @@ SHORTCUT_DEFAULTS = dict(points=64, passes=2, fanout=4, resolution=0.05, smooth_
 # status and ``edge_state`` values are the roadmap's (``ROADMAP_FOUND`` ...)
 GRIPPER_ROADMAP_DEFAULTS = dict(nodes=64, resolution=0.01, rot_weight=0.12, orient_spread=0.5, connect_radius=float("inf"),
                                 max_rounds=256, check_margin=1e-4, clearance=0.0, check_self=True)
+# MPX_SHORTCUT_DEFAULT_* and the gripper roadmap's values (include/mpinets_hip.h; profiles/gripper_shortcut_timing.md); the
+# status values are the shortcut's (``SHORTCUT_RETURNED``, ``SHORTCUT_BAD_ROW``)
+GRIPPER_SHORTCUT_DEFAULTS = dict(points=64, passes=2, fanout=4, resolution=0.01, rot_weight=0.12, check_margin=1e-4,
+                                 clearance=0.0, check_self=True)
 GRIPPER_ROADMAP_BOUNDS_PAD = 0.3  # [m] ``bounds=None``: the box hull of the two positions, grown by this much per side
 
 TASK_PADDING, TASK_SURFACE, TASK_VOLUME = 0, 1, 2  # ``support_kind`` of ``task_candidates``
@@ -96,6 +101,12 @@ def _gripper_roadmap_options(who: str, options: dict):
     return merge_options(who, _lib.GripperRoadmapOptions, GRIPPER_ROADMAP_DEFAULTS, options)
 
 
+def _gripper_shortcut_options(who: str, options: dict):
+    """Keyword options of the gripper's shortcut over ``GRIPPER_SHORTCUT_DEFAULTS`` -> the ``_lib.GripperShortcutOptions`` and
+    the merged dict."""
+    return merge_options(who, _lib.GripperShortcutOptions, GRIPPER_SHORTCUT_DEFAULTS, options)
+
+
 def _follow_options(who: str, options: dict):
     """Keyword options of the follower over ``FOLLOW_DEFAULTS`` -> the ``_lib.FollowOptions`` and the merged dict; ``lambda``
     is accepted for ``lambda_``."""
@@ -140,24 +151,33 @@ def _roadmap_outputs(B: int, rows0: tuple, V: int, dev: torch.device, return_gra
             torch.empty(B, dtype=torch.int32, device=dev) if return_graph else None)
 
 
-def _shortcut_call(who: str, points: torch.Tensor, count: torch.Tensor, T: int, return_trace: bool, options: dict, others=()):
-    """What both shortcut wrappers start from and end with: the polylines ``[B,Pin,7]`` and ``count`` ``[B]`` on the current
+def _shortcut_call(who: str, points: torch.Tensor, count: torch.Tensor, T: int, return_trace: bool, options: dict, others=(),
+                   W: Optional[int] = None, goal_pose: Optional[torch.Tensor] = None):
+    """What the shortcut wrappers start from and end with: the polylines ``[B,Pin,7]`` and ``count`` ``[B]`` on the current
     GPU, the options, the outputs in the entry's order -> ``run(entry, *environment)`` that calls ``entry`` and returns
-    ``traj, status, points_out, count_out, length`` (with ``return_trace`` also ``chords, configs``), and the merged options."""
-    _lib.require_cuda(points, count, *others)
+    ``traj, status, points_out, count_out, length`` (with ``return_trace`` also ``chords, configs``), and the merged options.
+    With ``W`` the gripper's form: ``mpx_gripper_shortcut_options``, ``poses`` [B,W,4,4] in the place of ``traj``, and ``W``
+    and ``goal_pose`` ([B,4,4] or None) where the joint-space entries take ``T``."""
+    _lib.require_cuda(points, count, goal_pose, *others)
     assert points.ndim == 3 and points.size(2) == 7 and count.shape == (points.size(0),)
     B, Pin, dev = points.size(0), points.size(1), points.device
     pts, cn = _lib.f32c(points), _lib.i32c(count)
-    copt, o = _shortcut_options(who, options)
+    copt, o = (_shortcut_options if W is None else _gripper_shortcut_options)(who, options)
     P = max(int(o["points"]), 0)
     i32 = dict(dtype=torch.int32, device=dev)
-    out = (torch.empty((B, T, 7), dtype=torch.float32, device=dev), torch.empty(B, **i32),
+    if W is None:
+        rows0, head = (T, 7), (int(T),)
+    else:
+        assert goal_pose is None or tuple(goal_pose.shape) == (B, 4, 4)
+        gp = None if goal_pose is None else _lib.f32c(goal_pose)
+        rows0, head = (max(int(W), 0), 4, 4), (int(W), _lib.ptr(gp))
+    out = (torch.empty((B,) + rows0, dtype=torch.float32, device=dev), torch.empty(B, **i32),
            torch.empty((B, P, 7), dtype=torch.float32, device=dev), torch.empty(B, **i32),
            torch.empty((B, 2), dtype=torch.float32, device=dev), torch.empty(B, **i32) if return_trace else None,
            torch.empty(B, **i32) if return_trace else None)
 
     def run(entry: str, finger: float, *environment):
-        _lib.call(entry, pts.data_ptr(), cn.data_ptr(), B, Pin, int(T), float(finger), *environment, ctypes.byref(copt),
+        _lib.call(entry, pts.data_ptr(), cn.data_ptr(), B, Pin, *head, float(finger), *environment, ctypes.byref(copt),
                   *_ptrs(out))
         return out if return_trace else out[:5]
 
@@ -311,7 +331,7 @@ def franka_shortcut(polylines: torch.Tensor, count: torch.Tensor, cuboids=None, 
 def _path_vertices(nodes: torch.Tensor, path: torch.Tensor, hops: torch.Tensor):
     """``nodes[path]`` of a roadmap's graph -> the polylines [B,V,7] (rows behind a path: node 0) and their vertex counts
     (0 where the roadmap found nothing: a bad row for the shortcut, whose NaN ``traj`` is the planner's NaN seed)."""
-    idx = path.clamp(min=0).long()[:, :, None].expand(-1, -1, 7)
+    idx = path.clamp(0, nodes.size(1) - 1).long()[:, :, None].expand(-1, -1, 7)
     return torch.gather(nodes, 1, idx), torch.where(hops > 0, hops + 1, torch.zeros_like(hops))
 
 
@@ -406,6 +426,71 @@ def gripper_roadmap(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=N
     _lib.call("mpx_gripper_roadmap", sp.data_ptr(), gp.data_ptr(), B, W, box.data_ptr(), float(finger), *prims,
               *options_tail(copt, seed, env_offset), *_ptrs(out))
     return out if return_graph else out[:2]
+
+
+def gripper_shortcut(polylines: torch.Tensor, count: torch.Tensor, cuboids=None, cylinders=None, W: int = 8,
+                     goal_pose: Optional[torch.Tensor] = None, return_trace: bool = False, with_base_link: bool = False,
+                     finger: float = ft.FINGER_OPENING, **options):
+    """Shortcut one SE(3) polyline of the free-flying gripper per problem on the GPU (csrc/gripper_shortcut.hip):
+    ``franka_shortcut``'s passes, densification and greedy ``fanout``-ary walk over ``gripper_roadmap``'s metric, nlerp edge
+    pose and validity, then that roadmap's resampling to ``W`` guide poses.  Part of the same stand-in for the reference's
+    end-effector planner, not a port of it.  Deterministic: no seed.
+
+    :param polylines: [B,Pin,7] float32 (position, unit quaternion x y z w; the sign of a quaternion is free), ``count`` int
+        [B]: the polyline of a row is its first ``count`` vertices (2 <= count <= Pin <= 256), e.g. ``nodes[path]`` of
+        ``gripper_roadmap(..., return_graph=True)``.  The caller vouches for its segments: they are not tested
+    :param cuboids, cylinders, W: as for ``gripper_roadmap``
+    :param goal_pose: [B,4,4] whose rows 0-2 become the last guide pose bit for bit, or None: the last vertex's own frame
+    :param options: the fields of ``mpx_gripper_shortcut_options``, see ``GRIPPER_SHORTCUT_DEFAULTS``
+    :returns: ``poses`` [B,W,4,4] (NaN rows where ``status`` != 0), ``status`` int32 [B] (0 a polyline is returned, 2 a bad
+        row: count < 2, count > Pin, a non-finite vertex or a quaternion that is not of unit length), ``points_out`` [B,P,7]
+        (NaN rows beyond ``count_out``), ``count_out`` int32 [B] and ``length`` [B,2] (metric length before, after); with
+        ``return_trace`` also ``chords`` and ``configs`` int32 [B], the chords and interior poses tested."""
+    run, o, B, dev = _shortcut_call("gripper_shortcut", polylines, count, 0, return_trace, options, (), W, goal_pose)
+    prims, held = sphere_primitive_args(cuboids, cylinders, B, dev, with_base_link)
+    return run("mpx_gripper_shortcut", finger, *prims)
+
+
+def _gripper_plan_shortcut(shortcut, ropt: dict, V: int) -> Optional[dict]:
+    """``shortcut`` of ``gripper_plan`` / ``gripper_plan_cloud`` -> None (off) or the shortcut's options: what it shares with
+    the roadmap defaults to the roadmap's values, ``points`` to max(64, nodes)."""
+    sopt = _shortcut_arg(shortcut)
+    if sopt is None:
+        return None
+    inherited = {k: ropt[k] for k in ("resolution", "rot_weight", "check_margin", "clearance", "check_self")}
+    return {"points": max(GRIPPER_SHORTCUT_DEFAULTS["points"], V), **inherited, **sopt}
+
+
+def _gripper_plan_result(poses, status, short, return_length: bool):
+    """The roadmap's ``poses, status`` with the shortcut's poses in their place (``short``: its outputs, or None)."""
+    if short is None:
+        length = None
+    else:
+        poses, length = short[0], short[4]  # (a row without a path is a bad row of the shortcut: NaN)
+    return (poses, status, length) if return_length else (poses, status)
+
+
+def gripper_plan(start_pose: torch.Tensor, goal_pose: torch.Tensor, cuboids=None, cylinders=None, W: int = 8, bounds=None,
+                 seed: int = 0, env_offset: int = 0, with_base_link: bool = False, finger: float = ft.FINGER_OPENING,
+                 return_length: bool = False, roadmap: Optional[dict] = None, shortcut=True):
+    """``gripper_roadmap`` with its graph, then ``gripper_shortcut`` over ``nodes[path]`` with the roadmap's ``goal_pose``:
+    the guide poses of the shortened path.  As ``franka_plan_global`` is to ``franka_roadmap``.
+
+    :param roadmap: options of ``gripper_roadmap`` (``GRIPPER_ROADMAP_DEFAULTS``)
+    :param shortcut: True, or a dict of ``gripper_shortcut``'s options (``resolution``, ``rot_weight``, ``check_margin``,
+        ``clearance`` and ``check_self`` default to the roadmap's, ``points`` to max(64, nodes)); None: the roadmap's poses
+        bit for bit
+    :returns: ``poses`` [B,W,4,4] and ``status`` int32 [B], the ROADMAP's (rows without a path are NaN); with
+        ``return_length`` also ``length`` [B,2], the shortcut's (None without it)."""
+    _, ropt = _gripper_roadmap_options("gripper_plan", dict(roadmap or {}))
+    sopt = _gripper_plan_shortcut(shortcut, ropt, int(ropt["nodes"]))
+    poses, status, *graph = gripper_roadmap(start_pose, goal_pose, cuboids, cylinders, W, bounds, seed, env_offset,
+                                            sopt is not None, with_base_link, finger, **(roadmap or {}))
+    short = None
+    if sopt is not None:
+        pts, cnt = _path_vertices(graph[2], graph[0], graph[1])
+        short = gripper_shortcut(pts, cnt, cuboids, cylinders, W, goal_pose, False, with_base_link, finger, **sopt)
+    return _gripper_plan_result(poses, status, short, return_length)
 
 
 def task_candidates(support_boxes: torch.Tensor, support_kind: torch.Tensor, cuboids=None, cylinders=None, C: int = 8,
@@ -760,6 +845,61 @@ def gripper_roadmap_cloud(start_pose: torch.Tensor, goal_pose: torch.Tensor, clo
               None if field is None else ctypes.byref(field.grid), float(point_radius), float(field_slack),
               *options_tail(copt, seed, env_offset), *_ptrs(out))
     return out if return_graph else out[:2]
+
+
+def gripper_shortcut_cloud(polylines: torch.Tensor, count: torch.Tensor, cloud: Optional[torch.Tensor],
+                           counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0,
+                           field_slack: float = 0.0, W: int = 8, goal_pose: Optional[torch.Tensor] = None,
+                           return_trace: bool = False, with_base_link: bool = False, finger: float = ft.FINGER_OPENING,
+                           **options):
+    """``gripper_shortcut`` against one POINT CLOUD per environment (csrc/gripper_shortcut_cloud.hip): the same passes,
+    densification, greedy walk, outputs and guide poses, with ``gripper_roadmap_cloud``'s validity test -- the cloud's
+    truncated distance field, ``point_radius``, ``field_slack``, "outside the grid or saturated: free".  The field
+    approximates the distance, so a guide pose may graze the cloud: the exact judge is ``check_cloud`` on what the follower
+    produces.
+
+    :param polylines, count, W, goal_pose: as for ``gripper_shortcut``
+    :param cloud, counts, field, point_radius, field_slack: as for ``gripper_roadmap_cloud`` (None and None: no environment)
+    :param options: the fields of ``mpx_gripper_shortcut_options``, see ``GRIPPER_SHORTCUT_DEFAULTS``
+    :returns: what ``gripper_shortcut`` returns."""
+    who = "gripper_shortcut_cloud"
+    run, o, B, dev = _shortcut_call(who, polylines, count, 0, return_trace, options, (cloud, counts), W, goal_pose)
+    if cloud is not None or field is not None:
+        cn = None if cloud is None else cloud_args(who, cloud, counts, B, point_radius)[1]
+        field = _plan_cloud_field(who, cloud, cn, field, B, point_radius, o["clearance"], FOLLOW_DEFAULTS["epsilon"],
+                                  with_base_link)
+    sc, sr, sl = sphere_table(dev, with_base_link)
+    return run("mpx_gripper_shortcut_cloud", finger, sc.data_ptr(), sr.data_ptr(), sl.data_ptr(), int(sc.size(0)),
+               None if field is None else field.values.data_ptr(), None if field is None else ctypes.byref(field.grid),
+               float(point_radius), float(field_slack))
+
+
+def gripper_plan_cloud(start_pose: torch.Tensor, goal_pose: torch.Tensor, cloud: Optional[torch.Tensor],
+                       counts: Optional[torch.Tensor] = None, field=None, point_radius: float = 0.0, field_slack: float = 0.0,
+                       W: int = 8, bounds=None, seed: int = 0, env_offset: int = 0, with_base_link: bool = False,
+                       finger: float = ft.FINGER_OPENING, return_length: bool = False, roadmap: Optional[dict] = None,
+                       shortcut=True):
+    """``gripper_roadmap_cloud`` with its graph, then ``gripper_shortcut_cloud`` over ``nodes[path]`` with the roadmap's
+    ``goal_pose``, both reading ONE field of the cloud (built here when ``field`` is None), at the same ``point_radius`` and
+    ``field_slack``.  ``roadmap``, ``shortcut`` and what is returned: as for ``gripper_plan``."""
+    who = "gripper_plan_cloud"
+    _, ropt = _gripper_roadmap_options(who, dict(roadmap or {}))
+    sopt = _gripper_plan_shortcut(shortcut, ropt, int(ropt["nodes"]))
+    if cloud is not None and field is None and sopt is not None:  # (one field for both; the roadmap alone builds its own)
+        B = start_pose.size(0)
+        _lib.require_cuda(start_pose, cloud, counts)
+        cn = cloud_args(who, cloud, counts, B, point_radius)[1]
+        field = _plan_cloud_field(who, cloud, cn, None, B, point_radius, max(ropt["clearance"], sopt["clearance"]),
+                                  FOLLOW_DEFAULTS["epsilon"], with_base_link)
+    poses, status, *graph = gripper_roadmap_cloud(start_pose, goal_pose, cloud, counts, field, point_radius, field_slack, W,
+                                                  bounds, seed, env_offset, sopt is not None, with_base_link, finger,
+                                                  **(roadmap or {}))
+    short = None
+    if sopt is not None:
+        pts, cnt = _path_vertices(graph[2], graph[0], graph[1])
+        short = gripper_shortcut_cloud(pts, cnt, cloud, counts, field, point_radius, field_slack, W, goal_pose, False,
+                                       with_base_link, finger, **sopt)
+    return _gripper_plan_result(poses, status, short, return_length)
 
 
 def franka_plan_global_cloud(q_start: torch.Tensor, q_goal: torch.Tensor, cloud: torch.Tensor,
