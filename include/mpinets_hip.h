@@ -29,8 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding):
-                          mpx_gripper_shortcut, mpx_gripper_shortcut_cloud, struct mpx_gripper_shortcut_options;
+int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding): mpx_scene_generate;
+                          341 (unchanged, likewise): mpx_gripper_shortcut, mpx_gripper_shortcut_cloud, struct mpx_gripper_shortcut_options;
                           341 (unchanged, likewise): mpx_franka_shortcut, mpx_franka_shortcut_cloud, struct mpx_shortcut_options; 341 (unchanged, likewise):
                           mpx_task_candidates, struct mpx_task_candidates_options; 341 (unchanged, likewise):
                           the form query mpx_linear_form; 341 (unchanged, likewise):
@@ -646,6 +646,80 @@ int mpx_task_candidates(const float *support_boxes, const int32_t *support_kind,
                         const float *cyl_radii, const float *cyl_heights, int M2,
                         const mpx_task_candidates_options *options, uint64_t seed, int64_t env_offset, float *poses,
                         int32_t *draw, int32_t *support, int32_t *count, mpx_stream_t stream);
+
+/* SCENES drawn on the device: the distributions of the host generators (mpinets_amd/scenes.py: _tabletop, _cubby, _dresser,
+ * themselves restatements of the reference's tabletop_environment.py:215-324, cubby_environment.py:62-74 and
+ * dresser_environment.py:198-222) with the supports make_task_scenes reads off them, every scene a function of
+ * (seed, scene id, kind, M1, M2, S) alone: a shard generates its own rows and nothing else.  A second SOURCE of scenes, not
+ * a port of the host's stream: numpy's PCG64 is sequential, these draws are counter-keyed, so the same seed gives other
+ * scenes of the same distribution.  One wave per scene, a lane per primitive slot, four scenes per workgroup.
+ *   scene_kind int32 [B]: 0 tabletop, 1 cubby, 2 dresser; any other code: an EMPTY scene (all padding, no supports).
+ *   scene_ids int64 [B] or NULL: the id of scene b (its low 32 bits are used); NULL: id = scene_offset + b.
+ *   3 <= M1 <= 64, 0 <= M2 <= 64.  support_boxes and support_kind both NULL with S == 0 (make_scenes' form), or both given
+ *   with 1 <= S <= MPX_TASK_MAX_SUPPORTS.
+ *   Outputs, make_task_scenes' arrays: cuboid_centers [B,M1,3], cuboid_dims [B,M1,3], cuboid_quats [B,M1,4] (w x y z),
+ *   cylinder_centers [B,M2,3], cylinder_radii [B,M2,1], cylinder_heights [B,M2,1], cylinder_quats [B,M2,4]; support_boxes
+ *   [B,S,12] = centre (3), dims (3), quaternion w x y z (4), approach, weight; support_kind int32 [B,S] (0 padding,
+ *   1 surface, 2 volume: mpx_task_candidates' operands).  EVERY element is written: live rows form a prefix of each array,
+ *   the rows behind them are PADDING = zero centre, zero dims / radius / height, quaternion (1, 0, 0, 0), and for a
+ *   support approach 0, weight 0, kind 0.  Every cylinder quaternion is (1, 0, 0, 0); every quaternion of a live row is
+ *   (qw, 0, 0, qz): the scenes are rotated about the world z axis only.
+ *   Draws.  word j of (item, block) = word j of Philox4x32-10(counter = {item, scene id, stream 19, block}, key = seed);
+ *   u(item, j) = u01 of word j of block 0 for j = 0..3 and of word j - 4 of block 1 for j = 4..7 (top 24 bits / 2^24).
+ *   Item 0 carries the scene's parameters, item k + 1 object or plate k.  A threshold compares u with the float32 constant
+ *   written; an integer draw from word x is  (((x >> 8) * n) >> 24)  in integer arithmetic.  All arithmetic is float32, each
+ *   operation rounded on its own in the order written, fma(a, b, c) = a b + c rounded once only where it is written;
+ *   decimal constants are the nearest float32; pi/2 = 1.57079632679489661923f, pi/18 = 0.17453292519943295f,
+ *   pi/9 = 0.3490658503988659f, pi/6 = 0.52359877559829887f, 2 pi/3 = 2.0943951023931953f.  sin and cos are float32
+ *   (within 2e-7).  The quaternion of a yaw is q(yaw) = (cos(0.5f yaw), 0, 0, sin(0.5f yaw)); with c = cos(yaw), s = sin(yaw)
+ *   a local point (lx, ly, lz) lies at  W(l) = ((c lx - s ly) + ox, s lx + c ly, lz + oz)  for the kind's origin (ox, oz).
+ *   TABLETOP (kind 0), with u_j = u(0, j):
+ *     h = 0 if u_0 < 0.35f else u_1 0.4f;  x0 = fma(u_2, 0.1f, 0.275f);  x1 = fma(u_3, 0.1f, 1.275f);
+ *     w = fma(u_4, 0.15f, 1.5f);  a side table stands iff u_5 < 0.5f, at side = -1 if u_6 < 0.5f else +1;
+ *     K = 3 + integer draw (n = 12) from word 3 of block 1: 3 .. 14 objects.
+ *     Cuboid 0, the front table: centre ((x0 + x1) 0.5f, 0, h - 0.025f), dims (x1 - x0, w, 0.05f).  Cuboid 1, with a side
+ *     table: centre (0, side fma(w, 0.25f, 0.45f), h - 0.025f), dims (0.9f, w 0.5f, 0.05f).  The next cuboid, the mount
+ *     table: centre (-0.35f, 0, -0.025f), dims (0.6f, 0.6f, 0.05f).  T = 2 or 3 tables, identity quaternions.
+ *     Object k = 0 .. K-1, with v_j = u(k + 1, j):  lo = x0 + 0.1f, px = fma(v_0, (x1 - 0.1f) - lo, lo);
+ *     hw = w 0.5f - 0.1f, py = fma(v_1, hw + hw, -hw);  it DREW a cylinder iff v_2 < 0.3f (v_3 is not used).
+ *     Slots, the host loop's rule without the loop: object k IS a cylinder when it drew one and fewer than M2 objects before
+ *     it did; its row is the number of those.  Otherwise it is a cuboid candidate (an overflowing cylinder draw included),
+ *     kept when r = the number of cuboid candidates before it satisfies T + r < M1, in row T + r; otherwise dropped.
+ *     Cylinder: radius fma(v_4, 0.1f, 0.05f), height hh = fma(v_5, 0.3f, 0.05f), centre (px, py, fma(hh, 0.5f, h)).
+ *     Cuboid: dims (fma(v_4, 0.1f, 0.05f), fma(v_5, 0.1f, 0.05f), dz = fma(v_6, 0.3f, 0.05f)), centre (px, py,
+ *     fma(dz, 0.5f, h)), quaternion q(v_7 pi/2).
+ *     Supports: row 0 the front table, row 1 the side table where it stands (the first S of them): SURFACES, the cuboid's
+ *     centre, dims and quaternion copied, approach 0, weight = dims_x dims_y.  The mount table is not a support.
+ *   CUBBY (kind 1), with u_j = u(0, j):  t = fma(u_0, 0.02f, 0.01f), W = fma(u_1, 0.4f, 0.7f), H = fma(u_2, 0.4f, 0.5f),
+ *     D = fma(u_3, 0.15f, 0.2f), ox = fma(u_4, 0.25f, 0.55f), oz = fma(u_5, 0.2f, 0.1f), yaw = fma(u_6, pi/9, -pi/18);
+ *     with hH = H 0.5f, hW = W 0.5f, ht = t 0.5f the first min(7, M1) of the plates (local centre; dims), all q(yaw), at W(l):
+ *       0 (0, 0, 0; D, W, t)   1 (0, 0, H; D, W, t)   2 (0, 0, hH; D, W, t)   3 (0, -hW, hH; D, t, H)   4 (0, hW, hH; D, t, H)
+ *       5 (0, 0, hH; D, t, H)   6 (D 0.5f, 0, hH; t, W, H).
+ *     Supports: the first min(4, S) pockets p = 2 zi + yi, VOLUMES:  (z0, z1) = (ht, hH - ht) for zi = 0, (hH + ht, H - ht)
+ *     for zi = 1;  (y0, y1) = (-hW + ht, -ht) for yi = 0, (ht, hW - ht) for yi = 1;  centre W(-(t 0.25f), (y0 + y1) 0.5f,
+ *     (z0 + z1) 0.5f), dims (D - ht, y1 - y0, z1 - z0), q(yaw), approach 0, weight 1.
+ *   DRESSER (kind 2), with u_j = u(0, j):  W = fma(u_0, 0.4f, 0.8f), D = fma(u_1, 0.2f, 0.2f), H = fma(u_2, 0.3f, 0.55f),
+ *     ox = fma(u_3, 0.2f, 0.55f), oz = 0, yaw = fma(u_4, 2 pi/3, pi/6);  n = min(M1, 12 + integer draw (n = 29) from word 1
+ *     of block 1): 12 .. 40 plates before the min;  rows = the smallest integer r with r r >= n;  wc = W / (float)rows,
+ *     hc = H / (float)rows.  Plate i = 0 .. n-1 in cell (ri, ci) = (i / rows, i mod rows), depth jitter
+ *     j = fma(u(i + 1, 0), 0.04f, -0.02f):  centre W(fma((float)ci + 0.5f, wc, -(W 0.5f)), j, ((float)ri + 0.5f) hc), dims
+ *     (wc 0.95f, D, hc 0.2f), q(yaw).  Supports: one VOLUME per plate, the first min(S, n): the plate's centre with local z
+ *     ((float)ri + 0.8f) hc, dims (wc 0.95f, D, hc 0.4f), q(yaw), weight 1, approach = yaw - pi/2.  (The host picks the sense
+ *     of the depth axis with a positive world-x component, yaw + pi/2 where sin(yaw) < 0; the drawn yaw lies in
+ *     (pi/6, 5 pi/6), its sine is positive, so the approach is yaw - pi/2 ALWAYS and the kernel does not test it.)
+ *   An output is at most eight rounded operations from its uniforms plus one sine or cosine on a lever arm below 1 m:
+ *   within about 1.2e-6 of exact arithmetic at the largest coordinate, 2 m.  The discrete decisions (thresholds, K, n, rows,
+ *   slots) are exact.
+ *   Refused before any launch: M1 outside 3 .. 64, M2 outside 0 .. 64, one support pointer without the other, S != 0 without
+ *   them or outside 1 .. MPX_TASK_MAX_SUPPORTS with them, scene_offset < 0, scene_offset + B > 2^32 (checked with scene_ids
+ *   too), B < 0; then B == 0 launches nothing; then a NULL scene_kind or primitive pointer (M2 == 0 excuses the four cylinder
+ *   pointers), or a cuboid_quats, cylinder_quats or support_boxes that is not 16-byte aligned (their rows are stored as
+ *   float4).  ceil(B / 4) workgroups of 256 threads on grid.x; no LDS (the slot compaction is two wave ballots and
+ *   popcounts), no scratch, no allocation, no global atomics; enqueued on `stream` (capturable).                        */
+int mpx_scene_generate(const int32_t *scene_kind, const int64_t *scene_ids, int B, int M1, int M2, int S, uint64_t seed,
+                       int64_t scene_offset, float *cuboid_centers, float *cuboid_dims, float *cuboid_quats,
+                       float *cylinder_centers, float *cylinder_radii, float *cylinder_heights, float *cylinder_quats,
+                       float *support_boxes, int32_t *support_kind, mpx_stream_t stream);
 
 /* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
  * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at

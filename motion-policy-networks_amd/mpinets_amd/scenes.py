@@ -181,6 +181,48 @@ def make_task_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M
     return _scene_arrays(B, seed, kinds, M1, M2, S)
 
 
+SCENE_KIND_CODES = {"tabletop": 0, "cubby": 1, "dresser": 2}  # ``mpx_scene_generate``'s ``scene_kind``
+
+
+def make_scenes_device(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16, S: Optional[int] = None,
+                       device="cuda:0", env_offset: int = 0, scene_ids: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The scenes of ``make_scenes`` (``S`` None) or ``make_task_scenes`` (``S`` >= 1) drawn ON THE DEVICE
+    (csrc/scene_gen.hip, ``mpx_scene_generate``): the same keys, shapes, dtypes, padding and DISTRIBUTIONS, as tensors on
+    ``device``, every scene a function of ``(seed, scene id, kind, M1, M2, S)`` alone -- Philox stream 19 keyed by the scene
+    id -- where the host generators walk one sequential rng.  A second source beside the host's, not a port of its stream:
+    the same seed gives other scenes of the same distribution.  Scene b has id ``env_offset + b``, or ``scene_ids[b]``
+    (int64 [B], any order, repeats allowed: the rows of a shard, the tiles of a ``scene_pool``); the kind of scene id g is
+    ``kinds[g % len(kinds)]``, the host's rule.  3 <= M1 <= 64, 0 <= M2 <= 64, S <= 64.  Every element is written by the
+    kernel; nothing is generated for a row that is not asked for."""
+    from . import _lib
+
+    dev = torch.device(device)
+    codes = torch.tensor([SCENE_KIND_CODES[k] for k in kinds], dtype=torch.int32)
+    if scene_ids is None:
+        ids = None
+        kind = codes[(int(env_offset) + torch.arange(B, dtype=torch.int64)) % len(kinds)].to(dev)
+    else:
+        ids = scene_ids.to(device=dev, dtype=torch.int64).contiguous()
+        if ids.shape != (B,):
+            raise _lib.MpxError(f"make_scenes_device: scene_ids must be [B] = [{B}], got {tuple(ids.shape)}")
+        kind = codes.to(dev)[ids % len(kinds)]
+    _lib.require_cuda(kind, ids)
+
+    def empty(*shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    out = {"cuboid_centers": empty(B, M1, 3), "cuboid_dims": empty(B, M1, 3), "cuboid_quats": empty(B, M1, 4),
+           "cylinder_centers": empty(B, M2, 3), "cylinder_radii": empty(B, M2, 1), "cylinder_heights": empty(B, M2, 1),
+           "cylinder_quats": empty(B, M2, 4)}
+    if S is not None:
+        out.update(support_boxes=empty(B, S, 12), support_kind=empty(B, S, dtype=torch.int32))
+    _lib.call("mpx_scene_generate", _lib.ptr(kind), _lib.ptr(ids), B, M1, M2, 0 if S is None else S, int(seed) & (2 ** 64 - 1),
+              int(env_offset), *(_lib.ptr(out[k]) for k in ("cuboid_centers", "cuboid_dims", "cuboid_quats", "cylinder_centers",
+                                                            "cylinder_radii", "cylinder_heights", "cylinder_quats")),
+              _lib.ptr(out.get("support_boxes")), _lib.ptr(out.get("support_kind")))
+    return out
+
+
 def sample_scene_clouds_host(scn: Dict[str, np.ndarray], num_points: int, seed: int = 0) -> np.ndarray:
     """Vectorised area-proportional surface sampling of every environment's primitives (NumPy).
 
@@ -559,7 +601,7 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                        expert_point_radius: float = EXPERT_CLOUD_POINT_RADIUS, hybrid: bool = False,
                        hybrid_guide: str = "global", hybrid_against: str = "primitives",
                        problems: str = "uniform", expert_shortcut: bool = False,
-                       hybrid_shortcut=False) -> Dict[str, torch.Tensor]:
+                       hybrid_shortcut=False, scene_source: str = "host") -> Dict[str, torch.Tensor]:
     """A batch of planning problems on ``device``: primitives, start configuration, target pose and
     the ``[B, 2048+4096+128, 4]`` slab (robot | scene | target rows, label column 0/1/2 --
     ``mpinets/data_loader.py:261-278``).  ``scene_pool`` bounds the number of distinct scenes
@@ -640,7 +682,16 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     live volume supports; NaN rows elsewhere): what the reference's inference problems carry for ``check_final_region``
     (``metrics.BatchedEvaluator``).  Invalid rows keep their uniform draws as start and target pose, a NaN ``q_goal`` and NaN /
     -1 in the new keys.  The reference's neutral starts (``random_neutral``) need robofin's constants, which are not in the
-    tree: out of scope."""
+    tree: out of scope.
+
+    ``scene_source`` (default "host", which leaves every key and every bit as it was: ``make_scenes`` / ``make_task_scenes``,
+    one sequential numpy rng, which has to generate every scene up to the batch's last one).  "device": the scenes come from
+    ``make_scenes_device`` (csrc/scene_gen.hip) -- the same distributions, supports included, but OTHER scenes than the host
+    draws from the same seed: numpy's stream cannot be reproduced by a counter rng.  The scene of global row ``gid`` has id
+    ``gid % nscene`` (``scene_pool`` keeps its meaning; without it every row has its own scene) and depends on
+    ``(seed, id, kind, M1, M2, S)`` alone, so ONLY this batch's rows are generated: the last shard of a 65536-row batch draws
+    its 8192 scenes, not 65536.  ``S`` follows ``problems`` as on the host.  Needs ``device_clouds=True``: the host cloud
+    sampler reads host arrays, which this source never makes.  Everything behind the scenes runs unchanged."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
@@ -673,6 +724,11 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
                          "roadmap path to shortcut")
     if problems not in ("uniform", "task"):
         raise ValueError(f"problems must be 'uniform' or 'task', got {problems!r}")
+    if scene_source not in ("host", "device"):
+        raise ValueError(f"scene_source must be 'host' or 'device', got {scene_source!r}")
+    if scene_source == "device" and not device_clouds:
+        raise ValueError("scene_source='device' needs device_clouds=True: the host cloud sampler reads the host generator's "
+                         "arrays, and the device source makes none")
     task = problems == "task"
     if task and not collision_free:
         raise ValueError("problems='task' poses checked starts and goals: it needs collision_free=True")
@@ -683,10 +739,14 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     nscene = total if scene_pool is None else min(total, scene_pool)
     gid = env_offset + np.arange(B)  # global environment ids of this batch's rows
     sid = gid % nscene  # environment g sits in scene g mod nscene
-    scn = (make_task_scenes if task else make_scenes)(nscene if scene_pool is not None else int(sid.max()) + 1 if B else 0,
-                                                      seed, kinds, M1, M2)
-    cloud = None if device_clouds else sample_scene_clouds_host(scn, NUM_OBSTACLE_POINTS, seed)
-    out = {k: torch.from_numpy(np.ascontiguousarray(v[sid])).to(dev) for k, v in scn.items()}
+    if scene_source == "device":  # (this batch's rows and nothing else; S is ``make_task_scenes``' default)
+        cloud = None
+        out = make_scenes_device(B, seed, kinds, M1, M2, S=8 if task else None, device=dev, scene_ids=torch.from_numpy(sid))
+    else:
+        scn = (make_task_scenes if task else make_scenes)(nscene if scene_pool is not None else int(sid.max()) + 1 if B else 0,
+                                                          seed, kinds, M1, M2)
+        cloud = None if device_clouds else sample_scene_clouds_host(scn, NUM_OBSTACLE_POINTS, seed)
+        out = {k: torch.from_numpy(np.ascontiguousarray(v[sid])).to(dev) for k, v in scn.items()}
     q = torch.from_numpy(random_configurations(env_offset + B, seed)[env_offset:]).to(dev)
     q_target = torch.from_numpy(random_configurations(env_offset + B, seed + 7)[env_offset:]).to(dev)
     lim = torch.as_tensor(ft.JOINT_LIMITS_REAL, dtype=torch.float32, device=dev)
