@@ -29,7 +29,8 @@ typedef void *mpx_stream_t;
 
 #define MPX_NUM_FRAMES 15 /* link0..8, hand, leftfinger, rightfinger, l/r fingertip, right_gripper */
 
-int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding): mpx_scene_generate;
+int mpx_version(void); /* 341 (unchanged: an addition, no caller of an earlier 341 library needs rebuilding): mpx_scene_generate_reference;
+                          341 (unchanged, likewise): mpx_scene_generate;
                           341 (unchanged, likewise): mpx_gripper_shortcut, mpx_gripper_shortcut_cloud, struct mpx_gripper_shortcut_options;
                           341 (unchanged, likewise): mpx_franka_shortcut, mpx_franka_shortcut_cloud, struct mpx_shortcut_options; 341 (unchanged, likewise):
                           mpx_task_candidates, struct mpx_task_candidates_options; 341 (unchanged, likewise):
@@ -720,6 +721,98 @@ int mpx_scene_generate(const int32_t *scene_kind, const int64_t *scene_ids, int 
                        int64_t scene_offset, float *cuboid_centers, float *cuboid_dims, float *cuboid_quats,
                        float *cylinder_centers, float *cylinder_radii, float *cylinder_heights, float *cylinder_quats,
                        float *support_boxes, int32_t *support_kind, mpx_stream_t stream);
+
+/* SCENES AS THE REFERENCE BUILDS THEM, drawn on the device: kind 3 the tabletop of setup_tables + place_objects +
+ * random_object (tabletop_environment.py:129-153, 215-324, 406-441; K from gen_data.py:618), kind 4 the cubby of
+ * Cubby.__init__ / .cuboids / .support_volumes (cubby_environment.py:62-431), kind 5 the merged cubby
+ * (MergedCubbyEnvironment, :660-704): that cubby with the plates between two pockets removed.  Restated from those lines,
+ * not copied.  geometrout is not in this tree: that its Cuboid.random, Cylinder.random and sample_volume draw uniformly
+ * between the bounds they are given is RECALLED, not pinned.  A new entry beside mpx_scene_generate, which it leaves as it
+ * is: operands, outputs, padding, keying and the Draws paragraph are that entry's, with these differences.
+ *   scene_kind int32 [B]: rows whose code is not 3, 4 or 5 are left UNTOUCHED (no element of theirs is written): a mixed
+ *   batch is mpx_scene_generate followed by this entry on the same arrays.  Of a row with code 3, 4 or 5 every element is
+ *   written.  7 <= M1 <= 64 (the cubby's plates), 0 <= M2 <= 64.
+ *   merge_pockets int32 [B,2] or NULL, read for kind 5 alone: the pocket pair (a, b) of scene b.  NULL: the scene draws its
+ *   pair.  (-1, -1): unmerged.  Anything else that is not a pair of DISTINCT pockets in 0 .. 3 is UNMERGED too (the operand
+ *   lives on the device, a launch cannot refuse it; scenes.make_scenes_device refuses it where it is handed host values).
+ *   Every scene is a function of (seed, scene id, kind, M1, M2, S, pair) alone; kinds 4 and 5 with one id and seed are the
+ *   same cubby.  Item 0 has FOUR blocks: u_j = u(0, j), j = 0 .. 15, is u01 of word j mod 4 of block j / 4.
+ *   TABLETOP (kind 3):  h = 0 if u_0 < 0.35f else u_1 0.4f.  Every table is a solid block from z = -0.02 to h: centre z
+ *     tz = (h - 0.02f) 0.5f, dim z td = h + 0.02f.  Front table: fx0 = fma(u_2, 0.1f, 0.275f), fx1 = fma(u_3, 0.1f, 1.275f),
+ *     fy1 = fma(u_4, 0.15f, 1.5f); a side table stands iff u_5 < 0.5f; fy0 = fma(u_6, 0.25f, -1.0f) with it (-1 .. -0.75),
+ *     else fma(u_6, 0.2f, -0.75f) (-0.75 .. -0.55).  Dx = fx1 - fx0, Dy = fy1 - fy0, ty = fma(u_7, 0.1f, 0.55f) Dy.
+ *       front TASK table: centre ((fx0 + fx1) 0.5f, fma(ty, 0.5f, fy0), tz), dims (Dx, ty, td);
+ *       front FREE table: centre ((fx0 + fx1) 0.5f, (fy1 + (fy0 + ty)) 0.5f, tz), dims (Dx, Dy - ty, td).
+ *     Side table (:272-303): sy1 = fma(u_8, 0.05f, -0.325f), length L = u_9 1.375f, sdx = L fma(u_10, 0.1f, 0.55f),
+ *     SDy = sy1 - fy0; it spans x from fx0 - L to fx0 and y from fy0 to sy1, split along x:
+ *       side TASK table (anchored at x max): centre (fx0 - sdx 0.5f, (sy1 + fy0) 0.5f, tz), dims (sdx, SDy, td);
+ *       side FREE table: centre (((fx0 - L) + (fx0 - sdx)) 0.5f, (sy1 + fy0) 0.5f, tz), dims (L - sdx, SDy, td).
+ *     Mount table (:306-324): mcx = fma(u_11, 0.04f, -0.02f), mcy = fma(u_12, 0.04f, -0.02f); centre (mcx, mcy, -0.01f),
+ *     dims (2 (fx0 - mcx), 2 (mcy - sy1) with a side table else fma(u_13, 0.04f, 0.9f), 0.02f).  The reference draws side_x
+ *     (:283), xdim (:315) and ydim (:321) and uses none of them: they are DROPPED, no uniform stands for them (u_14 is not
+ *     used).  K = 3 + integer draw (n = 12) from word 3 of block 3: 3 .. 14 objects.
+ *     Cuboid rows, the reference's `obstacles` order: task tables, free tables, mount table, objects -- with a side table
+ *     front task, side task, front free, side free, mount (T = 5), without front task, front free, mount (T = 3); identity
+ *     quaternions.  Supports: the task tables, front then side (the first S): SURFACES, the cuboid's centre, dims and
+ *     quaternion copied, approach 0, weight = dims_x dims_y.  Free tables and the mount table are not supports.
+ *     Candidates c = 0 .. 10 K - 1, points on the task tables' top faces, v_j = u(c + 1, j), j = 0 .. 7 (two blocks): with
+ *     A0 = Dx ty and A1 = sdx SDy (0 without a side table) the point lies on the side task table iff one stands and
+ *     v_0 (A0 + A1) >= A0 (probability proportional to the top face's area), at x = fma(v_1, sdx, fx0 - sdx),
+ *     y = fma(v_2, SDy, fy0); else on the front task table at x = fma(v_1, Dx, fx0), y = fma(v_2, ty, fy0).
+ *     The walk (place_objects): candidates in order while fewer than K objects are placed.  For a placed object i and
+ *     (dx, dy) = (x - x_i, y - y_i) the FOOTPRINT DISTANCE is, for a cylinder, sqrtf(fma(dx, dx, dy dy)) - radius_i; for a
+ *     cuboid with (ci, si) = (cos, sin) of its yaw: lx = fma(ci, dx, si dy), ly = fma(ci, dy, -(si dx)),
+ *     qx = |lx| - 0.5f dims_x, qy = |ly| - 0.5f dims_y, ex = max(qx, 0), ey = max(qy, 0),
+ *     d = sqrtf(fma(ex, ex, ey ey)) + min(max(qx, qy), 0).  The candidate is ACCEPTED iff every d_i > 0.05f.  This 2-D
+ *     test is the reference's 3-D sdf test: all objects stand on the table top, the candidate lies in the plane of their
+ *     bottom faces, so its offset along an object's axis is exactly the half height and contributes nothing; outside the
+ *     footprint the 3-D distance is the 2-D one, inside it both are <= 0 and the candidate is rejected either way.
+ *     m = the least d_i (1000 with nothing placed), xm = min(m, 0.15f), span = xm - 0.05f (> 0).  The object is a cylinder
+ *     iff v_3 < 0.3f: radius fma(v_4, span, 0.05f), height hh = fma(v_5, 0.3f, 0.05f), centre (x, y, fma(hh, 0.5f, h)).
+ *     Otherwise a cuboid: dims (fma(v_4, span, 0.05f), fma(v_5, span, 0.05f), dz = fma(v_6, 0.3f, 0.05f)), yaw v_7 pi/2,
+ *     quaternion q(yaw), centre (x, y, fma(dz, 0.5f, h)).  Cylinders fill rows 0, 1, .. of their arrays, cuboids rows T,
+ *     T + 1, .. in the order accepted.  OVERFLOW: an accepted cylinder with M2 cylinders placed, or an accepted cuboid whose
+ *     row would be M1, gets no row, does not count towards K and does not block later candidates; the walk goes on.
+ *   CUBBY (kind 4) and MERGED CUBBY (kind 5):  left = fma(u_0, 0.2f, 0.6f), right = fma(u_1, 0.2f, -0.8f),
+ *     bottom = fma(u_2, 0.2f, 0.1f), front = fma(u_3, 0.2f, 0.45f), back = front + fma(u_4, 0.4f, 0.15f),
+ *     top = fma(u_5, 0.2f, 0.6f), mz = fma(u_6, 0.2f, 0.35f) (the shelf's height), my = fma(u_7, 0.2f, -0.1f) (the centre
+ *     wall's y), t = fma(u_8, 0.02f, 0.01f) (both plate thicknesses too), yaw = fma(u_9, pi/9, -pi/18): the reference's twelve.
+ *     The plates are rotated about the vertical axis through the cabinet's centre (px, py) = ((front + back) 0.5f,
+ *     (left + right) 0.5f): a local point l lies at  W(l) = ((c ax - s ay) + px, (s ax + c ay) + py, lz)  with ax = lx - px,
+ *     ay = ly - py, (c, s) = (cos, sin) of yaw, every product, difference and sum rounded on its own.  With
+ *     pz = (top + bottom) 0.5f, Dd = back - front, Wd = left - right, Hd = (top - bottom) + t the seven plates in the
+ *     reference's order (local centre; dims), all q(yaw):
+ *       0 back (back, py, top 0.5f; t, Wd, top: it reaches the floor)   1 bottom (px, py, bottom; Dd, Wd, t)
+ *       2 top (px, py, top; Dd, Wd, t)   3 right (px, right, pz; Dd, t, Hd)   4 left (px, left, pz; Dd, t, Hd)
+ *       5 centre wall (px, my, pz; Dd, t, Hd)   6 middle shelf (px, py, mz; Dd, Wd, t).
+ *     The reference leaves the centre wall or the shelf out where isclose(position, 0): an event of measure zero in these
+ *     ranges for the wall and impossible for the shelf; a cubby here ALWAYS has seven plates.
+ *     Supports, unmerged: the four pockets p = 2 level + side of support_volumes' last branch in its order, level 0 the top
+ *     (z from mz to top; level 1 from bottom to mz), side 0 the +y side (y from my to left; side 1 from right to my):
+ *     VOLUMES, centre W(px, (ya + yb) 0.5f, (za + zb) 0.5f), dims (Dd, yb - ya, zb - za), q(yaw), approach 0, weight 1.
+ *     Merge, by MergedCubbyEnvironment's rule for a pair (a, b) of distinct pockets: the middle shelf goes when a and b lie
+ *     on different levels (a >> 1 != b >> 1), the centre wall when they lie on different sides (a & 1 != b & 1).  A removed
+ *     plate is DROPPED and the later rows move up (5 or 6 live plates): this tree's padding is the all-zero row and not
+ *     every consumer masks a cuboid with a single zero dim.  The reference instead keeps a zero-thickness cuboid that its
+ *     own consumers mask.  Supports become the matching branch of support_volumes, the whole extents taking the place of the
+ *     removed plate's position: both gone: ONE volume (y right .. left, z bottom .. top), every pocket p maps to support 0;
+ *     the wall alone gone: [top row, bottom row], p maps to p >> 1; the shelf alone gone: [left (+y) column, right column],
+ *     p maps to p & 1.  Without merge_pockets the pair is the i-th of (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), i = integer draw
+ *     (n = 6) from word 0 of block 3: one more uniform, which the cubby's own parameters do not read.
+ *   The longest chain is a rotated plate's or pocket's x or y: a parameter (one fma; back: two), px or py (two more), ax or
+ *   ay (one), two products, their sum, + p: at most ten rounded operations, each within 0.5 ulp (6e-8 below 1 m, 1.2e-7 at
+ *   2 m), plus a float32 sine and cosine within 2e-7 on a lever arm below 0.45 m: within about 1.4e-6 of exact arithmetic.
+ *   The tabletop's objects are at most five operations from their uniforms; its span = min(m, 0.15f) - 0.05f carries the
+ *   error of m (a dozen operations on magnitudes below 2 m and a square root), scaled by a uniform below 1.  Discrete
+ *   decisions that read a uniform alone are exact; the candidate's table and the accept test compare computed floats.
+ *   Refused before any launch: as mpx_scene_generate, with M1 outside 7 .. 64.  ceil(B / 4) workgroups of 256 threads on
+ *   grid.x, one wave per scene: every lane draws three candidates up front, the accept walk of at most 140 steps holds the
+ *   placed objects one per lane and combines the verdict with a ballot and the least distance with four lane exchanges.
+ *   No LDS, no scratch, no allocation, no atomics; enqueued on `stream` (capturable).                                   */
+int mpx_scene_generate_reference(const int32_t *scene_kind, const int64_t *scene_ids, const int32_t *merge_pockets, int B, int M1,
+                                 int M2, int S, uint64_t seed, int64_t scene_offset, float *cuboid_centers, float *cuboid_dims,
+                                 float *cuboid_quats, float *cylinder_centers, float *cylinder_radii, float *cylinder_heights,
+                                 float *cylinder_quats, float *support_boxes, int32_t *support_kind, mpx_stream_t stream);
 
 /* ---- planning against a point cloud: a truncated distance field, its sampler, the planner that reads it -------------
  * One grid for the whole batch (a host struct, read before the launch): node (i,j,k), 0 <= i < nx etc., sits at

@@ -49,6 +49,7 @@ PROTOTYPES = {
     "mpx_gripper_roadmap": [P, P, I, I, P, F, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P, P, P, P],
     "mpx_task_candidates": [P, P, I, I, P, I, F, P, P, P, I, P, P, I, P, P, P, I, P, ctypes.c_uint64, L, P, P, P, P, P],
     "mpx_scene_generate": [P, P, I, I, I, I, ctypes.c_uint64, L, P, P, P, P, P, P, P, P, P, P],
+    "mpx_scene_generate_reference": [P, P, P, I, I, I, I, ctypes.c_uint64, L, P, P, P, P, P, P, P, P, P, P],
     "mpx_cloud_field_build": [P, L, I, I, P, I, P, P, P],
     "mpx_cloud_field_sample": [P, P, I, P, L, I, I, P, P, P],
     "mpx_franka_plan_cloud_scratch": [I, I, I, I],

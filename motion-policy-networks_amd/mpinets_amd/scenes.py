@@ -1,7 +1,8 @@
 """Synthetic planning problems for tests and benchmarks.
 
 The reference's scene generators (``mpinets/data_pipeline/environments/*.py``) need PyBullet and
-IK and are out of scope; this module restates their *distributions* with a seeded NumPy RNG:
+IK and are out of scope; this module restates their *distributions* with a seeded NumPy RNG.  Three LOOSE stand-ins, kept
+bit for bit because benchmarks and goldens are drawn from them:
 
 * tabletop -- ``tabletop_environment.py:215-324,406-441``: table height 0 w.p. 0.35 else U(0,0.4);
   front table x in [U(.275,.375), U(1.275,1.375)], width U(1.5,1.65); optional side table p=0.5;
@@ -11,11 +12,23 @@ IK and are out of scope; this module restates their *distributions* with a seede
   U(.01,.03)), yaw +-pi/18;
 * dresser-like -- ``dresser_environment.py:198-222``: up to 40 yaw-rotated cuboids.
 
+and three restatements that follow the reference's construction draw by draw and plate by plate (each in two stages,
+draws -> named parameters and parameters -> primitives and supports; the second stage is pinned by fixtures made by
+running the reference, tests/golden/gen_scene_reference_golden.py):
+
+* tabletop_reference -- ``setup_tables`` + ``place_objects`` + ``random_object`` (``tabletop_environment.py:129-153,
+  215-324,406-441``): solid tables from z = -0.02 up, split into task and free parts, the mount table, and K = 3..14 objects
+  placed greedily at least 5 cm from the objects before them, the clearance found bounding the new footprint;
+* cubby_reference -- ``Cubby.__init__``, ``.cuboids``, ``.support_volumes`` (``cubby_environment.py:62-431``): twelve
+  parameters, seven plates in the reference's order rotated about the cabinet's centre, four pockets;
+* merged_cubby -- ``MergedCubbyEnvironment`` (``:660-704``): that cubby with the plates between two pockets removed.
+
 Primitive sets are zero-padded to fixed M1 / M2 exactly like the dataset rows
 (zero dims, identity quaternion, ``mpinets/data_loader.py:202,210-215``).
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -132,11 +145,207 @@ def _dresser(rng, M1, M2, supports=None):
     return cc, cd, cq, yc, yr, yh, yq
 
 
-_GENERATORS = {"tabletop": _tabletop, "cubby": _cubby, "dresser": _dresser}
+# ---- the reference's scenes, stage by stage ------------------------------------------------------------------------------------
+MERGE_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))  # the six unordered pocket pairs, in the order they are drawn
 
 
-def _scene_arrays(B: int, seed: int, kinds, M1: int, M2: int, S: Optional[int] = None) -> Dict[str, np.ndarray]:
+def _tabletop_reference_parameters(rng) -> Dict[str, float]:
+    """Stage 1 of ``setup_tables`` (tabletop_environment.py:215-324): the draws, named.  The reference also draws ``side_x``
+    (:283), ``xdim`` (:315) and ``ydim`` (:321) and uses none of them: they are DROPPED here, not consumed."""
+    p = dict(height=0.0 if rng.random() < 0.35 else rng.uniform(0.0, 0.4), front_x_min=rng.uniform(0.275, 0.375),
+             front_x_max=rng.uniform(1.275, 1.375), front_y_max=rng.uniform(1.5, 1.65), has_side_table=bool(rng.random() < 0.5))
+    p["front_y_min"] = rng.uniform(-1.0, -0.75) if p["has_side_table"] else rng.uniform(-0.75, -0.55)
+    p["front_task_scalar"] = rng.uniform(0.55, 0.65)
+    if p["has_side_table"]:
+        p.update(side_y_max=rng.uniform(-0.325, -0.275), side_length=rng.uniform(0.0, 1.375), side_task_scalar=rng.uniform(0.55, 0.65))
+    p.update(mount_x=rng.uniform(-0.02, 0.02), mount_y=rng.uniform(-0.02, 0.02), mount_dim_y=rng.uniform(0.9, 0.94))
+    return p
+
+
+def _tabletop_reference_tables(p):
+    """Stage 2: -> (task tables, free tables + the mount table), each a list of (centre, dims): the reference's ``tables`` and
+    ``clear_tables``.  Every table is a solid block from z = -0.02 to the table height."""
+    z, dz = (p["height"] - 0.02) / 2, p["height"] + 0.02
+    x0, x1, y0, y1 = p["front_x_min"], p["front_x_max"], p["front_y_min"], p["front_y_max"]
+    ty = p["front_task_scalar"] * (y1 - y0)
+    task = [([(x0 + x1) / 2, ty / 2 + y0, z], [x1 - x0, ty, dz])]
+    free = [([(x0 + x1) / 2, (y1 + (y0 + ty)) / 2, z], [x1 - x0, (y1 - y0) - ty, dz])]
+    mount_dim_y = p["mount_dim_y"]
+    if p["has_side_table"]:
+        sy1, L = p["side_y_max"], p["side_length"]
+        sdx = L * p["side_task_scalar"]
+        task.append(([x0 - sdx / 2, (sy1 + y0) / 2, z], [sdx, sy1 - y0, dz]))
+        free.append(([((x0 - L) + (x0 - sdx)) / 2, (sy1 + y0) / 2, z], [L - sdx, sy1 - y0, dz]))
+        mount_dim_y = 2 * (p["mount_y"] - sy1)
+    free.append(([p["mount_x"], p["mount_y"], -0.01], [2 * (x0 - p["mount_x"]), mount_dim_y, 0.02]))
+    return task, free
+
+
+def _footprint_distance(obj, x, y) -> float:
+    """Distance of (x, y) to the footprint of ``obj`` = ("cylinder", cx, cy, radius) or ("cuboid", cx, cy, dx, dy, yaw): what the
+    reference's 3-D ``sdf`` gives for a point in the plane of the objects' bottom faces wherever it is positive."""
+    dx, dy = x - obj[1], y - obj[2]
+    if obj[0] == "cylinder":
+        return math.hypot(dx, dy) - obj[3]
+    c, s = math.cos(obj[5]), math.sin(obj[5])
+    qx, qy = abs(c * dx + s * dy) - obj[3] / 2, abs(c * dy - s * dx) - obj[4] / 2
+    return math.hypot(max(qx, 0.0), max(qy, 0.0)) + min(max(qx, qy), 0.0)
+
+
+def _place_objects(points, how_many: int, new_object, distance=_footprint_distance):
+    """``place_objects`` (tabletop_environment.py:129-153): walk the candidate points in order while fewer than ``how_many``
+    objects stand; a candidate is accepted when every object's distance to it is above 0.05, and ``new_object(x, y, m)`` is
+    handed the least of them (1000 with nothing placed); None from it: the object found no row, is not counted and blocks
+    nothing.  -> (objects, accepted candidate indices, the clearances handed over)."""
+    objects, accepted, clearances = [], [], []
+    for i, (x, y) in enumerate(points):
+        if len(objects) >= how_many:
+            break
+        d = [distance(o, x, y) for o in objects]
+        if all(v > 0.05 for v in d):
+            m = min(d, default=1000.0)
+            o = new_object(x, y, m)
+            if o is not None:
+                objects.append(o), accepted.append(i), clearances.append(m)
+    return objects, accepted, clearances
+
+
+def _tabletop_reference(rng, M1, M2, supports=None):
+    assert M1 >= 7, "the reference's scenes need M1 >= 7 (five tables; a cubby's seven plates)"
+    cc, cd, cq = np.zeros((M1, 3)), np.zeros((M1, 3)), np.tile([1.0, 0, 0, 0], (M1, 1))
+    yc, yr, yh, yq = np.zeros((M2, 3)), np.zeros((M2, 1)), np.zeros((M2, 1)), np.tile([1.0, 0, 0, 0], (M2, 1))
+    p = _tabletop_reference_parameters(rng)
+    task, free = _tabletop_reference_tables(p)
+    for n, (c, d) in enumerate(task + free):  # (the reference's ``obstacles`` order: task tables, free tables, mount table)
+        cc[n], cd[n] = c, d
+        if n < len(task):
+            _support(supports, SUPPORT_SURFACE, c, d, cq[n], 0.0, d[0] * d[1])
+    T = len(task) + len(free)
+    K = int(rng.integers(3, 15))
+    area = np.array([d[0] * d[1] for _, d in task])
+    which = (rng.random(10 * K)[:, None] * area.sum() >= np.cumsum(area)[None]).sum(1).clip(max=len(task) - 1)
+    uv = rng.random((10 * K, 2))
+    lo = np.array([[c[0] - d[0] / 2, c[1] - d[1] / 2] for c, d in task])[which]
+    points = lo + uv * np.array([d[:2] for _, d in task])[which]
+    count = {"cuboid": T, "cylinder": 0}
+
+    def new_object(x, y, m):
+        xy_max = min(m, 0.15)
+        if rng.random() < 0.3:
+            r, hh = rng.uniform(0.05, xy_max), rng.uniform(0.05, 0.35)
+            if count["cylinder"] >= M2:
+                return None
+            i = count["cylinder"]
+            yc[i], yr[i], yh[i] = [x, y, p["height"] + hh / 2], r, hh
+            count["cylinder"] += 1
+            return ("cylinder", x, y, r)
+        d = np.array([rng.uniform(0.05, xy_max), rng.uniform(0.05, xy_max), rng.uniform(0.05, 0.35)])
+        yaw = rng.uniform(0, np.pi / 2)
+        if count["cuboid"] >= M1:
+            return None
+        i = count["cuboid"]
+        cc[i], cd[i], cq[i] = [x, y, p["height"] + d[2] / 2], d, _yaw_quat(yaw)
+        count["cuboid"] += 1
+        return ("cuboid", x, y, d[0], d[1], yaw)
+
+    _place_objects(points, K, new_object)
+    return cc, cd, cq, yc, yr, yh, yq
+
+
+def _cubby_reference_parameters(rng) -> Dict[str, float]:
+    """Stage 1 of ``Cubby.__init__`` (cubby_environment.py:62-74): the twelve parameters (the two plate thicknesses a merge
+    zeroes start as the cubby's)."""
+    p = dict(left=rng.uniform(0.6, 0.8), right=rng.uniform(-0.8, -0.6), bottom=rng.uniform(0.1, 0.3), front=rng.uniform(0.45, 0.65))
+    p["back"] = p["front"] + rng.uniform(0.15, 0.55)
+    p.update(top=rng.uniform(0.6, 0.8), mid_h_z=rng.uniform(0.35, 0.55), mid_v_y=rng.uniform(-0.1, 0.1),
+             thickness=rng.uniform(0.01, 0.03))
+    p.update(middle_shelf_thickness=p["thickness"], center_wall_thickness=p["thickness"],
+             rotation=rng.uniform(-np.pi / 18, np.pi / 18))
+    return p
+
+
+def check_merge_pockets(pair):
+    """(-1, -1): unmerged; otherwise a pair of distinct pockets in 0..3 -- anything else is refused."""
+    a, b = int(pair[0]), int(pair[1])
+    if (a, b) != (-1, -1) and not (0 <= a <= 3 and 0 <= b <= 3 and a != b):
+        raise ValueError(f"merge_pockets must be (-1, -1) or a pair of distinct pockets in 0..3, got {(a, b)}")
+    return a, b
+
+
+def merged_cubby_parameters(p: Dict[str, float], pair) -> Dict[str, float]:
+    """``MergedCubbyEnvironment.gen``'s rule (cubby_environment.py:679-686): the middle shelf goes when the two pockets lie on
+    different levels, the centre wall when they lie on different sides."""
+    a, b = check_merge_pockets(pair)
+    p = dict(p)
+    if a >= 0 and (a >> 1) != (b >> 1):
+        p["middle_shelf_thickness"] = 0.0
+    if a >= 0 and (a & 1) != (b & 1):
+        p["center_wall_thickness"] = 0.0
+    return p
+
+
+def merged_support_index(pocket: int, p: Dict[str, float]) -> int:
+    """The support row an original pocket (2 level + side) lies in after the merge ``p`` carries."""
+    no_shelf, no_wall = p["middle_shelf_thickness"] == 0.0, p["center_wall_thickness"] == 0.0
+    return 0 if no_shelf and no_wall else pocket >> 1 if no_wall else pocket & 1 if no_shelf else pocket
+
+
+def _cubby_reference_primitives(p: Dict[str, float]):
+    """Stage 2: -> (plates, supports), each a list of (centre, dims) in the world, and the yaw all of them share.  Plates in
+    the reference's order -- back, bottom, top, right, left, centre wall, middle shelf -- with a plate of thickness 0 DROPPED
+    (the reference keeps a zero-thickness cuboid that its own consumers mask); supports: ``support_volumes``' branches."""
+    L, R, Bo, F, Ba, To, mz, my, t = (p[k] for k in ("left", "right", "bottom", "front", "back", "top", "mid_h_z", "mid_v_y", "thickness"))
+    px, py, pz = (F + Ba) / 2, (L + R) / 2, (To + Bo) / 2
+    yaw = p["rotation"]
+    c, s = np.cos(yaw), np.sin(yaw)
+
+    def world(l):
+        ax, ay = l[0] - px, l[1] - py
+        return [(c * ax - s * ay) + px, (s * ax + c * ay) + py, l[2]]
+
+    plates = [([Ba, py, To / 2], [t, L - R, To]), ([px, py, Bo], [Ba - F, L - R, t]), ([px, py, To], [Ba - F, L - R, t]),
+              ([px, R, pz], [Ba - F, t, (To - Bo) + t]), ([px, L, pz], [Ba - F, t, (To - Bo) + t])]
+    no_wall, no_shelf = p["center_wall_thickness"] == 0.0, p["middle_shelf_thickness"] == 0.0
+    if not no_wall:
+        plates.append(([px, my, pz], [Ba - F, p["center_wall_thickness"], (To - Bo) + t]))
+    if not no_shelf:
+        plates.append(([px, py, mz], [Ba - F, L - R, p["middle_shelf_thickness"]]))
+    levels = [(Bo, To)] if no_shelf else [(mz, To), (Bo, mz)]
+    sides = [(R, L)] if no_wall else [(my, L), (R, my)]
+    pockets = [([px, (ya + yb) / 2, (za + zb) / 2], [Ba - F, yb - ya, zb - za]) for za, zb in levels for ya, yb in sides]
+    return [(world(l), d) for l, d in plates], [(world(l), d) for l, d in pockets], yaw
+
+
+def _cubby_reference(rng, M1, M2, supports=None, merge=(-1, -1)):
+    """``merge``: the pocket pair of a merged cubby ((-1, -1): unmerged); None: drawn from the six unordered pairs with one
+    more uniform, AFTER the cubby's own draws (so the cubby of a seed does not depend on it)."""
+    assert M1 >= 7, "a cubby has seven plates: M1 >= 7"
+    cc, cd, cq = np.zeros((M1, 3)), np.zeros((M1, 3)), np.tile([1.0, 0, 0, 0], (M1, 1))
+    yc, yr, yh, yq = np.zeros((M2, 3)), np.zeros((M2, 1)), np.zeros((M2, 1)), np.tile([1.0, 0, 0, 0], (M2, 1))
+    p = _cubby_reference_parameters(rng)
+    if merge is None:
+        merge = MERGE_PAIRS[min(int(rng.random() * 6), 5)]
+    plates, pockets, yaw = _cubby_reference_primitives(merged_cubby_parameters(p, merge))
+    for i, (c, d) in enumerate(plates):
+        cc[i], cd[i], cq[i] = c, d, _yaw_quat(yaw)
+    for c, d in pockets:
+        _support(supports, SUPPORT_VOLUME, c, d, _yaw_quat(yaw), 0.0, 1.0)
+    return cc, cd, cq, yc, yr, yh, yq
+
+
+def _merged_cubby(rng, M1, M2, supports=None, merge=None):
+    return _cubby_reference(rng, M1, M2, supports, merge)
+
+
+_GENERATORS = {"tabletop": _tabletop, "cubby": _cubby, "dresser": _dresser, "tabletop_reference": _tabletop_reference,
+               "cubby_reference": _cubby_reference, "merged_cubby": _merged_cubby}
+REFERENCE_KINDS = ("tabletop_reference", "cubby_reference", "merged_cubby")
+
+
+def _scene_arrays(B: int, seed: int, kinds, M1: int, M2: int, S: Optional[int] = None, merge_pockets=None) -> Dict[str, np.ndarray]:
     """``make_scenes`` (``S`` None) and ``make_task_scenes``: one rng, one walk over the generators."""
+    if merge_pockets is not None:
+        merge_pockets = [check_merge_pockets(pair) for pair in np.asarray(merge_pockets).reshape(B, 2)]
     rng = np.random.default_rng(seed)
     out = [[] for _ in range(7)]
     boxes = np.zeros((B, S or 0, 12), np.float32)
@@ -144,7 +353,11 @@ def _scene_arrays(B: int, seed: int, kinds, M1: int, M2: int, S: Optional[int] =
     kind = np.zeros((B, S or 0), np.int32)
     for b in range(B):
         supports = None if S is None else []
-        parts = _GENERATORS[kinds[b % len(kinds)]](rng, M1, M2, supports)
+        name = kinds[b % len(kinds)]
+        if name == "merged_cubby":  # (the pair of scene b; None: the scene draws its own)
+            parts = _merged_cubby(rng, M1, M2, supports, None if merge_pockets is None else merge_pockets[b])
+        else:
+            parts = _GENERATORS[name](rng, M1, M2, supports)
         for o, p in zip(out, parts):
             o.append(p)
         for i, (k, row) in enumerate((supports or [])[:S]):
@@ -157,12 +370,15 @@ def _scene_arrays(B: int, seed: int, kinds, M1: int, M2: int, S: Optional[int] =
     return arrays
 
 
-def make_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16) -> Dict[str, np.ndarray]:
-    """-> float32 arrays cuboid_{centers,dims,quats} [B,M1,*], cylinder_{centers,radii,heights,quats} [B,M2,*]."""
-    return _scene_arrays(B, seed, kinds, M1, M2)
+def make_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16, merge_pockets=None) -> Dict[str, np.ndarray]:
+    """-> float32 arrays cuboid_{centers,dims,quats} [B,M1,*], cylinder_{centers,radii,heights,quats} [B,M2,*].
+    ``merge_pockets`` (int [B,2]; read by "merged_cubby" scenes alone): the pocket pair of scene b, (-1, -1) unmerged; None:
+    every merged cubby draws its pair."""
+    return _scene_arrays(B, seed, kinds, M1, M2, merge_pockets=merge_pockets)
 
 
-def make_task_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16, S: int = 8) -> Dict[str, np.ndarray]:
+def make_task_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16, S: int = 8,
+                     merge_pockets=None) -> Dict[str, np.ndarray]:
     """``make_scenes``' arrays, bit for bit (the supports cost no draw of the rng), plus where each scene can be worked on:
     ``support_boxes`` float32 [B,S,12] -- centre (3), dims (3), quaternion w x y z (4), ``approach`` (the world yaw of the axis
     the gripper reaches along) and ``weight`` -- and ``support_kind`` int32 [B,S]: 0 padding (zero dims, the identity
@@ -176,16 +392,24 @@ def make_task_scenes(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M
     * dresser: a STAND-IN with no reference counterpart (this dresser is "dresser-like", not the reference's recursive one):
       one volume per plate, the free space above it inside its cell; ``approach`` is the horizontal direction along the
       plate's depth axis that has a positive world-x component (the reach runs from the robot inward), weight 1.  With more
-      plates than ``S`` the first ``S`` are kept."""
+      plates than ``S`` the first ``S`` are kept.
+    * tabletop_reference: the TASK tables (front, then side where it stands) are surfaces, weight = the top face's area; the
+      free tables and the mount table are not supports.
+    * cubby_reference: the four pockets of ``support_volumes``' last branch in its order, pocket 2 level + side with level 0
+      the top and side 0 the +y side: volumes, ``approach`` 0, weight 1.
+    * merged_cubby: the matching branch -- one whole volume, or [top row, bottom row], or [left column, right column];
+      ``merged_support_index`` maps an original pocket to its row."""
     assert S >= 1
-    return _scene_arrays(B, seed, kinds, M1, M2, S)
+    return _scene_arrays(B, seed, kinds, M1, M2, S, merge_pockets)
 
 
-SCENE_KIND_CODES = {"tabletop": 0, "cubby": 1, "dresser": 2}  # ``mpx_scene_generate``'s ``scene_kind``
+# ``scene_kind``: 0..2 are ``mpx_scene_generate``'s, 3..5 ``mpx_scene_generate_reference``'s
+SCENE_KIND_CODES = {"tabletop": 0, "cubby": 1, "dresser": 2, "tabletop_reference": 3, "cubby_reference": 4, "merged_cubby": 5}
 
 
 def make_scenes_device(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16, M2: int = 16, S: Optional[int] = None,
-                       device="cuda:0", env_offset: int = 0, scene_ids: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                       device="cuda:0", env_offset: int = 0, scene_ids: Optional[torch.Tensor] = None,
+                       merge_pockets=None) -> Dict[str, torch.Tensor]:
     """The scenes of ``make_scenes`` (``S`` None) or ``make_task_scenes`` (``S`` >= 1) drawn ON THE DEVICE
     (csrc/scene_gen.hip, ``mpx_scene_generate``): the same keys, shapes, dtypes, padding and DISTRIBUTIONS, as tensors on
     ``device``, every scene a function of ``(seed, scene id, kind, M1, M2, S)`` alone -- Philox stream 19 keyed by the scene
@@ -193,10 +417,22 @@ def make_scenes_device(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16,
     the same seed gives other scenes of the same distribution.  Scene b has id ``env_offset + b``, or ``scene_ids[b]``
     (int64 [B], any order, repeats allowed: the rows of a shard, the tiles of a ``scene_pool``); the kind of scene id g is
     ``kinds[g % len(kinds)]``, the host's rule.  3 <= M1 <= 64, 0 <= M2 <= 64, S <= 64.  Every element is written by the
-    kernel; nothing is generated for a row that is not asked for."""
+    kernel; nothing is generated for a row that is not asked for.
+
+    The kinds "tabletop_reference", "cubby_reference" and "merged_cubby" come from a second entry
+    (csrc/scene_gen_reference.hip, ``mpx_scene_generate_reference``; they need M1 >= 7): a batch of old kinds alone calls the
+    first entry alone, as before; one of new kinds alone the second alone; a mixed one the first, then the second on the same
+    arrays (it leaves the rows of the old kinds untouched).  ``merge_pockets`` (int [B,2], read by "merged_cubby" rows alone):
+    the pocket pair of row b, (-1, -1) unmerged; None: every merged cubby draws its pair.  Host values (a list, an array, a
+    CPU tensor) that are neither are refused with a ``ValueError``; a tensor already on the device is not read back, and the
+    kernel treats such a row as unmerged."""
     from . import _lib
 
     dev = torch.device(device)
+    if merge_pockets is not None and not (isinstance(merge_pockets, torch.Tensor) and merge_pockets.is_cuda):
+        merge_pockets = torch.as_tensor(np.asarray(merge_pockets)).reshape(-1, 2)
+        for pair in merge_pockets.tolist():
+            check_merge_pockets(pair)
     codes = torch.tensor([SCENE_KIND_CODES[k] for k in kinds], dtype=torch.int32)
     if scene_ids is None:
         ids = None
@@ -216,10 +452,21 @@ def make_scenes_device(B: int, seed: int = 0, kinds=("tabletop",), M1: int = 16,
            "cylinder_quats": empty(B, M2, 4)}
     if S is not None:
         out.update(support_boxes=empty(B, S, 12), support_kind=empty(B, S, dtype=torch.int32))
-    _lib.call("mpx_scene_generate", _lib.ptr(kind), _lib.ptr(ids), B, M1, M2, 0 if S is None else S, int(seed) & (2 ** 64 - 1),
-              int(env_offset), *(_lib.ptr(out[k]) for k in ("cuboid_centers", "cuboid_dims", "cuboid_quats", "cylinder_centers",
-                                                            "cylinder_radii", "cylinder_heights", "cylinder_quats")),
-              _lib.ptr(out.get("support_boxes")), _lib.ptr(out.get("support_kind")))
+    tail = (B, M1, M2, 0 if S is None else S, int(seed) & (2 ** 64 - 1), int(env_offset),
+            *(_lib.ptr(out[k]) for k in ("cuboid_centers", "cuboid_dims", "cuboid_quats", "cylinder_centers", "cylinder_radii",
+                                         "cylinder_heights", "cylinder_quats")),
+            _lib.ptr(out.get("support_boxes")), _lib.ptr(out.get("support_kind")))
+    new = [k in REFERENCE_KINDS for k in kinds]
+    if not all(new):
+        _lib.call("mpx_scene_generate", _lib.ptr(kind), _lib.ptr(ids), *tail)
+    if any(new):
+        pockets = None
+        if merge_pockets is not None:
+            pockets = merge_pockets.to(device=dev, dtype=torch.int32).contiguous()
+            if pockets.shape != (B, 2):
+                raise _lib.MpxError(f"make_scenes_device: merge_pockets must be [B,2] = [{B},2], got {tuple(pockets.shape)}")
+            _lib.require_cuda(pockets)
+        _lib.call("mpx_scene_generate_reference", _lib.ptr(kind), _lib.ptr(ids), _lib.ptr(pockets), *tail)
     return out
 
 
@@ -419,6 +666,39 @@ def _task_problems(prims: Dict[str, torch.Tensor], support_boxes: torch.Tensor, 
     goal_pose = torch.where(valid[:, None, None], pose_g, torch.full_like(pose_g, nan))
     target_support = torch.where(valid, sup_g, torch.full_like(sup_g, -1))
     return q_start, q_goal, valid, start_pose, goal_pose, target_support
+
+
+def _merge_task_rows(out: Dict[str, torch.Tensor], kinds, sid: np.ndarray, valid: torch.Tensor, start_pose: torch.Tensor,
+                     goal_pose: torch.Tensor, target_support: torch.Tensor, seed: int, M1: int, M2: int, dev) -> torch.Tensor:
+    """``MergedCubbyEnvironment.gen`` per row (cubby_environment.py:666-704): the merged-cubby rows of the batch were generated
+    UNMERGED and their start and goal drawn in different pockets; here every VALID one of them is generated again with those
+    two pockets as its pair -- the same cubby (same id and seed) without the plates between them -- and written over the
+    row's primitives and supports in ``out``.  Invalid rows stay unmerged.  The pockets are found as the reference finds
+    them, by which unmerged support holds the pose's position.  -> ``target_support`` mapped to the merged supports.
+    Everything computed afterwards (the region keys, the experts, the followers, the scene cloud) sees the merged scene; the
+    reference leaves its candidates' negative volumes stale after the merge, here they follow from the merged supports."""
+    S = out["support_kind"].shape[1]
+    is_merged = torch.from_numpy(np.asarray([kinds[g % len(kinds)] == "merged_cubby" for g in sid], bool)).to(dev)
+    rows = is_merged & valid
+    boxes = out["support_boxes"]
+
+    def pocket_of(pose):  # the unmerged pocket that holds the position (-1: none; the goal's is ``target_support``)
+        local = pose[:, None, :3, 3] - boxes[..., :3]
+        c, s = 1 - 2 * boxes[..., 9] ** 2, 2 * boxes[..., 6] * boxes[..., 9]  # (cos, sin of the yaw of (w, 0, 0, z))
+        lx, ly = c * local[..., 0] + s * local[..., 1], c * local[..., 1] - s * local[..., 0]
+        inside = (lx.abs() <= boxes[..., 3] / 2) & (ly.abs() <= boxes[..., 4] / 2) & (local[..., 2].abs() <= boxes[..., 5] / 2)
+        inside &= out["support_kind"] == SUPPORT_VOLUME
+        return torch.where(inside.any(1), inside.float().argmax(1), torch.full_like(inside[:, 0], -1, dtype=torch.int64))
+
+    a, b = pocket_of(start_pose), target_support.long()
+    rows &= (a >= 0) & (b >= 0) & (a != b) & (a < 4) & (b < 4)
+    pair = torch.where(rows[:, None], torch.stack([a, b], 1), torch.full((len(sid), 2), -1, dtype=torch.int64, device=dev)).int()
+    merged = make_scenes_device(len(sid), seed, kinds, M1, M2, S=S, device=dev, scene_ids=torch.from_numpy(sid), merge_pockets=pair)
+    for key, v in merged.items():
+        out[key] = torch.where(rows.reshape((-1,) + (1,) * (v.dim() - 1)), v, out[key])
+    no_shelf, no_wall = (a >> 1) != (b >> 1), (a & 1) != (b & 1)
+    mapped = torch.where(no_shelf & no_wall, torch.zeros_like(b), torch.where(no_wall, b >> 1, b & 1))
+    return torch.where(rows, mapped.to(target_support.dtype), target_support)
 
 
 def _task_region_keys(support_boxes: torch.Tensor, support_kind: torch.Tensor, target_support: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -691,7 +971,16 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     ``gid % nscene`` (``scene_pool`` keeps its meaning; without it every row has its own scene) and depends on
     ``(seed, id, kind, M1, M2, S)`` alone, so ONLY this batch's rows are generated: the last shard of a 65536-row batch draws
     its 8192 scenes, not 65536.  ``S`` follows ``problems`` as on the host.  Needs ``device_clouds=True``: the host cloud
-    sampler reads host arrays, which this source never makes.  Everything behind the scenes runs unchanged."""
+    sampler reads host arrays, which this source never makes.  Everything behind the scenes runs unchanged.
+
+    ``kinds`` may name the reference's own scenes, "tabletop_reference", "cubby_reference" and "merged_cubby" (M1 >= 7), under
+    both sources.  With ``problems="uniform"`` a merged cubby is the one with its drawn pocket pair.  With ``problems="task"``
+    a merged-cubby row follows ``MergedCubbyEnvironment``: the scene is generated unmerged, start and goal are picked in
+    different pockets as for any cubby, then every VALID such row is generated again with those two pockets as its pair and
+    ``target_support`` is mapped to the merged support; ``target_volume``, the experts, the followers and the scene cloud all
+    see the merged primitives (``target_negative_volumes`` are recomputed from the merged supports, where the reference leaves
+    its own stale); invalid rows stay unmerged.  The merge is per ROW, not per scene, so this needs
+    ``scene_source="device"`` and ``device_clouds=True`` and anything else raises a ``ValueError``."""
     from .robot import FrankaSampler, franka_fk, frames_to_matrix
 
     assert collision_free or not expert, "expert trajectories need collision_free=True (checked start and goal)"
@@ -732,6 +1021,16 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     task = problems == "task"
     if task and not collision_free:
         raise ValueError("problems='task' poses checked starts and goals: it needs collision_free=True")
+    unknown = [k for k in kinds if k not in SCENE_KIND_CODES]
+    if unknown:
+        raise ValueError(f"kinds must be among {tuple(SCENE_KIND_CODES)}, got {unknown}")
+    if any(k in REFERENCE_KINDS for k in kinds) and M1 < 7:
+        raise ValueError(f"the kinds {REFERENCE_KINDS} need M1 >= 7 (a cubby has seven plates), got M1 = {M1}")
+    merge_rows = task and "merged_cubby" in kinds
+    if merge_rows and not (scene_source == "device" and device_clouds):
+        raise ValueError("kinds with 'merged_cubby' under problems='task' need scene_source='device' and device_clouds=True: "
+                         "the plates between the start's and the goal's pocket are removed PER ROW, after the problem is "
+                         "drawn, and the host source makes one scene (and one host cloud) for all the rows that share it")
 
     dev = torch.device(device)
     total = env_offset + B if total_envs is None else int(total_envs)
@@ -741,7 +1040,9 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     sid = gid % nscene  # environment g sits in scene g mod nscene
     if scene_source == "device":  # (this batch's rows and nothing else; S is ``make_task_scenes``' default)
         cloud = None
-        out = make_scenes_device(B, seed, kinds, M1, M2, S=8 if task else None, device=dev, scene_ids=torch.from_numpy(sid))
+        unmerged = torch.full((B, 2), -1, dtype=torch.int32, device=dev) if merge_rows else None
+        out = make_scenes_device(B, seed, kinds, M1, M2, S=8 if task else None, device=dev, scene_ids=torch.from_numpy(sid),
+                                 merge_pockets=unmerged)
     else:
         scn = (make_task_scenes if task else make_scenes)(nscene if scene_pool is not None else int(sid.max()) + 1 if B else 0,
                                                           seed, kinds, M1, M2)
@@ -754,6 +1055,8 @@ def make_problem_batch(B: int, seed: int = 0, device="cuda:0", kinds=("tabletop"
     if task:
         q, q_goal, valid, start_pose, task_pose, target_support = _task_problems(out, out["support_boxes"], out["support_kind"],
                                                                                  q, q_target, seed, env_offset)
+        if merge_rows:
+            target_support = _merge_task_rows(out, kinds, sid, valid, start_pose, task_pose, target_support, seed, M1, M2, dev)
         out.update(q_goal=q_goal, valid=valid, start_pose=start_pose, target_support=target_support,
                    **_task_region_keys(out["support_boxes"], out["support_kind"], target_support))
     elif collision_free:
